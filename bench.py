@@ -18,7 +18,17 @@ Paths (--path):
   fused              one mapf_step_observe_random launch per step (the path a
                      policy-in-the-loop rollout uses), hipGraph replays of 24 steps
   split              mapf_step_random + mapf_observe, two launches per step
-The breakdown also times the one-launch-per-step path.
+
+A plain run sets up, warms up, times --steps steps down the chosen path, writes that path's
+last-step outputs if --dump-outputs DIR is given, and prints the result line (metric, value,
+ms_per_step, the workload).  --full adds everything else to the same line, each measured in
+runs of its own after the timed region: the per-kernel breakdown (which also times the
+one-launch-per-step path), the roofline figures, the other paths and the CPU baseline.
+
+--dump-outputs DIR: what a caller of the timed path receives from its last timed step --
+actions, obs, vec and every step output -- as DIR/<name>.npy (float32; integer outputs as
+float64, exact), the envs of a fixed seeded sample where all of them would exceed ~48 MB.
+The workload is seeded, so the same arguments give the same files on every run.
 
 Default workload (N=1): BASELINE config c2 -- 4096 envs x 8 agents, 20x20
 generalised warehouse, FOV 11, 6 channels, Human with random goals,
@@ -215,6 +225,27 @@ def pmc_traffic_per_step(B, N, H, W, F, C, kernel, slots=False):
     return t / rep.get("steps_per_launch", 1) / 1e6
 
 
+DUMP_BUDGET = 48e6      # bytes of .npy files per rank (--dump-outputs)
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """Write `arrays` (name -> device tensor, every one with the envs as its leading dimension)
+    as dirname/<name>.npy: floats as float32, integers as float64.  Where all envs would exceed
+    DUMP_BUDGET, the same seeded sample of envs (ascending) of every array.  Returns (envs
+    written, envs)."""
+    os.makedirs(dirname, exist_ok=True)
+    first = next(iter(arrays.values()))
+    B = first.shape[0]
+    per_env = sum(a[0].numel() * (4 if a.dtype.is_floating_point else 8) for a in arrays.values())
+    keep = min(B, max(1, int(DUMP_BUDGET // per_env)))
+    envs = np.sort(np.random.default_rng(seed).choice(B, keep, replace=False)) if keep < B else np.arange(B)
+    sel = torch.from_numpy(envs).to(first.device)
+    for name, a in arrays.items():
+        x = a.index_select(0, sel).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), x.astype(np.float32 if x.dtype.kind == "f" else np.float64))
+    return keep, B
+
+
 def launch_ranks(n):
     """`--gpus N` with no launcher around us: start N ranks of this same command under
     torch.distributed.run (one process per GPU, 127.0.0.1 rendezvous) as a CHILD process and
@@ -265,7 +296,15 @@ def main():
                          "split evenly over the ranks")
     ap.add_argument("--no-paths", action="store_true",
                     help="skip the per-path breakdown (slot-buffer rollout, one launch per step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure, after the timed steps, the per-kernel breakdown, the roofline figures, "
+                         "the other paths and the CPU baseline (--no-paths, --no-cpu leave those two out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs of the timed path as DIR/<name>.npy "
+                         "(ranks above 0: DIR/rank<r>/)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.split:
         args.path = "split"
     preset = PRESETS[args.config]
@@ -346,7 +385,8 @@ def main():
         else:
             env.step_observe(acts, obs, vec, random_policy=True)
 
-    # warm-up: the timed path and the per-step path of the breakdown
+    # warm-up: --warmup steps, one launch each (the per-step path, which --full's breakdown times
+    # too), then one launch of the rollout path where that is the timed one
     for _ in range(args.warmup):
         one_step()
     if path == "rollout":
@@ -374,6 +414,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    n = 0
     if path == "rollout":
         done = 0
         while done < K:
@@ -395,7 +436,75 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # Per-kernel timing: HIP events around each launch on the launch stream
+    # what the timed path's last step handed its caller: slot n-1 of the last launch's rollout
+    # buffers, else the [B]-leading buffers every step re-writes
+    dumped = None
+    if args.dump_outputs:
+        if roll is not None:
+            last = dict(actions=roll["actions"][n - 1], obs=roll["obs"][n - 1], vec=roll["vec"][n - 1],
+                        **{k: v[n - 1] for k, v in roll["out"].items()})
+        else:
+            last = dict(actions=acts, obs=obs, vec=vec, **env.out)
+        dumped = dump_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"), last)
+
+    def head():
+        """The result line of a plain run; --full adds its own measurements to it."""
+        return {
+            "metric": METRIC, "value": round(world_size * B * N * K / elapsed, 1), "unit": "agent-steps/s",
+            "n_gpus": world_size,
+            "steps": K, "warmup": args.warmup, "ms_per_step": round(elapsed / K * 1e3, 4),
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "int32",
+            "data": "synthetic (seeded warehouse episodes on device, uniform random policy)",
+            "config": {"workload": f"{args.config}: {B} envs x {N} agents per GPU, {H}x{W} "
+                                   f"{'warehouse' if shared else 'random p=0.3 maps (one per env)'}, FOV {F}, "
+                                   f"{C} channels, random policy, env.step+observe",
+                       "num_envs_per_gpu": B, "num_agents": N, "grid": [H, W], "fov": F, "channels": C,
+                       "human": "Human (random goals, device A*)", "goals": "lifelong, random", "keep_bfs": True,
+                       "path": path + (f" (T={T} steps per launch, " + (f"[{TS}]-slot rollout buffers" if roll
+                                                                         else "[B] buffers re-written in place") + ")"
+                                       if path == "rollout" else ""),
+                       "kernel_form": env.rollout_plan(slots=roll is not None) if path == "rollout" else None,
+                       "total_envs": B * world_size,
+                       "parallelism": f"env-shards x{world_size}",
+                       "devices_used": devices_used,
+                       "collective_backend": backend if world_size > 1 else None},
+        }
+
+    def finish(line, counters):
+        """Rank 0: the device counters and the run's labels into `line`."""
+        line["device_counters"] = [int(x) for x in counters[:8]]
+        if dumped:
+            line["outputs_dumped"] = {"dir": args.dump_outputs, "envs": dumped[0], "of_envs": dumped[1],
+                                      "sample": "all" if dumped[0] == dumped[1] else "seeded (0), ascending"}
+        # States the reference does not survive, counted and resolved on the device (DESIGN.md §5):
+        # empty viable sets (it raises) and fixActions deadlocks (it never returns).  Any other
+        # counter is an impossible state: the line is then marked invalid.
+        line["reference_unsurvivable_states"] = {"empty_viable": int(counters[2]), "fix_deadlock": int(counters[1])}
+        bad = {i: int(counters[i]) for i in (0, 3, 4, 5, 6) if counters[i]}
+        if bad:
+            line["valid"] = False
+            line["invalid_reason"] = f"device error counters {bad}"
+            print(f"bench: device error counters {bad}", file=sys.stderr)
+        if devices_used < world_size:
+            line["rehearsal"] = (f"{world_size} ranks on {devices_used} GPU(s) (MAPF_BENCH_BACKEND={backend}): "
+                                 "exercises the multi-rank launch, barriers and max-over-ranks timing; "
+                                 "not a scaling result")
+        if B * N < 1024:
+            line["note"] = (f"{B * N} agents per GPU: one rollout step is a chain of dependent wave-level "
+                            "phases (latency-bound, a few us), so a single CPU thread stepping small "
+                            "batches can be faster; the GPU path is for thousands of envs (c2-c5)")
+
+    if not args.full:
+        if rank == 0:
+            line = head()
+            finish(line, env.counters())
+            print(json.dumps(line), flush=True)
+        env.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # --full from here on.  Per-kernel timing: HIP events around each launch on the launch stream
     # (torch's current stream, which the env launches on), direct launches.
     #  rollout: each mapf_rollout_random launch of T steps -- the roofline kernel;
     #  fused:   one step_observe launch per step (previous step's search riding in it);
@@ -504,8 +613,6 @@ def main():
     counters = env.counters()
 
     if rank == 0:
-        total_agent_steps = world_size * B * N * K
-        value = total_agent_steps / elapsed
         if path == "rollout":
             # the template instantiation the library launched (mapf_rollout_plan), e.g.
             # rollout_random_kernel<true,4> at c2 (slot buffers, the 16 waves of a CU in one workgroup)
@@ -518,24 +625,8 @@ def main():
         achieved = bpa * B * N * steps_pl / (kms * 1e-3) / 1e9
         traffic = pmc_traffic_per_step(B, N, H, W, F, C, kname, slots=roll is not None)
         ic_resident = path == "rollout" and roll is None and B * N * C * F * F * 4 < 128e6
-        line = {
-            "metric": METRIC, "value": round(value, 1), "unit": "agent-steps/s", "n_gpus": world_size,
-            "steps": K, "warmup": args.warmup, "ms_per_step": round(elapsed / K * 1e3, 4),
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "int32",
-            "data": "synthetic (seeded warehouse episodes on device, uniform random policy)",
-            "config": {"workload": f"{args.config}: {B} envs x {N} agents per GPU, {H}x{W} "
-                                   f"{'warehouse' if shared else 'random p=0.3 maps (one per env)'}, FOV {F}, "
-                                   f"{C} channels, random policy, env.step+observe",
-                       "num_envs_per_gpu": B, "num_agents": N, "grid": [H, W], "fov": F, "channels": C,
-                       "human": "Human (random goals, device A*)", "goals": "lifelong, random", "keep_bfs": True,
-                       "path": path + (f" (T={T} steps per launch, " + (f"[{TS}]-slot rollout buffers" if roll
-                                                                         else "[B] buffers re-written in place") + ")"
-                                       if path == "rollout" else ""),
-                       "kernel_form": env.rollout_plan(slots=roll is not None) if path == "rollout" else None,
-                       "total_envs": B * world_size,
-                       "parallelism": f"env-shards x{world_size}",
-                       "devices_used": devices_used,
-                       "collective_backend": backend if world_size > 1 else None},
+        line = head()
+        line.update({
             "breakdown_ms": {"rollout_launch": round(roll_ms, 4) if roll_ms else None,
                              "rollout_per_step": round(roll_ms / TR, 5) if roll_ms else None,
                              "rollout_steps_per_launch": TR if roll_ms else None,
@@ -558,27 +649,10 @@ def main():
                                        "Infinity Cache, so no HBM roofline applies (the HBM-bound form of the same work "
                                        "is the default slot-buffer path)" % (B * N * C * F * F * 4 / 1e6))
                          if ic_resident else "HBM: every store a fresh line" if roll is not None else "HBM"},
-            "device_counters": [int(x) for x in counters[:8]],
-        }
+        })
         if paths:
             line["paths"] = paths
-        # States the reference does not survive, counted and resolved on the device:
-        # empty viable sets (it raises) and fixActions deadlocks (it never returns).  Any other
-        # counter is an impossible state: the line is then marked invalid.
-        line["reference_unsurvivable_states"] = {"empty_viable": int(counters[2]), "fix_deadlock": int(counters[1])}
-        bad = {i: int(counters[i]) for i in (0, 3, 4, 5, 6) if counters[i]}
-        if bad:
-            line["valid"] = False
-            line["invalid_reason"] = f"device error counters {bad}"
-            print(f"bench: device error counters {bad}", file=sys.stderr)
-        if devices_used < world_size:
-            line["rehearsal"] = (f"{world_size} ranks on {devices_used} GPU(s) (MAPF_BENCH_BACKEND={backend}): "
-                                 "exercises the multi-rank launch, barriers and max-over-ranks timing; "
-                                 "not a scaling result")
-        if B * N < 1024:
-            line["note"] = (f"{B * N} agents per GPU: one rollout step is a chain of dependent wave-level "
-                            "phases (latency-bound, a few us), so a single CPU thread stepping small "
-                            "batches can be faster; the GPU path is for thousands of envs (c2-c5)")
+        finish(line, counters)
         if not args.no_cpu:
             # north_star: "1/2/4/8-GPU throughput and the CPU baseline reported in the same run" -- so
             # every line carries it, multi-rank ones too: rank 0 times it after the timed region and

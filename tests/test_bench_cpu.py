@@ -77,6 +77,34 @@ def test_all_cores_figure_is_labelled():
     assert "extrapolated" in line["all_host_cores_basis"]
 
 
+def test_dump_outputs_writes_a_seeded_bounded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: floats as float32, integers as float64 (exact); within the budget every env,
+    above it the same seeded, ascending sample of envs of every array, run after run."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(5)
+    arrays = dict(obs=torch.rand(10, 3, 5, generator=g),
+                  status=torch.randint(-3, 4, (10, 3), dtype=torch.int8, generator=g),
+                  shadow_goals=torch.randint(0, 1 << 30, (10,), dtype=torch.int32, generator=g))
+    per_env = 3 * 5 * 4 + 3 * 8 + 8
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == (10, 10)
+    for k, v in arrays.items():
+        x = np.load(tmp_path / "all" / f"{k}.npy")
+        assert x.dtype == (np.float32 if k == "obs" else np.float64)
+        assert np.array_equal(x, v.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * per_env + 1)
+    assert bench.dump_outputs(str(tmp_path / "a"), arrays) == (4, 10)
+    assert bench.dump_outputs(str(tmp_path / "b"), arrays) == (4, 10)
+    envs = np.sort(np.random.default_rng(0).choice(10, 4, replace=False))
+    written = 0
+    for k, v in arrays.items():
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert np.array_equal(a, b) and np.array_equal(a, v.numpy()[envs])
+        written += a.nbytes
+    assert written <= bench.DUMP_BUDGET
+
+
 def test_gpus_flag_launches_that_many_ranks(monkeypatch):
     """`bench.py --gpus N` with no launcher around it starts N ranks of the same
     command under torch.distributed.run (a child process; 127.0.0.1 rendezvous) and exits with its

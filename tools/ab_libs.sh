@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 for round in ${ROUNDS:-1 2}; do
   for c in ${CFGS:-c2 c4}; do
     for lib in ${LIBS:-libmapf.so libmapf_argptr.so}; do
-      MAPF_LIB=primal-ppo_amd/lib/$lib timeout -k 10 300 python3 bench.py --config $c --no-cpu --no-paths --steps ${BSTEPS:-512} \
+      MAPF_LIB=primal-ppo_amd/lib/$lib timeout -k 10 300 python3 bench.py --full --config $c --no-cpu --no-paths --steps ${BSTEPS:-512} \
         --warmup 16 ${BARGS:-} > gpurun_out/ablib.log 2>&1 || { rc=$?; tail -5 gpurun_out/ablib.log; exit $rc; }
       python3 -c "
 import json,sys

@@ -8,7 +8,7 @@ for round in ${ROUNDS:-1 2}; do
   for c in ${CFGS:-c4}; do
     for v in ${VARIANTS:-wide_prio=0 wide_prio=1}; do
       t=$v; [ "$t" = "-" ] && t=""
-      timeout -k 10 300 python3 bench.py --config $c --no-cpu --no-paths --steps ${BSTEPS:-512} --warmup 16 --tune "$t" ${BARGS:-} \
+      timeout -k 10 300 python3 bench.py --full --config $c --no-cpu --no-paths --steps ${BSTEPS:-512} --warmup 16 --tune "$t" ${BARGS:-} \
         > gpurun_out/abtune.log 2>&1 || { rc=$?; tail -5 gpurun_out/abtune.log; exit $rc; }
       python3 -c "
 import json,sys

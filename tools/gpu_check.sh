@@ -28,11 +28,11 @@ for s in $STEPS; do
       timeout -k 10 1000 python3 -m pytest ${PYTEST_ARGS:-tests} -m gpu -q > "$OUT/pytest_gpu.log" 2>&1
       rc=$?; echo "pytest rc=$rc"; tail -15 "$OUT/pytest_gpu.log"; stop_if_fatal $rc pytest ;;
     bench)
-      timeout -k 10 400 python3 bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
+      timeout -k 10 400 python3 bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
       rc=$?; echo "bench rc=$rc"; tail -3 "$OUT/bench.log"; stop_if_fatal $rc bench ;;
     sweep)
       for cfg in ${SWEEP:-"search_blocks=32" "search_blocks=64" "search_blocks=128"}; do
-        timeout -k 10 200 python3 bench.py --no-cpu --steps 2000 --path split --tune "$cfg" > "$OUT/sweep.log" 2>&1
+        timeout -k 10 200 python3 bench.py --full --no-cpu --steps 2000 --path split --tune "$cfg" > "$OUT/sweep.log" 2>&1
         rc=$?; echo "sweep $cfg rc=$rc $(python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(d['value'], d['breakdown_ms'])" "$OUT/sweep.log" 2>/dev/null)"
         stop_if_fatal $rc sweep
       done ;;
@@ -48,7 +48,7 @@ for s in $STEPS; do
     pmc)
       for ctr in WRITE_SIZE FETCH_SIZE; do
         (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --pmc $ctr --kernel-trace --output-format csv \
-          -d "$OUT/pmc_$ctr" -o run -- python3 "$ROOT/bench.py" --steps 64 --warmup 10 --no-cpu --graph-steps 0 \
+          -d "$OUT/pmc_$ctr" -o run -- python3 "$ROOT/bench.py" --full --steps 64 --warmup 10 --no-cpu --graph-steps 0 \
           --rollout-steps 32 --kernel-launches 4 ${PMC_ARGS:-}) > "$OUT/pmc_$ctr.log" 2>&1
         rc=$?; echo "pmc $ctr rc=$rc"; stop_if_fatal $rc pmc
       done
@@ -58,13 +58,13 @@ for s in $STEPS; do
       for grp in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS" "SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_INSTS_BRANCH" ${SQ_EXTRA:-}; do
         i=$((i+1))
         (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv \
-          -d "$OUT/sq_$i" -o run -- python3 "$ROOT/bench.py" --steps 64 --warmup 10 --no-cpu --graph-steps 0 \
+          -d "$OUT/sq_$i" -o run -- python3 "$ROOT/bench.py" --full --steps 64 --warmup 10 --no-cpu --graph-steps 0 \
           --rollout-steps 32 --kernel-launches 4) > "$OUT/sq_$i.log" 2>&1
         rc=$?; echo "sq $i ($grp) rc=$rc"; stop_if_fatal $rc sq
       done ;;
     prof)
       (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/prof" -o run -- python3 "$ROOT/bench.py" --no-cpu ${PROF_ARGS:-}) > "$OUT/prof.log" 2>&1
+        -d "$OUT/prof" -o run -- python3 "$ROOT/bench.py" --full --no-cpu ${PROF_ARGS:-}) > "$OUT/prof.log" 2>&1
       rc=$?; echo "prof rc=$rc"; tail -3 "$OUT/prof.log"; stop_if_fatal $rc prof
       find "$OUT/prof" -name "*stats*" | head ;;
   esac

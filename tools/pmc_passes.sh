@@ -13,7 +13,7 @@ for p in ${PASSES:-c2 c2inplace c4 c4inplace c5 c5inplace}; do
   for ctr in WRITE_SIZE FETCH_SIZE; do
     rm -rf "$OUT/pmc_${p}_$ctr"
     (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 240 rocprofv3 --pmc $ctr --kernel-trace --output-format csv \
-      -d "$OUT/pmc_${p}_$ctr" -o run -- python3 "$ROOT/bench.py" $args --steps 64 --warmup 4 --no-cpu --no-paths \
+      -d "$OUT/pmc_${p}_$ctr" -o run -- python3 "$ROOT/bench.py" --full $args --steps 64 --warmup 4 --no-cpu --no-paths \
       --rollout-steps 32 --kernel-launches 4) > "$OUT/pmc_${p}_$ctr.log" 2>&1
     rc=$?; echo "pmc $p $ctr rc=$rc"; [ $rc -eq 0 ] || { tail -5 "$OUT/pmc_${p}_$ctr.log"; exit $rc; }
   done

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
-BARGS="${BENCH_ARGS:---no-cpu --steps 600}"
+BARGS="--full ${BENCH_ARGS:---no-cpu --steps 600}"   # --full: the breakdown and roofline printed below
 for cfg in "$@"; do
   env $cfg timeout -k 10 200 python3 bench.py $BARGS > gpurun_out/sweep.log 2>&1
   rc=$?
