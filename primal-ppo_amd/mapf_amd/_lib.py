@@ -7,6 +7,8 @@ C signature.  Loading fails loudly when the library is missing.
 import ctypes
 import os
 
+import torch
+
 from .config import MapfConfig
 
 PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -104,8 +106,6 @@ SIGNATURES = {
     "mapf_cast_f32_to_f16_multi_flip": (ctypes.c_int, [P, P, P, P, P, I32, P]),
     "mapf_tokens_layernorm_train": (ctypes.c_int, [P, P, P, P, P, I64, I32, F32, P, U32, P, P, F32, P, P]),
     "mapf_tokens_train_bwd": (ctypes.c_int, [P, P, P, P, P, P, P, P, I64, I32, F32, P, U32, P]),
-    "mapf_optim_unscale_clip_adam": (ctypes.c_int, [P, P, P, P, P, P, I32, P, F32, F32, F32, F32, F32, P, P, P,
-                                                    I64, P]),
     "mapf_cast_f16_to_f32_multi": (ctypes.c_int, [P, P, P, I32, P]),
     "mapf_layernorm_bwd_f16": (ctypes.c_int, [P, I64, P, P, P, P, P, P, P, I64, I32, ctypes.c_float, P]),
     "mapf_layernorm_dropout_bwd_f16": (ctypes.c_int, [P, P, P, P, P, P, P, P, P, I64, I32, F32, F32, P, U32, P]),
@@ -170,3 +170,20 @@ def check(rc):
         msg = lib().mapf_last_error()
         raise RuntimeError(f"libmapf error {rc}: {msg.decode() if msg else ''}")
     return rc
+
+
+def call(name, *args, check_rc=True, device=None):
+    """One launch of a policy entry point (csrc/mapf_policy.hip, mapf_ppo.hip: `void *stream` last):
+    a tensor argument passes as its data_ptr(), None as NULL, anything else (sizes, floats, an address
+    with an offset as a plain int, a ctypes array) as it is; the trailing stream is the current one of
+    the first tensor argument's device (or of `device`, for a call whose pointers are all in arrays).
+    Raises on a non-zero return code unless check_rc is False; returns the code."""
+    raw = []
+    for a in args:
+        if isinstance(a, torch.Tensor):
+            if device is None:
+                device = a.device
+            a = a.data_ptr()
+        raw.append(a)
+    rc = getattr(lib(), name)(*raw, torch.cuda.current_stream(device).cuda_stream)
+    return check(rc) if check_rc else rc

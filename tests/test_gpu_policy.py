@@ -444,7 +444,7 @@ def test_hip_attention_autograd_vs_sdpa(n, first, bwd_form):
 
 
 def _attention_vs_sdpa(n, first):
-    from mapf_amd.net import _HipAttention
+    from mapf_amd.train_ops import _HipAttention
     g = torch.Generator(device="cuda").manual_seed(n + 100 * first)
     b, d, scale = 37, 512, 512 ** -0.5
     gout = torch.randn(b, 1 if first else n, d, device="cuda", generator=g).half()

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("rows,n_in,n_out", [(34816, 512, 1536), (34816, 512, 512), (8192, 512, 1024)])
 def test_split_weight_gradient_matches_autocast_linear(rows, n_in, n_out):
-    from mapf_amd.net import _SplitKLinear, _train_linear
+    from mapf_amd.train_ops import _SplitKLinear, _train_linear
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     g = torch.Generator(device="cuda").manual_seed(rows + n_out)
@@ -41,13 +41,18 @@ def test_split_weight_gradient_matches_autocast_linear(rows, n_in, n_out):
           f"{_SplitKLinear.out_dtype_ok}")
 
 
-@pytest.mark.parametrize("rows,strided", [(2048, False), (2048, True), (4095, False), (77, True), (1, False)])
-def test_short_linear_matches_autocast_linear(rows, strided):
+@pytest.mark.parametrize("rows,strided,gy_off", [(2048, False, 0), (2048, True, 0), (4095, False, 0), (77, True, 0),
+                                                 (1, False, 0), (77, False, 4)],
+                         ids=["2048-False", "2048-True", "4095-False", "77-True", "1-False", "77-misaligned"])
+def test_short_linear_matches_autocast_linear(rows, strided, gy_off):
     """net._LinearBG (the training forward's short 2-D fp16 linears via _train_linear: torch's addmm and
     backward GEMMs, the bias gradient from mapf_colsum_f16's one-launch column sum) against autocast
     F.linear: output bit-identical, input / weight gradients equal (the same GEMMs), the bias gradient
-    within fp16 rounding of another fp32 summation order.  strided: x is token 0 of a [rows, 17, 512]."""
-    from mapf_amd.net import _LinearBG, _train_linear
+    within fp16 rounding of another fp32 summation order.  strided: x is token 0 of a [rows, 17, 512].
+    gy_off: the upstream gradient is a contiguous view gy_off elements into a larger buffer -- 4 fp16 = 8 bytes,
+    so not 16-byte aligned: mapf_colsum_f16 then takes its partials path (G * C floats of work space) even
+    for these few rows, and the bias-gradient check against the fp64 column sum covers it."""
+    from mapf_amd.train_ops import _LinearBG, _train_linear
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     g = torch.Generator(device="cuda").manual_seed(rows + strided)
@@ -55,10 +60,15 @@ def test_short_linear_matches_autocast_linear(rows, strided):
     w0 = (torch.randn(512, 512, device="cuda", generator=g) / 512 ** 0.5).half()
     b0 = (torch.randn(512, device="cuda", generator=g) * 0.1).half()
     gy = torch.randn(rows, 512, device="cuda", generator=g).half()
-    res, calls = [], []
-    orig = _LinearBG.forward
+    if gy_off:
+        buf = torch.empty(rows * 512 + 2 * gy_off, dtype=torch.float16, device="cuda")
+        gy = buf[gy_off:gy_off + rows * 512].view(rows, 512).copy_(gy)
+        assert gy.is_contiguous() and gy.data_ptr() % 16 == 2 * gy_off == 8
+    res, calls, seen = [], [], []
+    orig, orig_bwd = _LinearBG.forward, _LinearBG.backward
     try:
         _LinearBG.forward = staticmethod(lambda ctx, *a: calls.append(1) or orig(ctx, *a))
+        _LinearBG.backward = staticmethod(lambda ctx, d: seen.append(d.data_ptr() % 16) or orig_bwd(ctx, d))
         for own in (True, False):
             x3, w, b = (t.clone().requires_grad_(True) for t in (xs, w0, b0))
             x = x3[:, 0]
@@ -67,8 +77,9 @@ def test_short_linear_matches_autocast_linear(rows, strided):
             y.backward(gy)
             res.append((y.detach(), x3.grad, w.grad, b.grad))
     finally:
-        _LinearBG.forward = orig
+        _LinearBG.forward, _LinearBG.backward = orig, orig_bwd
     assert calls == [1]
+    assert seen == [2 * gy_off], seen          # the backward saw the gradient at that address
     assert torch.equal(res[0][0], res[1][0])
     torch.testing.assert_close(res[0][1], res[1][1], rtol=0, atol=0)
     torch.testing.assert_close(res[0][2], res[1][2], rtol=1e-3, atol=1e-3)
@@ -85,7 +96,7 @@ def test_qkv_first_matches_two_linears(b):
     backward) against the two _train_linear calls it replaces (a _LinearBG on x[:, 0] and a _SplitKLinear on
     x): q and kv bit-identical; kv's weight and both bias gradients equal (the same kernels); x's gradient and
     q's weight gradient within fp16 rounding (token 0's rows: one fused accumulate instead of an fp16 add)"""
-    from mapf_amd.net import _QKVFirst, _train_linear
+    from mapf_amd.train_ops import _QKVFirst, _train_linear
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     n, d = 17, 512
@@ -140,7 +151,7 @@ def test_hip_layernorm_matches_autocast_layernorm(rows):
     """net._HipLayerNorm (mapf_layernorm_f16 forward, mapf_layernorm_bwd_f16 backward) against torch's
     LayerNorm under autocast followed by the fp16 cast the next linear makes: z within one fp16 ulp,
     dx / dgamma / dbeta to fp32 rounding of the reductions."""
-    from mapf_amd.net import _HipLayerNorm
+    from mapf_amd.train_ops import _HipLayerNorm
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     g = torch.Generator(device="cuda").manual_seed(rows)
@@ -285,7 +296,8 @@ def test_hip_conv_matches_miopen_conv(cin, cout, ks, pad, hw, b):
     weight gradient MIOpen's) against F.conv2d on the same fp16 NHWC tensors, MIOpen's
     deterministic algorithms: output and data gradient to fp16 rounding of another fp32 summation order
     (2e-3 relative in norm, elementwise 1e-2 of the tensor's scale), weight gradient equal (the same call)."""
-    from mapf_amd.net import SCRIMPNet, _HipConv
+    from mapf_amd.net import SCRIMPNet
+    from mapf_amd.train_ops import _HipConv
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     g = torch.Generator(device="cuda").manual_seed(cin + cout + hw)
@@ -317,7 +329,8 @@ def test_hip_conv_matches_miopen_conv(cin, cout, ks, pad, hw, b):
 def test_training_forward_convs_take_hip_conv():
     """SCRIMPNet's training forward (GPU, autocast, grad) runs conv1a .. conv2b through _HipConv
     (conv1 from the 6-channel observation and conv3 stay MIOpen's: shapes the kernel does not have)"""
-    from mapf_amd.net import SCRIMPNet, _HipConv
+    from mapf_amd.net import SCRIMPNet
+    from mapf_amd.train_ops import _HipConv
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     net = SCRIMPNet(numChannel=6, num_agents=8, fov=9).cuda().to(memory_format=torch.channels_last)
@@ -333,7 +346,7 @@ def test_training_forward_convs_take_hip_conv():
         out[1].float().sum().backward()
     finally:
         _HipConv.forward = orig
-    # the un-pooled layers take the bias + ReLU in the conv's epilogue (SCRIMPNet.conv_bias_relu)
+    # the un-pooled layers take the bias + ReLU in the conv's epilogue (_HipConv with a bias)
     assert calls == [((128, 128, 3, 3), True), ((128, 128, 3, 3), False), ((256, 128, 2, 2), True),
                      ((256, 256, 2, 2), True), ((256, 256, 2, 2), False)], calls
     # each carries its flipped, transposed weight from _CastParams' launch (mapf_cast_f32_to_f16_multi_flip)
@@ -346,7 +359,7 @@ def test_hip_conv_bias_relu_epilogue_equals_two_passes(cin, cout, ks, pad, hw, b
     """_HipConv with the bias (bias + ReLU in the conv kernel's epilogue; backward: mapf_relu_bias_bwd_f16
     then the conv's own gradients) == _BiasReLU over _HipConv's raw output: output, data, weight and bias
     gradients bit-identical (the same roundings: fp16(fp16(acc) + b), the same backward kernels)"""
-    from mapf_amd.net import _BiasReLU, _HipConv
+    from mapf_amd.train_ops import _BiasReLU, _HipConv
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     g = torch.Generator(device="cuda").manual_seed(3 * cin + cout)
@@ -411,7 +424,7 @@ def test_drop_res_ln_matches_torch_chain(p, strided):
     fp16 branch, then _HipLayerNorm -- given the SAME mask: p = 0 bit-identical forward and gradients;
     p = 0.2: the mask the kernel drew is read back from its output (x - res == 0 exactly where dropped)
     and fed to the chain; keep rate 0.8 +- 0.01.  strided: res is token 0 of a [b, 17, 512] stream."""
-    from mapf_amd.net import _DropResLN, _HipLayerNorm
+    from mapf_amd.train_ops import _DropResLN, _HipLayerNorm
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     g = torch.Generator(device="cuda").manual_seed(3)
@@ -457,7 +470,7 @@ def test_tokens_ln_matches_torch_chain(p, B):
     exactly 0 where dropped): x and z bit-identical; gradients of A, VV, cls, pos, gamma, beta within fp32
     summation order (1e-5 relative in norm; dVV, fp16, within 1e-3); keep rate 1 - p +- 0.01.  B = 301: a
     ragged last block of the backward's per-block sums."""
-    from mapf_amd.net import _HipLayerNorm, _TokensLN
+    from mapf_amd.train_ops import _HipLayerNorm, _TokensLN
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     g = torch.Generator(device="cuda").manual_seed(B + int(10 * p))
@@ -494,7 +507,8 @@ def test_training_forward_takes_tokens_ln():
     """SCRIMPNet's training forward (GPU, autocast, grad) builds the tokens through _TokensLN, and with
     SCRIMPNet.fused_tokens off through torch's chain: outputs within fp16 rounding, every gradient within
     2e-2 (relative norm) -- dropout off (eval), deterministic convolutions"""
-    from mapf_amd.net import SCRIMPNet, _TokensLN
+    from mapf_amd.net import SCRIMPNet
+    from mapf_amd.train_ops import _TokensLN
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     torch.manual_seed(1)
@@ -533,7 +547,7 @@ def test_gelu_dropout_matches_torch(p):
     """net._GeluDropout against F.gelu then the same mask (read back from the output) on fp16: p = 0
     bit-identical forward and gradient (torch's fp16 GELU and GeluBackward compute in fp32); p = 0.2
     to fp16 rounding (torch scales after the GELU's rounding the same way), keep rate 0.8 +- 0.01."""
-    from mapf_amd.net import _GeluDropout
+    from mapf_amd.train_ops import _GeluDropout
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     g = torch.Generator(device="cuda").manual_seed(4)
@@ -608,3 +622,87 @@ def test_training_forward_fused_residuals_equal_unfused():
         net.transformer.layers[-1][1].fn.fn.do2.p = 0.0
     outs = [net(obs, vec)[1].detach() for _ in range(2)]
     assert not torch.equal(outs[0], outs[1])
+
+
+def test_hip_training_forward_backward_matches_torch_autocast():
+    """SCRIMPNet's training forward + backward on the HIP ops (SCRIMPNet.hip_train on: A) against torch's own
+    fp16 autocast pipeline on the GPU (hip_train off: B -- MIOpen, SDPA, nn.LayerNorm) with the same net in
+    fp32 on the CPU (C) as the reference: seeded init, eval() (p = 0: the fused ops still run), one seeded
+    64 x 8 batch (8,704 token rows: every op at the default thresholds), the loss a fixed seeded linear
+    functional of the seven outputs (normal weights / 512 rows) times 2^8.  A runs every HIP Function at least once, B none.  With
+    d(X) = |X - C| / |C| (2-norms), every output and every parameter's gradient has
+    d(A) <= 2 * d(B) + 1e-6: two fp16 pipelines that round at different points, where a wrong backward would
+    be off by order 1.
+
+    Measured (MI355X), d(A) / d(B):
+      policy 1.386e-03 / 1.389e-03   value 7.530e-04 / 7.294e-04   blocking 4.530e-04 / 4.960e-04
+      policy_sig 6.400e-04 / 6.580e-04   x 9.419e-04 / 9.416e-04   logits 1.368e-03 / 1.386e-03
+      cost_value 7.839e-04 / 7.688e-04
+      gradients of conv1 .. conv2b (weights, biases): 2.2e-02 .. 5.9e-02 / 2.3e-02 .. 6.0e-02
+        (conv1.weight 5.856e-02 / 5.979e-02, conv2b.bias 2.169e-02 / 2.335e-02)
+      of conv3, fully_connected_1..3: 8.9e-03 .. 2.2e-02 / 9.0e-03 .. 2.3e-02
+      of token_wV, pos_embedding, cls_token, the encoder, nn_same and the heads (46 tensors):
+        2.1e-04 .. 1.6e-03 / 2.1e-04 .. 1.6e-03; token_wA: 0 / 0 (a softmax over one element)
+      largest d(A) / d(B): 1.14 (policy_layer.bias 5.490e-04 / 4.797e-04), next 1.06 (value_layer.weight);
+      smallest 0.58 (blocking_layer.bias 9.548e-04 / 1.636e-03)."""
+    import copy
+    from mapf_amd import train_ops as T
+    from mapf_amd.net import SCRIMPNet
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need an MI355X")
+    torch.manual_seed(0)
+    ref = SCRIMPNet(numChannel=6, num_agents=8, fov=9).eval()
+    net = copy.deepcopy(ref).cuda().to(memory_format=torch.channels_last)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    obs = (torch.rand(64, 8, 6, 9, 9, device="cuda", generator=g) < 0.3).float()
+    vec = torch.randn(64, 8, 4, device="cuda", generator=g)
+    gw = torch.Generator().manual_seed(2)
+    # normal weights over the 512 agent rows: each output element's gradient is O(2^8 / 512), the size the PPO
+    # loss (a mean over the rows) gives it at GradScaler's 2^8 -- unit weights on all of x overflow fp16 in both
+    # fp16 pipelines' weight gradients
+    ws = [torch.randn(64, 8, k, generator=gw) / 512 for k in (5, 1, 1, 5, 512, 5, 1)]
+    names = ["policy", "value", "blocking", "policy_sig", "x", "logits", "cost_value"]
+    pnames = [n for n, _ in net.named_parameters()]
+
+    def run(m, obs, vec, ws):
+        m.zero_grad()
+        with torch.autocast(device_type=obs.device.type, enabled=obs.is_cuda):
+            out = m(obs, vec)
+        assert [tuple(o.shape) for o in out] == [tuple(w.shape) for w in ws]
+        (sum((o.float() * w).sum() for o, w in zip(out, ws)) * 2.0 ** 8).backward()
+        return ([o.detach().float().cpu() for o in out],
+                [None if p.grad is None else p.grad.detach().float().cpu() for p in m.parameters()])
+
+    ops = ["_HipConv", "_BiasReLUPool", "_TokensLN", "_DropResLN", "_GeluDropout", "_HipAttention", "_SplitKLinear",
+           "_QKVFirst", "_LinearBG", "_CastParams"]
+    origs = {n: getattr(T, n).forward for n in ops}
+    calls = {True: [], False: []}
+    res = {}
+    old = torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark
+    torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = True, False
+    try:
+        for hip in (True, False):
+            SCRIMPNet.hip_train = hip
+            for n in ops:
+                getattr(T, n).forward = staticmethod(
+                    lambda ctx, *a, n=n, hip=hip: calls[hip].append(n) or origs[n](ctx, *a))
+            res[hip] = run(net, obs, vec, [w.cuda() for w in ws])
+    finally:
+        SCRIMPNet.hip_train = True
+        for n in ops:
+            getattr(T, n).forward = origs[n]
+        torch.backends.cudnn.deterministic, torch.backends.cudnn.benchmark = old
+    C = run(ref, obs.cpu(), vec.cpu(), ws)
+    assert set(calls[True]) == set(ops), sorted(set(ops) - set(calls[True]))
+    assert calls[False] == [], calls[False]
+    bad = []
+    for k, title in ((0, names), (1, ["d " + n for n in pnames])):
+        for name, a, b, c in zip(title, res[True][k], res[False][k], C[k]):
+            assert (a is None) == (b is None) == (c is None), name
+            if c is None:
+                continue
+            da, db = (((x - c).norm() / c.norm().clamp_min(1e-30)).item() for x in (a, b))
+            print(f"{name:50s} d(A) {da:.3e}  d(B) {db:.3e}")
+            if not da <= 2 * db + 1e-6:
+                bad.append((name, da, db))
+    assert not bad, bad

@@ -77,7 +77,7 @@ def _train(m, z):
 @pytest.mark.parametrize("split_k", [False, True])
 @pytest.mark.parametrize("graph", [False, True])
 def test_device_update_matches_reference_update(two_agents, graph, split_k, monkeypatch):
-    from mapf_amd.net import _SplitKLinear
+    from mapf_amd.train_ops import _SplitKLinear
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     if split_k:        # the 17-token layers' split weight gradient (34,816+ rows in real minibatches)
@@ -132,7 +132,7 @@ def test_relu_epilogues_keep_nan_like_torch():
     """_BiasReLU / _BiasReLUPool with NaNs in the conv output: forward and gradient equal torch's
     F.relu / max_pool2d on the same fp16 arithmetic, NaNs included (max_pool2d's argmax takes the
     window's NaN; threshold_backward passes the gradient where the output is NaN)."""
-    from mapf_amd.net import _BiasReLU, _BiasReLUPool
+    from mapf_amd.train_ops import _BiasReLU, _BiasReLUPool
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
     g = torch.Generator(device="cuda").manual_seed(5)

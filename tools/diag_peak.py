@@ -1,6 +1,7 @@
 """Peak device memory of Model.train (256 x 8 rows, graphed: 2 eager warm-ups + capture + replays)
-with round 5's training-path features toggled one at a time (tests/test_gpu_rollout.py bounds the
-driver block's peak at 2 GiB)."""
+with the training path's switches set from the argument -- "hip": SCRIMPNet.hip_train (else torch's
+autocast forward), "fused": _Encoder.fused_train, "split": 4 row chunks in _SplitKLinear (else never split)
+(tests/test_gpu_rollout.py bounds the driver block's peak at 2 GiB)."""
 import json
 import os
 import sys
@@ -13,10 +14,11 @@ import torch  # noqa: E402
 def run(feat):
     from mapf_amd import net as N
     from mapf_amd.model import Model
+    from mapf_amd.train_ops import _SplitKLinear
     from test_gpu_update_graph import _batch
-    N.SCRIMPNet.cast_params = "cast" in feat
-    N._PreNorm.hip_layernorm = "ln" in feat
-    N._SplitKLinear.SPLIT = 4 if "split" in feat else 10 ** 9
+    N.SCRIMPNet.hip_train = "hip" in feat
+    N._Encoder.fused_train = "fused" in feat
+    _SplitKLinear.SPLIT = 4 if "split" in feat else 10 ** 9
     torch.manual_seed(0)
     m = Model(0, "cuda", global_model=True, numChannel=6, num_agents=8, fov=9)
     g = torch.Generator(device="cuda").manual_seed(1)

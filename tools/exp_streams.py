@@ -1,6 +1,6 @@
 """Experiment: does the c3 acting forward gain from running batch chunks on two HIP streams (kernels of
 different kinds overlapping each other's latency / VALU-bound phases)?  Times SCRIMPNet's acting
-forward (no grad, _forward_fused) on 4096 x 8 agents: whole batch; K chunks in order on one stream;
+forward (no grad, acting.forward_fused) on 4096 x 8 agents: whole batch; K chunks in order on one stream;
 K chunks alternating over two streams.  Prints one JSON line.
 
     python tools/exp_streams.py [--envs 4096] [--chunks 2] [--reps 10]

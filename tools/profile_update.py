@@ -24,7 +24,8 @@ def main():
     ap.add_argument("--split", type=int, default=None, help="net._SplitKLinear.SPLIT (row chunks)")
     ap.add_argument("--fp16-partials", action="store_true", help="split weight gradients with fp16 partials")
     ap.add_argument("--ab", default=None,
-                    help="A/B a SCRIMPNet class switch (e.g. conv3_gemm, hip_conv): captured updates with it on / off, "
+                    help="A/B a training switch (hip_train, fused_tokens, _Encoder.fused_train, _SelfAttention.hip_attention, "
+                         "_SplitKLinear.SPLIT=8,16, _SplitKLinear.MIN_ROWS=...): captured updates with it on / off, "
                          "alternating, each a fresh capture; prints one JSON line and exits")
     ap.add_argument("--shapes", action="store_true", help="profile eager updates grouped by aten op + input shapes")
     args = ap.parse_args()
@@ -34,7 +35,7 @@ def main():
     from mapf_amd.maps import generate_warehouse
     from mapf_amd.model import Model
     from mapf_amd.runner import DeviceRunner
-    from mapf_amd.net import _SplitKLinear
+    from mapf_amd.train_ops import _SplitKLinear
     if args.split:
         _SplitKLinear.SPLIT = args.split
     if args.fp16_partials:
@@ -57,10 +58,9 @@ def main():
     import json
     if args.ab:
         from mapf_amd import net as netmod
-        spec, _, vals = args.ab.partition("=")   # "conv3_gemm", "_LinearBG.enabled" or "_SplitKLinear.SPLIT=8,16"
+        spec, _, vals = args.ab.partition("=")   # "hip_train", "_Encoder.fused_train" or "_SplitKLinear.SPLIT=8,16"
         head, _, tail = spec.partition(".")
-        owner, attr = ((model, tail) if head == "model" else      # "model.fused_optim": the Model instance's
-                       (getattr(netmod, head), tail) if tail else (netmod.SCRIMPNet, spec))
+        owner, attr = (getattr(netmod, head), tail) if tail else (netmod.SCRIMPNet, spec)
         if vals:
             choices = [type(getattr(owner, attr))(v) for v in vals.split(",")]
         else:
