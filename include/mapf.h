@@ -196,7 +196,24 @@ int mapf_step_observe_random(mapf_env *env, int32_t *actions_out, const mapf_ste
  * [T][B][N], every out field [T][...], obs [T][B][N][C][F][F], vec [T][B][N][4]),
  * i.e. rollout buffers; slots = 0: every step overwrites the same [B]-leading
  * buffers.  Each wave of the one-launch kernel owns one env and loops step ->
- * observe -> its own search work, so steps overlap other envs' store drains. */
+ * observe -> its own search work, so steps overlap other envs' store drains.
+ *
+ * `slots` is a bit set.  MAPF_SLOTS (bit 0) is the meaning above.
+ * MAPF_SLOTS_BAND_CLEAN (bit 1) is a promise by the caller: the config-static
+ * zero band of every slot passed (channel 5 of every agent while use_hp is off:
+ * floats [5*F*F, 6*F*F) of each [C][F][F] block, 0.0 at every step) already
+ * holds zeros -- typically because an earlier launch of this handle wrote these
+ * very slots without the bit and nothing else has written them since.  The
+ * pair-lane kernel (mapf_rollout_random_fused == 1) then leaves out the stores
+ * that lie wholly inside the band, in aligned pieces (mapf_obs_band_skip gives the
+ * exact set): at c2 2,577 of 3,001 bytes per agent-step are written.  Every
+ * other byte, and every other output, is written as without the bit.  The bit
+ * is ignored -- everything is stored -- where no such band exists (use_hp on,
+ * num_channel < 6, fov > 11), without MAPF_SLOTS, and in the one-wave-per-env
+ * and per-step forms.  The library keeps no record of buffers: an address says
+ * nothing about its content, so only the caller can make this promise. */
+#define MAPF_SLOTS 1
+#define MAPF_SLOTS_BAND_CLEAN 2
 int mapf_rollout_random(mapf_env *env, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
                         float *obs, float *vec, void *stream);
 /* Which kernel mapf_rollout_random runs for this configuration (0: T per-step
@@ -207,6 +224,15 @@ int mapf_rollout_random(mapf_env *env, int32_t T, int32_t slots, int32_t *action
  * configuration whose per-env LDS (map rows, observation bit-stream, BFS image)
  * fits 64 KiB: up to 64 agents, per-env maps, the BFS channel (c4, c5). */
 int mapf_rollout_random_fused(const mapf_env *env);
+/* The stores a MAPF_SLOTS_BAND_CLEAN launch leaves out, computed on the host (no device call) by
+ * the function the kernel runs: for one env whose observation slice [N][C][F][F] starts at byte
+ * address byte_offset (a multiple of 16; only its value modulo the unit matters), skip[q] = 1 iff
+ * float4 q of the slice is not stored, for q < min(n, float4s per env).  A float4 is skipped iff
+ * the unit-aligned `unit` bytes around it (16, 64 or 128) lie wholly inside one agent's zero band.
+ * unit = 0: the unit the kernel uses (64).  For units above 16 the set depends on the slice's
+ * address: pass the address of the very slot and env asked about, obs + ((t * B + b) * N*C*F*F) * 4.
+ * Returns the float4s per env, or a negative error. */
+int mapf_obs_band_skip(const mapf_config *cfg, int32_t unit, uint64_t byte_offset, uint8_t *skip, int32_t n);
 
 /* Launch tuning of one handle: which form of a kernel the launches take (the measured choices
  * of DESIGN.md §4 / §9).  The reference has no counterpart (its env is Python); these fields
@@ -249,7 +275,9 @@ int mapf_get_tuning(const mapf_env *env, mapf_tuning *t);
 int mapf_set_tuning(mapf_env *env, const mapf_tuning *t);
 /* The kernel mapf_rollout_random would launch now for `slots`, as text into buf (n bytes, NUL-terminated),
  * e.g. "rollout_wide3_kernel<u64,1,false> wpe=3 epw=4 grid=1 overlap=1 slack=-1 fair=0".  Returns
- * mapf_rollout_random_fused's kind (0: per-step launches, text "step_observe") or a negative error. */
+ * mapf_rollout_random_fused's kind (0: per-step launches, text "step_observe") or a negative error.
+ * `slots` takes mapf_rollout_random's bits: where MAPF_SLOTS_BAND_CLEAN takes effect the pair-lane
+ * kernel's name reads e.g. "rollout_random_kernel<true,4,band64>"; the text for 0 and 1 is as before. */
 int mapf_rollout_plan(const mapf_env *env, int32_t slots, char *buf, int32_t n);
 
 /* Launch the search work a committed step left pending (agent.bfsMap updates, the

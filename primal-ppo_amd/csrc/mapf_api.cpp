@@ -19,6 +19,7 @@
 
 #include "mapf.h"
 #include "mapf_kernels.h"
+#include "mapf_observe.h"   // obs_band_skip, evaluated on the host by mapf_obs_band_skip
 
 using namespace mapf;
 
@@ -289,10 +290,27 @@ int mapf_rollout_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
     if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
     if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
     const int kind = mapf_rollout_random_fused(e);
-    if (kind == 1) describe_rollout_random(e->d, slots ? 1 : 0, e->tune, buf, (size_t)n);
-    else if (kind == 2) describe_rollout_wide(e->d, slots ? 1 : 0, e->tune, buf, (size_t)n);
+    if (kind == 1) describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n);
+    else if (kind == 2) describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n);
     else std::snprintf(buf, (size_t)n, "step_observe");
     return kind;
+}
+
+int mapf_obs_band_skip(const mapf_config *cfg, int32_t unit, uint64_t byte_offset, uint8_t *skip, int32_t n) {
+    if (!cfg || !skip || n < 0) return fail(MAPF_EINVAL, "null argument");
+    if (unit != 0 && unit != 16 && unit != 64 && unit != 128) return fail(MAPF_EINVAL, "unit must be 0, 16, 64 or 128");
+    if (byte_offset & 15) return fail(MAPF_EINVAL, "byte_offset must be a multiple of 16");
+    if (cfg->num_agents < 1 || cfg->num_agents > 64 || cfg->fov < 1 || cfg->fov > 16 ||
+        cfg->num_channel < 5 || cfg->num_channel > 7)
+        return fail(MAPF_EINVAL, "num_agents, fov or num_channel out of range");
+    DevEnv d{};
+    d.N = cfg->num_agents; d.F = cfg->fov; d.C = cfg->num_channel; d.use_hp = cfg->use_hp;
+    const int env_floats = d.N * d.C * d.F * d.F;
+    if (env_floats & 3) return fail(MAPF_EINVAL, "an env's observation is not a whole number of float4s");
+    if (unit == 0) unit = MAPF_BAND_UNIT;
+    const int nq = env_floats >> 2;
+    for (int q = 0; q < nq && q < n; ++q) skip[q] = obs_band_skip(d, unit, (size_t)byte_offset, q) ? 1 : 0;
+    return nq;
 }
 
 // s waits for the deferred aux-stream searches: every one (all), or those due before the
@@ -627,6 +645,7 @@ int mapf_rollout_random(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_
                         float *obs, float *vec, void *stream) {
     if (!e || !actions_out || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
     if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
+    if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN)) return fail(MAPF_EINVAL, "slots: unknown bits");
     if (!e->ready) return fail(MAPF_ESTATE, "mapf_rollout_random before mapf_reset");
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
@@ -639,9 +658,9 @@ int mapf_rollout_random(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_
     if (T == 0) return MAPF_OK;
     if (rollout_random_fused(e)) {
         if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
-        int rc = launch_rollout_random(e->d, T, actions_out, o, obs, vec, slots ? 1 : 0, e->tune, e->args, s);
-        if (rc == ROLLOUT_NOT_COVERED)
-            rc = launch_rollout_wide(e->d, T, actions_out, o, obs, vec, slots ? 1 : 0, e->tune, e->args, s);
+        int rc = launch_rollout_random(e->d, T, actions_out, o, obs, vec, slots, e->tune, e->args, s);
+        if (rc == ROLLOUT_NOT_COVERED)      // the wide kernels store everything (MAPF_SLOTS_BAND_CLEAN ignored)
+            rc = launch_rollout_wide(e->d, T, actions_out, o, obs, vec, slots & 1, e->tune, e->args, s);
         if (rc != MAPF_OK)
             return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
                                      "(16 per handle, ArgRing; mapf_release_captures frees them)");
@@ -651,7 +670,7 @@ int mapf_rollout_random(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_
     // not covered by the one-launch kernel: T step_observe launches, same results
     const size_t BN = (size_t)e->d.B * e->d.N, obs_t = BN * e->d.C * e->d.F * e->d.F;
     for (int32_t t = 0; t < T; ++t) {
-        const size_t k = slots ? (size_t)t : 0;
+        const size_t k = (slots & 1) ? (size_t)t : 0;
         mapf_step_out ot{};
         if (out) {
             auto adv = [&](auto *p, size_t n) { return p ? p + k * n : p; };

@@ -168,7 +168,9 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e) {
 // stay cache-resident between steps, measured faster).
 // SUBS 4-env quarters per workgroup: SUBS = 4 puts all 16 waves of a CU in one workgroup, so
 // each can see how far the others are (pacing, below)
-template <bool NT, int SUBS>
+// BAND: a slot-buffer launch with MAPF_SLOTS_BAND_CLEAN -- the wave leaves out the stores that lie
+// wholly inside its env's zero band (obs_band_skip; the band of every slot already holds zeros)
+template <bool NT, int SUBS, bool BAND = false>
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_kernel(
 #if MAPF_ARGS_PTR      // experiment build: arguments through a device pointer (mapf_rollout_wide.hip)
     const RolloutArgs *__restrict__ args, int T) {
@@ -212,6 +214,18 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
     // register's load "pending" at the loop header and waits vmcnt(0) -- i.e. behind
     // all of the previous step's stores -- where the loop uses it
     __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0), expcnt/lgkmcnt untouched
+    // the lane's skip set, one bit per store of its env's slice, from the slice's address.  It is
+    // the same at every step where the unit divides the slot stride (every slot of the env keeps
+    // slot 0's alignment: c2); where it does not (B * env bytes not a multiple of the unit, e.g.
+    // B = 37) the set moves with t and the loop computes it again for each slot.
+    uint32_t band_mask = 0;
+    bool band_moves = false;
+    if constexpr (BAND) {
+        band_moves = ((size_t)e.B * e.N * e.C * e.F * e.F * 4) % MAPF_BAND_UNIT != 0;
+        if (le < nenv && !band_moves)
+            band_mask = obs_band_skip_mask(e, MAPF_BAND_UNIT, (size_t)(ro.obs + (size_t)(b0 + le) * e.N * e.C * e.F * e.F),
+                                           (int)(threadIdx.x & 63));
+    }
     RSTAMP_BEGIN();
     const bool pacing = SUBS > 1 && ro.slack >= 0 && le < nenv;
     const bool fair = SUBS > 1 && ro.fair > 0 && le < nenv;
@@ -240,7 +254,11 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
                                             L, b0, RegMap{mreg, true}, dfr, &rs);
         if (le < nenv) {
             const ObsGroup g = obs_wave_init(E, L, le, mreg);
-            obs_emit<false, NT>(E, L, R.obs + s * BN * E.C * E.F * E.F, R.vec + s * BN * 4, g, b0, false);
+            if (BAND && band_moves)
+                band_mask = obs_band_skip_mask(E, MAPF_BAND_UNIT,
+                                               (size_t)(R.obs + (s * BN + (size_t)(b0 + le) * E.N) * E.C * E.F * E.F),
+                                               (int)(threadIdx.x & 63));
+            obs_emit<false, NT, BAND>(E, L, R.obs + s * BN * E.C * E.F * E.F, R.vec + s * BN * 4, g, b0, false, band_mask);
             step_pairs_search_inline(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs);
             if (pacing || fair) publish_count(prog + gw, (uint32_t)(t + 1));
         }
@@ -297,19 +315,32 @@ static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &t
     return true;
 }
 
+// MAPF_SLOTS_BAND_CLEAN takes effect: slot buffers, a config-static zero band, one mask bit per store
+static bool rollout_band_form(const DevEnv &e, int slots) {
+    int z0, z1;
+    return (slots & MAPF_SLOTS_BAND_CLEAN) && (slots & 1) && obs_zero_band(e, z0, z1) && obs_band_iters(e) <= 32;
+}
+
 void describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n) {
+    const bool band = rollout_band_form(e, slots);
+    slots &= 1;
     RolloutPlan p;
     if (!plan_rollout_random(e, slots, tu, p)) {
         std::snprintf(buf, n, "none");
         return;
     }
-    std::snprintf(buf, n, "rollout_random_kernel<%s,%d> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
-                  slots ? "true" : "false", p.subs, p.grid, 256 * p.subs, p.lds, p.subs > 1 ? p.fair : 0,
+    char form[24] = "";
+    if (band) std::snprintf(form, sizeof form, ",band%d", MAPF_BAND_UNIT);
+    std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
+                  slots ? "true" : "false", p.subs, form, p.grid, 256 * p.subs, p.lds, p.subs > 1 ? p.fair : 0,
                   p.subs > 1 ? p.slack : -1, p.remap);
 }
 
+// slots: the MAPF_SLOTS_* bits of mapf_rollout_random
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
                           int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s) {
+    const bool band = rollout_band_form(e, slots) && ((uintptr_t)obs & 15) == 0;     // whole float4s
+    slots &= 1;
     RolloutPlan p;
     if (!plan_rollout_random(e, slots, tu, p)) return ROLLOUT_NOT_COVERED;
     const RolloutOut ro{actions, out, obs, vec, slots, p.remap, p.sub_lds, p.slack, p.fair};
@@ -325,6 +356,7 @@ int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOu
         return MAPF_OK;
     };
     (void)ring;
+    if (band) return p.subs == 4 ? launch(rollout_random_kernel<true, 4, true>) : launch(rollout_random_kernel<true, 1, true>);
     if (p.subs == 4) return slots ? launch(rollout_random_kernel<true, 4>) : launch(rollout_random_kernel<false, 4>);
     return slots ? launch(rollout_random_kernel<true, 1>) : launch(rollout_random_kernel<false, 1>);
 }

@@ -87,7 +87,8 @@ void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, 
 // ROLLOUT_NOT_COVERED (nothing launched) if the configuration is not covered; MAPF_ESTATE
 // (nothing launched) if a captured launch found no free argument slot (ArgRing)
 // (the kernel's form from the handle's tuning, mapf.h: mapf_tuning); describe_* write the
-// form launch_* would take as text (mapf_rollout_plan)
+// form launch_* would take as text (mapf_rollout_plan).  launch_/describe_rollout_random take
+// mapf_rollout_random's `slots` bits (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN), the wide ones 0 / 1.
 constexpr int ROLLOUT_NOT_COVERED = 1;
 bool rollout_random_fusable(const DevEnv &e);
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,

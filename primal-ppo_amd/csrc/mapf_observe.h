@@ -174,6 +174,40 @@ __host__ __device__ inline bool obs_zero_band(const DevEnv &e, int &z0, int &z1)
     return true;
 }
 
+// The skip set of a slot-buffer rollout launched with MAPF_SLOTS_BAND_CLEAN (mapf.h): the caller
+// guarantees that the zero band of every slot already holds zeros, so the band's whole `unit`-byte
+// pieces (16, 64 or 128, at unit-aligned absolute addresses) need no store.  Float4 q of an env's
+// observation, whose slice starts at byte address `off` (16-B aligned; only off % unit matters),
+// is skipped iff the aligned unit around it lies wholly inside one agent's band -- never a byte
+// outside the band.  The one function both the kernel and the host (mapf_obs_band_skip) evaluate.
+__host__ __device__ inline bool obs_band_skip(const DevEnv &e, int unit, size_t off, int q) {
+    int z0, z1;
+    if (!obs_zero_band(e, z0, z1)) return false;
+    const uint32_t ab = (uint32_t)(e.C * e.F * e.F) * 4u;              // bytes per agent
+    const uint32_t o = (uint32_t)(off & (size_t)(unit - 1));
+    const uint32_t u0 = (o + 16u * (uint32_t)q) & ~(uint32_t)(unit - 1);   // the unit, from the aligned base below off
+    if (u0 < o) return false;                                          // it begins before the env's slice
+    const uint32_t r0 = u0 - o, r1 = r0 + (uint32_t)unit;               // the unit within the env's slice
+    const uint32_t k = r0 / ab;
+    return r0 >= k * ab + 4u * (uint32_t)z0 && r1 <= k * ab + 4u * (uint32_t)z1;
+}
+// The wave store loop's iterations per env (lane l stores float4 l + 64k, k < obs_band_iters), and
+// a lane's skip set as one bit per iteration (obs_emit<.., BAND>); a mask holds at most 32
+__host__ __device__ inline int obs_band_iters(const DevEnv &e) { return ((e.N * e.C * e.F * e.F) / 4 + 63) / 64; }
+__host__ __device__ inline uint32_t obs_band_skip_mask(const DevEnv &e, int unit, size_t off, int lane) {
+    const int nq = (e.N * e.C * e.F * e.F) >> 2;
+    uint32_t m = 0;
+    for (int k = 0, q = lane; q < nq && k < 32; ++k, q += 64)
+        if (obs_band_skip(e, unit, off, q)) m |= 1u << k;
+    return m;
+}
+// The unit a flagged launch skips in: the measured choice (holes of whole
+// 64-B pieces cost the store stream nothing, 16-B holes leave partial pieces and run slower than
+// no holes at all).  An experiment build may pass another one of 16, 64, 128.
+#ifndef MAPF_BAND_UNIT
+#define MAPF_BAND_UNIT 64
+#endif
+
 // The band's whole float4s of agents [k0, k1) of `obs` (16-B aligned), written
 // as zeros by `nt` threads numbered `t`: float4 q of the buffer belongs to the
 // band iff 4q >= k*CFF + z0 and 4q + 4 <= k*CFF + z1 for its agent k.  The fused
@@ -198,7 +232,8 @@ __device__ inline void obs_zero_band_store(const DevEnv &e, float *__restrict__ 
 // whole float4s were written by obs_zero_band_store in this launch.
 // BFSCH = false compiles the BFS channel (C = 7) out (the fused launch never
 // has it: step_observe_fusable).  NT: the table-driven store loop (L.lut) uses
-// nontemporal stores.
+// nontemporal stores.  BAND: the one-wave table loop skips the stores of `band_mask`
+// (bit k = this lane's iteration k, obs_band_skip_mask); BAND = false compiles the test out.
 // The threads that observe a run of the workgroup's envs together: the whole
 // workgroup (workgroup barriers) or one wave observing its own env (per_env
 // layout; wave-level ordering only).
@@ -240,9 +275,9 @@ __device__ inline ObsGroup obs_wave_init(const DevEnv &e, const ObsLds &L, int l
     return g;
 }
 
-template <bool BFSCH = true, bool NT = false>
+template <bool BFSCH = true, bool NT = false, bool BAND = false>
 __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restrict__ obs, float *__restrict__ vec,
-                                const ObsGroup &G, int b0, bool skip_band = false) {
+                                const ObsGroup &G, int b0, bool skip_band = false, uint32_t band_mask = 0) {
     using namespace obsd;
     const int N = e.N, F = e.F, C = e.C, FF = F * F, CFF = C * FF;
     const int K = G.nenv * N;                 // agents of the group; k below is group-relative
@@ -411,7 +446,9 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
 #pragma unroll 4
         for (int rem = ((K * CFF) >> 2) - tid; rem > 0; rem -= 64) {
             const float4 f = L.lut[__builtin_amdgcn_ubfe(*swp, sh, 4)];
-            if constexpr (NT) {   // streaming stores (rollout slot buffers: not re-read by this launch)
+            if (BAND && (band_mask & 1u)) {
+                // inside the clean zero band: nothing to store
+            } else if constexpr (NT) {   // streaming stores (rollout slot buffers: not re-read by this launch)
                 typedef float v4f __attribute__((ext_vector_type(4)));
 #if defined(MAPF_SLOT_STORE) && MAPF_SLOT_STORE == 1     // store-policy experiment: nt only (round 2's)
                 __builtin_nontemporal_store(v4f{f.x, f.y, f.z, f.w}, reinterpret_cast<v4f *>(dp));
@@ -440,6 +477,7 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
                 *dp = f;
 #endif
             }
+            if constexpr (BAND) band_mask >>= 1;
             swp += 8;
             dp += 64;
         }

@@ -34,6 +34,7 @@ class MapGenSpec(ctypes.Structure):
 
 
 MAPS_WAREHOUSE, MAPS_RANDOM = 0, 1
+SLOTS, SLOTS_BAND_CLEAN = 1, 2          # mapf_rollout_random's `slots` bits
 
 
 class StepOut(ctypes.Structure):
@@ -73,6 +74,7 @@ SIGNATURES = {
     "mapf_step_observe_random": (ctypes.c_int, [P, P, ctypes.POINTER(StepOut), P, P, P]),
     "mapf_rollout_random": (ctypes.c_int, [P, I32, I32, P, ctypes.POINTER(StepOut), P, P, P]),
     "mapf_rollout_random_fused": (ctypes.c_int, [P]),
+    "mapf_obs_band_skip": (ctypes.c_int, [ctypes.POINTER(MapfConfig), I32, ctypes.c_uint64, P, I32]),
     "mapf_tuning_default": (None, [ctypes.POINTER(Tuning)]),
     "mapf_get_tuning": (ctypes.c_int, [P, ctypes.POINTER(Tuning)]),
     "mapf_set_tuning": (ctypes.c_int, [P, ctypes.POINTER(Tuning)]),

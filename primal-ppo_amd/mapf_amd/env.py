@@ -123,10 +123,12 @@ class BatchedMapfGym:
         _lib.check(_lib.lib().mapf_set_tuning(self.h, ctypes.byref(t)))
         self._query_forms()
 
-    def rollout_plan(self, slots=False):
-        """The kernel (template instantiation + form) mapf_rollout_random launches now, as text."""
+    def rollout_plan(self, slots=False, band_clean=False):
+        """The kernel (template instantiation + form) mapf_rollout_random launches now, as text
+        (band_clean: for a slots launch with MAPF_SLOTS_BAND_CLEAN)."""
         buf = ctypes.create_string_buffer(512)
-        kind = _lib.lib().mapf_rollout_plan(self.h, 1 if slots else 0, buf, 512)
+        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
+        kind = _lib.lib().mapf_rollout_plan(self.h, bits, buf, 512)
         if kind < 0:
             _lib.check(kind)
         return buf.value.decode()
@@ -292,12 +294,15 @@ class BatchedMapfGym:
         _lib.check(fn(self.h, _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return (self.out if out is None else out), obs, vec
 
-    def rollout_random(self, T, slots=False, actions=None, obs=None, vec=None, out=None):
+    def rollout_random(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False):
         """T x step_observe(random_policy=True) -- runner.py:64-100 with the uniform random
         policy, T times -- as ONE launch where mapf_rollout_random_fused (each wave owns an
         env and loops step -> observe -> its search work).  slots: step t writes slot t of
         [T]-leading buffers (actions [T, B, N], obs [T, B, N, C, F, F], vec [T, B, N, 4],
         out[k] [T, ...]); otherwise every step overwrites the [B]-leading buffers.
+        band_clean (with slots): the caller's promise that the zero band of every slot of `obs`
+        (channel 5 while use_hp is off) already holds zeros, e.g. from an earlier call on the same
+        buffer without it; the launch then need not store it (MAPF_SLOTS_BAND_CLEAN, mapf.h).
         Returns (out, obs, vec)."""
         if not slots and actions is None and obs is None and vec is None and out is None:
             # the default [B]-leading buffers (checked at construction): the call's arguments are
@@ -327,7 +332,8 @@ class BatchedMapfGym:
                 ref = self.out[key]
                 _check(t, ref.dtype, k * ref.numel(), self.device, key)
             so = self._make_stepout(out)
-        _lib.check(_lib.lib().mapf_rollout_random(self.h, int(T), 1 if slots else 0, _ptr(actions), ctypes.byref(so),
+        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
+        _lib.check(_lib.lib().mapf_rollout_random(self.h, int(T), bits, _ptr(actions), ctypes.byref(so),
                                                   _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
 
@@ -335,7 +341,14 @@ class BatchedMapfGym:
         """rollout_random(T, slots, ...) prepared once: the buffers are checked and the C call's
         arguments built now, on the current stream; the returned callable issues the launch with
         no per-call host work beyond one ctypes call (a 20-step rollout is ~350 us on the GPU, the
-        checks and wrapping ~60 us of host time).  The buffers must outlive the launcher."""
+        checks and wrapping ~60 us of host time).  The launcher keeps its buffers alive.
+
+        With slots, the launcher's first call stores every float (right for torch.empty buffers
+        too); its later calls tell the library that the observation buffer's zero band (channel 5
+        while use_hp is off) is already clean, and the kernel leaves those stores out
+        (MAPF_SLOTS_BAND_CLEAN, mapf.h).  The contract: between calls of one launcher nobody writes
+        non-zeros into that band of `obs`.  Whoever does (or hands the memory to something that
+        may) calls launch.invalidate(): the next call stores everything again."""
         k = T if slots else 1
         actions = self.actions if actions is None else actions
         obs = self.obs if obs is None else obs
@@ -350,14 +363,21 @@ class BatchedMapfGym:
         for key, t in out.items():
             _check(t, self.out[key].dtype, k * self.out[key].numel(), self.device, key)
         so = self._make_stepout(out)
-        args = (self.h, int(T), 1 if slots else 0, _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec),
+        args = (self.h, int(T), _lib.SLOTS if slots else 0, _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec),
                 _stream(self.device))
+        clean = args[:2] + (_lib.SLOTS | _lib.SLOTS_BAND_CLEAN,) + args[3:] if slots else args
         fn = _lib.lib().mapf_rollout_random
         keep = (so, actions, obs, vec, out)
+        state = [args]                  # the next call's arguments: `clean` once a call has stored the band
 
         def launch():
-            _lib.check(fn(*args))
+            _lib.check(fn(*state[0]))
+            state[0] = clean
             return keep[4], keep[2], keep[3]
+
+        def invalidate():
+            state[0] = args
+        launch.invalidate = invalidate
         return launch
 
     def _check_out(self, out):

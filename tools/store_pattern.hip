@@ -8,8 +8,18 @@
 //     hipcc -O3 --offload-arch=gfx950 tools/store_pattern.hip -o tools/store_pattern
 //     ./tools/store_pattern [waves kib_per_wave steps in_place waves_per_workgroup]
 // (default: the c2 slot pattern, 4096 23 64 0 4; c4's observer pattern in place: 1024 32 256 1 1)
+//
+//     ./tools/store_pattern slice [steps reps]
+// writes the real c2 slice instead -- 23,232 B per wave (8 agents x 6 x 11 x 11 floats), env b at
+// b * 23232, so odd envs start mid-line -- with the rollout kernel's lane mapping (lane l stores
+// float4 l + 64k, k < 23), fresh slices, 4096 waves, 16 per workgroup, and leaves out the whole
+// 16 / 64 / 128-B units of every agent's zero band (channel 5: bytes [2420, 2904) of each 2904-B
+// agent block) with the skipped lanes predicated off; "compact 16": the 1,216 float4s that remain
+// at the 16-B unit as 19 full instructions.  Each form with plain and with `sc1 nt` stores; the
+// full pattern is measured in the same run (min / median / max of the repeats).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <vector>
 
@@ -34,8 +44,122 @@ __global__ __launch_bounds__(1024) void stores(float *buf, int steps, int kib_pe
     }
 }
 
+// ---- the c2 slice with holes ----
+constexpr int AGENTS = 8, AGENT_BYTES = 6 * 11 * 11 * 4, BAND0 = 5 * 11 * 11 * 4;   // band = [BAND0, AGENT_BYTES)
+constexpr int ENV_BYTES = AGENTS * AGENT_BYTES, ENV_Q = ENV_BYTES / 16, ITERS = (ENV_Q + 63) / 64;   // 23232, 1452, 23
+constexpr int COMPACT_ITERS = 19;
+
+template <bool NT>
+__device__ inline void store4(v4f *p, v4f v) {
+    if (NT) asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
+    else *p = v;
+}
+
+// masks: [2][64] per-lane skip bits (bit k = float4 lane + 64k) by env parity, or null (full);
+// cidx: [COMPACT_ITERS][64] float4 indices of the compacted form, or null
+template <bool NT>
+__global__ __launch_bounds__(1024) void slice_stores(float *buf, int steps, size_t step_floats, const uint32_t *masks,
+                                                     const int *cidx) {
+    const int lane = threadIdx.x & 63;
+    const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t mask = masks ? masks[(w & 1) * 64 + lane] : 0u;      // env offset % 128 = 64 * (w & 1)
+    int idx[COMPACT_ITERS];
+#pragma unroll
+    for (int k = 0; k < COMPACT_ITERS; ++k) idx[k] = cidx ? cidx[k * 64 + lane] : 0;
+    for (int s = 0; s < steps; ++s) {
+        v4f *base = reinterpret_cast<v4f *>(buf + (size_t)s * step_floats + (size_t)w * (ENV_BYTES / 4));
+        const v4f v = {(float)s, 1.f, 0.f, 1.f};
+        if (cidx) {
+#pragma unroll
+            for (int k = 0; k < COMPACT_ITERS; ++k) store4<NT>(base + idx[k], v);
+        } else {
+            uint32_t m = mask;
+#pragma unroll
+            for (int k = 0; k < ITERS; ++k) {
+                const int q = lane + 64 * k;
+                if (q < ENV_Q && !(m & 1u)) store4<NT>(base + q, v);
+                m >>= 1;
+            }
+        }
+    }
+}
+
+// float4 q of an env slice at byte offset `off` (mod 128) is skipped iff the aligned unit around
+// it lies wholly inside one agent's band
+static bool skip_q(int unit, int off, int q) {
+    const int o = off & (unit - 1), u0 = (o + 16 * q) & ~(unit - 1);
+    if (u0 < o) return false;
+    const int r0 = u0 - o, r1 = r0 + unit, k = r0 / AGENT_BYTES;
+    return r0 >= k * AGENT_BYTES + BAND0 && r1 <= (k + 1) * AGENT_BYTES;
+}
+
+static int slice_mode(int steps, int reps) {
+    const int waves = 4096, wpg = 16;
+    const size_t step_floats = (size_t)waves * ENV_BYTES / 4;
+    printf("c2 slice: %d waves x %d B, %d steps, fresh slices, %d waves per workgroup, %d repeats\n", waves, ENV_BYTES,
+           steps, wpg, reps);
+    float *buf = nullptr;
+    if (hipMalloc(&buf, step_floats * 4 * steps) != hipSuccess) return 1;
+    uint32_t *dmask = nullptr;
+    int *dcidx = nullptr;
+    if (hipMalloc(&dmask, 3 * 2 * 64 * 4) != hipSuccess || hipMalloc(&dcidx, COMPACT_ITERS * 64 * 4) != hipSuccess) return 1;
+    const int units[3] = {16, 64, 128};
+    double skipped[3] = {0, 0, 0};
+    std::vector<uint32_t> hm(3 * 2 * 64, 0u);
+    for (int u = 0; u < 3; ++u)
+        for (int par = 0; par < 2; ++par)
+            for (int q = 0; q < ENV_Q; ++q)
+                if (skip_q(units[u], 64 * par, q)) {
+                    hm[(u * 2 + par) * 64 + (q & 63)] |= 1u << (q >> 6);
+                    skipped[u] += 16.0 / 2;
+                }
+    std::vector<int> hc;
+    for (int q = 0; q < ENV_Q; ++q)
+        if (!skip_q(16, 0, q)) hc.push_back(q);
+    if ((int)hc.size() != COMPACT_ITERS * 64) return 1;
+    hipMemcpy(dmask, hm.data(), hm.size() * 4, hipMemcpyHostToDevice);
+    hipMemcpy(dcidx, hc.data(), hc.size() * 4, hipMemcpyHostToDevice);
+    hipEvent_t a, b;
+    hipEventCreate(&a);
+    hipEventCreate(&b);
+    auto run = [&](const char *name, bool nt, const uint32_t *masks, const int *cidx, double bytes_env) {
+        std::vector<float> us;
+        for (int r = 0; r <= reps; ++r) {
+            hipEventRecord(a);
+            if (nt) hipLaunchKernelGGL(slice_stores<true>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx);
+            else hipLaunchKernelGGL(slice_stores<false>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx);
+            hipEventRecord(b);
+            hipEventSynchronize(b);
+            float ms;
+            hipEventElapsedTime(&ms, a, b);
+            if (r > 0) us.push_back(ms * 1e3f / steps);       // the first launch is warm-up
+        }
+        std::sort(us.begin(), us.end());
+        const double med = us[us.size() / 2];
+        printf("%-22s %-6s %7.0f B/env  %6.2f / %6.2f / %6.2f us/step (min / median / max)  %6.0f GB/s\n", name,
+               nt ? "sc1 nt" : "plain", bytes_env, us.front(), med, us.back(), bytes_env * waves / (med * 1e-6) / 1e9);
+    };
+    for (int nt = 0; nt < 2; ++nt) {
+        run("full", nt, nullptr, nullptr, ENV_BYTES);
+        for (int u = 0; u < 3; ++u) {
+            char name[32];
+            snprintf(name, sizeof name, "skip %d-B units", units[u]);
+            run(name, nt, dmask + u * 2 * 64, nullptr, ENV_BYTES - skipped[u]);
+        }
+        run("compact 16 (19 instr)", nt, nullptr, dcidx, ENV_BYTES - skipped[0]);
+        run("full (again)", nt, nullptr, nullptr, ENV_BYTES);
+    }
+    hipFree(buf);
+    hipFree(dmask);
+    hipFree(dcidx);
+    return 0;
+}
+
 #include <cstdlib>
+#include <cstring>
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "slice"))
+        return slice_mode(argc > 2 ? atoi(argv[2]) : 64, argc > 3 ? atoi(argv[3]) : 7);
     // c2: 4096 envs x ~23 KiB each per step, fresh slices
     const int waves = argc > 1 ? atoi(argv[1]) : 4096, kib = argc > 2 ? atoi(argv[2]) : 23;
     const int steps = argc > 3 ? atoi(argv[3]) : 64, inplace = argc > 4 ? atoi(argv[4]) : 0;
