@@ -19,6 +19,7 @@
  *   Runner.run GAE                  runner.py:117-149               -> mapf_gae
  *   Model.train normalisation       model.py:106-113                -> mapf_normalize_advantages
  *   Model.step sampling             model.py:38-40                  -> mapf_sample_actions
+ *   minibatch shuffle + indexing    driver.py:123-134               -> mapf_minibatch_rows, mapf_gather_rows
  *
  * Conventions
  *  - One handle = B lockstep environments resident on one GPU (Structure of
@@ -380,6 +381,64 @@ int mapf_episode_sum(const float *x, int32_t T, int32_t B, int32_t N, float *out
  * with a Philox uniform (key seed, counter (row, step)).  DEVICE. */
 int mapf_sample_actions(const float *ps, int32_t ps_stride, int32_t *actions, int64_t *actions64, int32_t M,
                         uint64_t seed, uint32_t step, void *stream);
+
+/* ---- PPO epochs over a whole device rollout: minibatch rows and their gather (csrc/mapf_minibatch.hip) ----
+ *
+ * mapf_minibatch_rows: rows_out[j] = P(start + j) for j < count, DEVICE int64 [count], where P is a
+ * bijection of [0, n) fixed by (seed, epoch, n).  Stateless: every output is computed on its own
+ * (no sort, no scratch of size n, no host data), so a minibatch is any window [start, start + count)
+ * of the epoch's permutation.  Specification (csrc/mapf_common.h: shuffle_index, the one
+ * __host__ __device__ function both entry points run):
+ *   h    = the smallest integer >= 1 with 2^(2h) >= n (h <= 32); mask = 2^h - 1
+ *   k[0..7] = the two Philox4x32-10 draws with key `seed` and counter
+ *             (low 32 bits of n, P_SHUFFLE | d << 8, epoch, high 32 bits of n), d = 0, 1 (P_SHUFFLE = 11),
+ *             taken x, y, z, w of draw 0 then of draw 1; rounds use k[0..5]
+ *   x -> E(x), a 6-round balanced Feistel network over 2h bits: (L, R) = (x >> h, x & mask), then per
+ *             round i: (L, R) <- (R, L ^ (F(R + k[i]) & mask)) in uint32 arithmetic, with
+ *             F(v): v ^= v >> 16; v *= 0x7FEB352D; v ^= v >> 15; v *= 0x846CA68B; v ^= v >> 16;
+ *             E(x) = L << h | R
+ *   P(i) = the first of E(i), E(E(i)), ... that is < n (cycle walking: fewer than 4 steps expected).
+ * MAPF_EINVAL for n < 1, start < 0, count < 0, start + count > n or a null rows_out with count > 0;
+ * count == 0 launches nothing.  Asynchronous on `stream`; capturable. */
+int mapf_minibatch_rows(uint64_t seed, uint32_t epoch, int64_t n, int64_t start, int64_t count, int64_t *rows_out,
+                        void *stream);
+/* The same rows into a HOST array, computed by the same function on the host: no device call, so it
+ * works on a machine without a GPU. */
+int mapf_minibatch_rows_host(uint64_t seed, uint32_t epoch, int64_t n, int64_t start, int64_t count,
+                             int64_t *rows_out);
+
+/* One gathered array of mapf_gather_rows: row j of dst = row rows[j] (env-major) of src. */
+typedef struct mapf_gather_array {
+    const void *src;         /* DEVICE, t-major [T][B][row_bytes]                           */
+    void *dst;               /* DEVICE, [M][row_bytes]                                      */
+    int64_t row_bytes;       /* a positive multiple of 4                                    */
+} mapf_gather_array;
+
+#define MAPF_GATHER_MAX 16
+
+typedef struct mapf_gather_spec {
+    int32_t T, B;            /* the rollout: T steps of B envs                              */
+    int64_t M;               /* rows gathered                                               */
+    const int64_t *rows;     /* DEVICE [M]: env-major row ids in [0, B*T)                   */
+    int32_t count;           /* arrays, 1..MAPF_GATHER_MAX                                  */
+    int32_t reserved;
+    mapf_gather_array arrays[MAPF_GATHER_MAX];
+} mapf_gather_spec;
+
+/* Gathers `count` arrays in ONE launch: for every array a and every j < M, the row_bytes bytes of
+ * a.dst at j * row_bytes are the bytes of a.src at ((rows[j] % T) * B + rows[j] / T) * row_bytes --
+ * env-major row r is env r / T, step r % T of the t-major rollout buffers (the rows of
+ * runner.EnvMajorRows).  No other byte is written; duplicate row ids are legal.
+ * Row ids are NOT range-checked on the device: a row outside [0, B*T) reads outside src (the Python
+ * wrapper checks explicit host indices; mapf_minibatch_rows produces rows in range by construction).
+ * An array whose src, dst and row_bytes are all multiples of 16 moves in 16-byte loads and stores; any
+ * other array in 4-byte ones (src and dst 4-byte aligned), decided per array on the host.  Grid: per
+ * gathered row, one workgroup of 256 lanes per 4 KiB piece of each array with rows longer than 1 KiB;
+ * the shorter arrays ride with the row's first workgroup.
+ * MAPF_EINVAL, before any launch, on a null spec / rows / src / dst, count outside 1..16, a row_bytes
+ * that is not a positive multiple of 4, a src or dst not 4-byte aligned, T, B or M < 1, or more than
+ * 2^31 - 1 workgroups.  No host synchronisation and no allocation: capturable. */
+int mapf_gather_rows(const mapf_gather_spec *spec, void *stream);
 
 /* ---- Policy acting forward: fused elementwise epilogues (csrc/mapf_policy.hip) ----
  * SCRIMPNet.forward (net.py:101-155) under autocast with no grad (Model.step /

@@ -1018,4 +1018,70 @@ int mapf_sample_actions(const float *ps, int32_t ps_stride, int32_t *actions, in
     return MAPF_OK;
 }
 
+static int minibatch_window_ok(int64_t n, int64_t start, int64_t count, const int64_t *rows_out) {
+    if (n < 1) return fail(MAPF_EINVAL, "n must be >= 1");
+    if (start < 0 || count < 0) return fail(MAPF_EINVAL, "start and count must be >= 0");
+    if (start > n || count > n - start) return fail(MAPF_EINVAL, "start + count must be <= n");
+    if (!rows_out && count > 0) return fail(MAPF_EINVAL, "null argument");
+    return MAPF_OK;
+}
+
+int mapf_minibatch_rows(uint64_t seed, uint32_t epoch, int64_t n, int64_t start, int64_t count, int64_t *rows_out,
+                        void *stream) {
+    if (int rc = minibatch_window_ok(n, start, count, rows_out)) return rc;
+    if (count == 0) return MAPF_OK;
+    launch_minibatch_rows(shuffle_key(seed, epoch, (uint64_t)n), start, count, rows_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+int mapf_minibatch_rows_host(uint64_t seed, uint32_t epoch, int64_t n, int64_t start, int64_t count,
+                             int64_t *rows_out) {
+    if (int rc = minibatch_window_ok(n, start, count, rows_out)) return rc;
+    const ShuffleKey key = shuffle_key(seed, epoch, (uint64_t)n);
+    for (int64_t j = 0; j < count; ++j) rows_out[j] = (int64_t)shuffle_index(key, (uint64_t)(start + j));
+    return MAPF_OK;
+}
+
+int mapf_gather_rows(const mapf_gather_spec *spec, void *stream) {
+    if (!spec || !spec->rows) return fail(MAPF_EINVAL, "null argument");
+    if (spec->count < 1 || spec->count > MAPF_GATHER_MAX) return fail(MAPF_EINVAL, "count must be in 1..16");
+    if (spec->T < 1 || spec->B < 1 || spec->M < 1) return fail(MAPF_EINVAL, "T, B and M must be >= 1");
+    GatherArgs a{};
+    a.rows = spec->rows;
+    a.T = spec->T;
+    a.B = spec->B;
+    a.count = spec->count;
+    int64_t chunks = 0;
+    for (int i = 0; i < spec->count; ++i) {
+        const mapf_gather_array &g = spec->arrays[i];
+        if (!g.src || !g.dst) return fail(MAPF_EINVAL, "null src or dst");
+        if (g.row_bytes < 4 || (g.row_bytes & 3)) return fail(MAPF_EINVAL, "row_bytes must be a positive multiple of 4");
+        if (((uintptr_t)g.src | (uintptr_t)g.dst) & 3) return fail(MAPF_EINVAL, "src and dst must be 4-byte aligned");
+        a.nbig += g.row_bytes > GATHER_SMALL;
+    }
+    int nb = 0, ns = a.nbig;                       // big arrays first, each group in the caller's order
+    for (int i = 0; i < spec->count; ++i) {
+        const mapf_gather_array &g = spec->arrays[i];
+        const bool big = g.row_bytes > GATHER_SMALL;
+        const int k = big ? nb++ : ns++;
+        a.src[k] = static_cast<const char *>(g.src);
+        a.dst[k] = static_cast<char *>(g.dst);
+        a.row_bytes[k] = g.row_bytes;
+        if (!((((uintptr_t)g.src | (uintptr_t)g.dst) & 15) || (g.row_bytes & 15))) a.vec16 |= 1u << k;
+    }
+    for (int k = 0; k < a.nbig; ++k) {
+        a.chunk_begin[k] = (int)chunks;
+        chunks += (a.row_bytes[k] + GATHER_CHUNK - 1) / GATHER_CHUNK;
+        if (chunks > 0x7FFFFFFF) return fail(MAPF_EINVAL, "more than 2^31 - 1 workgroups");
+    }
+    a.chunk_begin[a.nbig] = (int)chunks;
+    a.chunks_per_row = chunks > 0 ? (int)chunks : 1;
+    const int64_t blocks = spec->M * a.chunks_per_row;
+    if (spec->M > 0x7FFFFFFF || blocks > 0x7FFFFFFF) return fail(MAPF_EINVAL, "more than 2^31 - 1 workgroups");
+    launch_gather_rows(a, blocks, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
 }  // extern "C"

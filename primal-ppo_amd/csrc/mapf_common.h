@@ -35,7 +35,7 @@ __host__ __device__ constexpr int opp(int a) { return a == 0 ? 0 : (a == 1 ? 3 :
 
 // Philox purposes (shared spec with oracle/mapf_oracle.c).
 enum : uint32_t { P_ENTRANCE = 1, P_HGOAL0 = 2, P_START = 3, P_GOAL0 = 4, P_GOAL = 5,
-                  P_HGOAL = 6, P_FIX = 7, P_ACT = 8, P_SAMPLE = 9, P_MAPGEN = 10 };
+                  P_HGOAL = 6, P_FIX = 7, P_ACT = 8, P_SAMPLE = 9, P_MAPGEN = 10, P_SHUFFLE = 11 };
 
 // counters[] slots
 enum : int { C_BAD_ACTION = 0, C_FIX_BOUND = 1, C_EMPTY_VIABLE = 2, C_FREECELL = 3,
@@ -101,6 +101,56 @@ __device__ inline u32x4 philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
     return {c0, c1, c2, c3};
+}
+// The same draw, callable on the host too (the device-only philox() above keeps its own codegen).
+__host__ __device__ inline u32x4 philox_hd(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint64_t seed) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int i = 0; i < 10; ++i) {
+        const uint64_t m0 = (uint64_t)0xD2511F53u * c0, m1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(m1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(m0 >> 32) ^ c3 ^ k1;
+        c0 = n0; c1 = (uint32_t)m1; c2 = n2; c3 = (uint32_t)m0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return {c0, c1, c2, c3};
+}
+
+// The epoch's minibatch permutation P of [0, n) (include/mapf.h: mapf_minibatch_rows has the
+// specification): a 6-round balanced Feistel network over 2h bits, 2^(2h) >= n, keyed by two Philox
+// draws of purpose P_SHUFFLE, cycle-walked into [0, n).  The one function the device kernel and
+// mapf_minibatch_rows_host both run.
+struct ShuffleKey {
+    uint32_t k[8];
+    int h;
+    uint64_t n;
+};
+__host__ __device__ inline ShuffleKey shuffle_key(uint64_t seed, uint32_t epoch, uint64_t n) {
+    ShuffleKey s;
+    s.n = n;
+    s.h = 1;
+    while (s.h < 32 && (1ull << (2 * s.h)) < n) ++s.h;
+    for (int d = 0; d < 2; ++d) {
+        const u32x4 o = philox_hd((uint32_t)n, P_SHUFFLE | ((uint32_t)d << 8), epoch, (uint32_t)(n >> 32), seed);
+        s.k[4 * d] = o.x; s.k[4 * d + 1] = o.y; s.k[4 * d + 2] = o.z; s.k[4 * d + 3] = o.w;
+    }
+    return s;
+}
+__host__ __device__ inline uint32_t shuffle_mix(uint32_t v) {
+    v ^= v >> 16; v *= 0x7FEB352Du; v ^= v >> 15; v *= 0x846CA68Bu; v ^= v >> 16;
+    return v;
+}
+__host__ __device__ inline uint64_t shuffle_index(const ShuffleKey &s, uint64_t i) {
+    const uint32_t mask = s.h == 32 ? 0xFFFFFFFFu : (1u << s.h) - 1u;
+    uint64_t x = i;
+    do {    // cycle walking: E permutes [0, 2^(2h)), so the walk from i < n returns below n
+        uint32_t L = (uint32_t)(x >> s.h) & mask, R = (uint32_t)x & mask;
+        for (int r = 0; r < 6; ++r) {
+            const uint32_t t = L ^ (shuffle_mix(R + s.k[r]) & mask);
+            L = R;
+            R = t;
+        }
+        x = ((uint64_t)L << s.h) | R;
+    } while (x >= s.n);
+    return x;
 }
 
 // Uniform random policy (the env-only benchmark's actions): one Philox draw

@@ -181,5 +181,21 @@ void launch_normalize_stats(const float *ret, const float *v, const float *cret,
 void launch_episode_sum(const float *x, int T, int B, int N, float *out, hipStream_t s);
 void launch_sample(const float *ps, int stride, int32_t *a32, int64_t *a64, int M, uint64_t seed, uint32_t step,
                    hipStream_t s);
+// minibatch rows and their gather (mapf_minibatch.hip).  GatherArgs: the arrays of a mapf_gather_spec
+// with the nbig arrays of rows longer than GATHER_SMALL first; chunk_begin[k] = the first
+// GATHER_CHUNK piece of big array k within a gathered row's chunks_per_row workgroups (>= 1: the
+// row's first workgroup also copies the small arrays); bit k of vec16: array k moves in 16-byte accesses.
+constexpr int64_t GATHER_CHUNK = 4096, GATHER_SMALL = 1024;
+struct GatherArgs {
+    const int64_t *rows;
+    int T, B, count, nbig, chunks_per_row;
+    uint32_t vec16;
+    int chunk_begin[MAPF_GATHER_MAX + 1];
+    int64_t row_bytes[MAPF_GATHER_MAX];
+    const char *src[MAPF_GATHER_MAX];
+    char *dst[MAPF_GATHER_MAX];
+};
+void launch_minibatch_rows(const ShuffleKey &key, int64_t start, int64_t count, int64_t *rows, hipStream_t s);
+void launch_gather_rows(const GatherArgs &a, int64_t blocks, hipStream_t s);
 
 }  // namespace mapf

@@ -46,6 +46,20 @@ class State(ctypes.Structure):
     _fields_ = [(n, P) for n in ("pos", "goal", "last_action", "seq_cursor", "human", "human_path", "clock")]
 
 
+GATHER_MAX = 16
+
+
+class GatherArray(ctypes.Structure):
+    """include/mapf.h: mapf_gather_array."""
+    _fields_ = [("src", P), ("dst", P), ("row_bytes", I64)]
+
+
+class GatherSpec(ctypes.Structure):
+    """include/mapf.h: mapf_gather_spec."""
+    _fields_ = [("T", I32), ("B", I32), ("M", I64), ("rows", P), ("count", I32), ("reserved", I32),
+                ("arrays", GatherArray * GATHER_MAX)]
+
+
 TUNING_FIELDS = ("roll_occ", "roll_group", "roll_fair", "roll_slack", "wide_nt", "wide_pipe", "wide_grid",
                  "wide_overlap", "wide_obs", "wide_epw", "wide_pair", "wide_slack", "wide_fair", "wide_prio",
                  "wide_bfsobs", "xcd_remap", "obs_envs", "step_block", "search_blocks", "band_blocks", "agent_lanes",
@@ -93,6 +107,9 @@ SIGNATURES = {
     "mapf_gae": (ctypes.c_int, [P, P, P, P, P, I32, I32, ctypes.c_double, ctypes.c_double, P]),
     "mapf_normalize_advantages": (ctypes.c_int, [P, P, P, P, P, P, I32, ctypes.c_double, I32, P]),
     "mapf_sample_actions": (ctypes.c_int, [P, I32, P, P, I32, ctypes.c_uint64, U32, P]),
+    "mapf_minibatch_rows": (ctypes.c_int, [ctypes.c_uint64, U32, I64, I64, I64, P, P]),
+    "mapf_minibatch_rows_host": (ctypes.c_int, [ctypes.c_uint64, U32, I64, I64, I64, P]),
+    "mapf_gather_rows": (ctypes.c_int, [ctypes.POINTER(GatherSpec), P]),
     "mapf_advantage_moments": (ctypes.c_int, [P, P, P, P, I32, P, P, P]),
     "mapf_normalize_advantages_stats": (ctypes.c_int, [P, P, P, P, P, P, P, I32, ctypes.c_double, I32, P]),
     "mapf_normalize_advantages_stats_dlam": (ctypes.c_int, [P, P, P, P, P, P, P, I32, P, I32, P]),

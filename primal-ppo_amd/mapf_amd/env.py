@@ -610,3 +610,61 @@ def sample_actions(ps, seed, step, out32=None, out64=None):
     _lib.check(_lib.lib().mapf_sample_actions(_ptr(ps2), ps2.stride(0), _ptr(out32), _ptr(out64), M, seed, step,
                                               _stream(ps.device)))
     return out32 if out32 is not None else out64
+
+
+def minibatch_rows(n, seed, epoch, start, count, out=None, device=None):
+    """Rows [start, start + count) of epoch `epoch`'s permutation of [0, n) (mapf_minibatch_rows:
+    a keyed bijection computed element by element, no sort and no host indices): an int64 tensor
+    [count].  out: the tensor to write (its device decides where); device="cpu" (or a CPU `out`)
+    runs the host twin, the same function on the host -- no GPU needed."""
+    n, start, count = int(n), int(start), int(count)
+    if out is not None:
+        device = out.device
+    device = torch.device("cuda" if device is None else device)
+    if out is None:
+        out = torch.empty(max(count, 0), dtype=torch.int64, device=device)
+    _check(out, torch.int64, max(count, 0), None, "out")
+    seed, epoch = int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF
+    if device.type == "cpu":
+        _lib.check(_lib.lib().mapf_minibatch_rows_host(seed, epoch, n, start, count, _ptr(out)))
+    else:
+        _lib.check(_lib.lib().mapf_minibatch_rows(seed, epoch, n, start, count, _ptr(out), _stream(out.device)))
+    return out
+
+
+def gather_rows(srcs, T, B, rows, dsts):
+    """dsts[a][j] = srcs[a][rows[j] % T, rows[j] // T] for up to 16 arrays in ONE launch
+    (mapf_gather_rows): srcs t-major contiguous [T, B, ...] rollout buffers (views that start inside
+    their storage included), rows int64 [M] on the device, ENV-MAJOR row ids in [0, B * T) (row r =
+    env r // T, step r % T: runner.EnvMajorRows' order), dsts contiguous with M leading rows.  The
+    rows are not range-checked on the device and not read back here: pass rows from minibatch_rows,
+    or check explicit indices on the host first (DeviceTrainer / Model.train_rows do).  Capturable."""
+    srcs, dsts = list(srcs), list(dsts)
+    if len(srcs) != len(dsts) or not 1 <= len(srcs) <= _lib.GATHER_MAX:
+        raise ValueError(f"gather_rows: {len(srcs)} sources and {len(dsts)} destinations (1..{_lib.GATHER_MAX} pairs)")
+    T, B = int(T), int(B)
+    if T < 1 or B < 1:
+        raise ValueError("gather_rows: T and B must be >= 1")
+    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
+        raise ValueError("gather_rows: rows must be a tensor on the GPU")
+    dev, M = rows.device, rows.numel()
+    _check(rows, torch.int64, M, dev, "rows")
+    if M < 1:
+        raise ValueError("gather_rows: no rows")
+    spec = _lib.GatherSpec(T=T, B=B, M=M, rows=rows.data_ptr(), count=len(srcs))
+    for a, (src, dst) in enumerate(zip(srcs, dsts)):
+        if not isinstance(src, torch.Tensor) or not isinstance(dst, torch.Tensor):
+            raise TypeError(f"gather_rows: pair {a} is not a pair of tensors")
+        if src.dtype != dst.dtype or src.device != dev or dst.device != dev:
+            raise ValueError(f"gather_rows: pair {a}: {src.dtype} on {src.device} -> {dst.dtype} on {dst.device}, "
+                             f"rows on {dev}")
+        if src.dim() < 2 or tuple(src.shape[:2]) != (T, B) or not src.is_contiguous():
+            raise ValueError(f"gather_rows: source {a} must be a contiguous [T={T}, B={B}, ...] buffer, got "
+                             f"{tuple(src.shape)}")
+        row = src[0, 0].numel()
+        if dst.dim() < 1 or dst.shape[0] != M or dst.numel() != M * row or not dst.is_contiguous():
+            raise ValueError(f"gather_rows: destination {a} must be contiguous with {M} rows of {row} elements, "
+                             f"got {tuple(dst.shape)}")
+        spec.arrays[a] = _lib.GatherArray(src.data_ptr(), dst.data_ptr(), row * src.element_size())
+    _lib.check(_lib.lib().mapf_gather_rows(ctypes.byref(spec), _stream(dev)))
+    return dsts

@@ -292,6 +292,19 @@ class Model:
         The loss scale and its growth tracker are net_scaler's own tensors (one AMP state per
         model, as the reference's one GradScaler, shared by every minibatch shape and by the
         eager path)."""
+        upd = self._device_update(observation, vector, returns, old_ps, train_valid, action)
+        upd.load(observation, vector, returns, cost_returns, old_v, old_cv, action, old_ps, train_valid,
+                 coef=self._loss_coef(lam), lam=lam)
+        return self._run_device_update(upd, episode_cost, distributed)
+
+    @staticmethod
+    def _loss_coef(lam):
+        T = TrainingParameters
+        return (T.CLIP_RANGE, T.ENTROPY_COEF, T.VALUE_COEF, T.VALID_COEF, T.COST_VALUE_COEF, T.COST_COEF * lam)
+
+    def _device_update(self, observation, vector, returns, old_ps, train_valid, action):
+        """The _DeviceUpdate of this minibatch shape (the arguments give shapes only; a new one is made
+        when net_scaler was replaced or reconfigured)."""
         key = (tuple(observation.shape), tuple(vector.shape), tuple(old_ps.shape), tuple(train_valid.shape))
         sc = self.net_scaler
         if sc._scale is None:
@@ -301,10 +314,10 @@ class Model:
             upd = None                        # net_scaler replaced or reconfigured: re-capture
         if upd is None:
             upd = self._updates[key] = _DeviceUpdate(self, observation, vector, returns, old_ps, train_valid, action)
-        T = TrainingParameters
-        upd.load(observation, vector, returns, cost_returns, old_v, old_cv, action, old_ps, train_valid,
-                 coef=(T.CLIP_RANGE, T.ENTROPY_COEF, T.VALUE_COEF, T.VALID_COEF, T.COST_VALUE_COEF, T.COST_COEF * lam),
-                 lam=lam)
+        return upd
+
+    def _run_device_update(self, upd, episode_cost, distributed):
+        """One update from upd's loaded static inputs, the Lagrangian step, and the 12 stats."""
         upd.run(graph=self.graph_update, allreduce=distributed)
         # the Lagrangian step (host, model.py:180) depends only on the episode cost
         if distributed:   # every rank must update the multiplier with the same episode cost
@@ -315,6 +328,45 @@ class Model:
         self.network.weights_updated()        # replays bump no tensor version: drop the fp16 acting copies
         stats = upd.stats.cpu().numpy()       # one device -> host copy
         return [np.asarray(v) for v in stats] + [self.lagrange.get_lagrangian_param()]
+
+    def train_rows(self, runner, rows, episode_cost, checked=False):
+        """One update on the env-major rows `rows` of runner's last rollout (a DeviceRunner; row r =
+        env r // T, step r % T, runner.EnvMajorRows' order), read straight from its device buffers:
+        _train_device with _DeviceUpdate.load_rows in place of load -- one HIP launch gathers the nine
+        training arrays into the captured update's static inputs (no host indices, no per-array
+        indexing or copy launches).  Keyed and captured exactly as Model.train's device update, whose
+        _DeviceUpdate of the same minibatch shape it shares.  rows: int64 device tensor (e.g.
+        env.minibatch_rows) or any driver-style host index; range-checked as runner._row_index does
+        unless checked=True says the caller has (device rows then cost no read-back).  Returns the
+        same 12 stats as train().  A model that is not on the GPU, or has fused_loss off, trains
+        through train() on torch-indexed rows."""
+        from .runner import _row_index
+        T, B = runner.T, runner.env.B
+        dev = self.device
+        if getattr(runner, "returns", True) is None:
+            raise RuntimeError("train_rows: the runner holds no rollout yet (call runner.run() first)")
+        if not (checked and isinstance(rows, torch.Tensor) and rows.dtype == torch.int64 and rows.dim() == 1):
+            rows, _ = _row_index(rows, T * B, dev)
+        if dev.type != "cuda" or not self.fused_loss:
+            mb = runner.batch()
+            return self.train(mb.observations[rows], mb.vectors[rows], mb.returns[rows], mb.costReturns[rows],
+                              mb.values[rows], mb.costValues[rows], mb.actions[rows], mb.ps[rows],
+                              mb.hiddenState[rows], mb.trainValid[rows], episode_cost)
+        if isinstance(rows, np.ndarray):
+            rows = torch.from_numpy(rows)
+        rows = rows.to(dev, non_blocking=True).contiguous()
+        buffers = (runner.obs[:T], runner.vec[:T], runner.returns, runner.cost_returns, runner.values,
+                   runner.cost_values, runner.actions, runner.ps, runner.train_valid)
+        M = rows.numel()
+        meta = lambda x, *tail: torch.empty((M,) + tuple(x.shape[2:]) + tail, device="meta")   # noqa: E731
+        obs, vec, ret, _, _, _, act, ps, tv = buffers
+        upd = self._device_update(meta(obs), meta(vec), meta(ret), meta(ps), meta(tv), meta(act, 1))
+        lam = self.lagrange.get_lagrangian_param()
+        distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        if self.distributed_update is not None:
+            distributed = bool(self.distributed_update) and dist.is_available() and dist.is_initialized()
+        upd.load_rows(buffers, T, B, rows, coef=self._loss_coef(lam), lam=lam)
+        return self._run_device_update(upd, episode_cost, distributed)
 
     def _finish_update(self, all_loss, policy_loss, entropy, critic_loss, valid_loss, cost_critic_loss, cost_loss,
                        clip_frac, advantage, cost_advantage, episode_cost, distributed):
@@ -411,9 +463,23 @@ class _DeviceUpdate:
                          (self.v, old_v), (self.cv, old_cv), (self.old_ps, old_ps), (self.tv, train_valid)):
             dst.copy_(src.reshape(dst.shape), non_blocking=True)
         self.action.copy_(action.reshape(self.action.shape), non_blocking=True)
+        self._load_dyn(coef, lam)
+
+    def _load_dyn(self, coef, lam):
         # host double -> f32 exactly as the host-argument kernels round them
         h = torch.tensor(list(coef) + [lam, lam + 1.0], dtype=torch.float64).float()
         self.dyn.copy_(h.pin_memory() if torch.cuda.is_available() else h, non_blocking=True)
+
+    def load_rows(self, buffers, T, B, rows, coef, lam):
+        """load() straight from a rollout's t-major [T, B, ...] device buffers: buffers = (obs, vec,
+        returns, cost returns, values, cost values, actions int64, ps, train_valid), rows = int64
+        device tensor of env-major row ids in [0, B * T), one per minibatch row.  One gather launch
+        (env.gather_rows) fills the nine static inputs; with the coefficients' copy that is two
+        launches per minibatch."""
+        from .env import gather_rows
+        gather_rows(buffers, T, B, rows, (self.obs, self.vec, self.ret, self.cret, self.v, self.cv, self.action,
+                                          self.old_ps, self.tv))
+        self._load_dyn(coef, lam)
 
     def _front(self, allreduce):
         """normalise -> forward -> fused loss -> backward (graph segment A when distributed); with
