@@ -281,6 +281,24 @@ int mapf_set_tuning(mapf_env *env, const mapf_tuning *t);
  * kernel's name reads e.g. "rollout_random_kernel<true,4,band64>"; the text for 0 and 1 is as before. */
 int mapf_rollout_plan(const mapf_env *env, int32_t slots, char *buf, int32_t n);
 
+/* T x mapf_step_observe(actions_in + t*B*N, ...): the caller's policy, T steps, ONE launch where
+ * mapf_rollout_random_fused says so (same kernels, same coverage), otherwise T per-step launches --
+ * identical results.  actions_in: DEVICE int32 [T][B][N], read-only, always [T]-leading whatever
+ * `slots` says; values outside 0..4 are counted (the bad-action counter) and played as 0, exactly
+ * as mapf_step does.  slots / out / obs / vec and MAPF_SLOTS_BAND_CLEAN: as mapf_rollout_random.
+ * actions_fixed (out) is what was executed.  The tape is read by the launch, on the stream, not by
+ * the call; it must not overlap out->actions_fixed (MAPF_EINVAL).  T = 0 does nothing.  Like
+ * mapf_rollout_random the call allocates, copies and waits for nothing and may be captured (the
+ * three-wave form takes an argument slot, mapf_release_captures). */
+int mapf_rollout_actions(mapf_env *env, int32_t T, int32_t slots, const int32_t *actions_in,
+                         const mapf_step_out *out, float *obs, float *vec, void *stream);
+/* mapf_rollout_plan for mapf_rollout_actions: the same text with ",tape" inside the angle brackets,
+ * e.g. "rollout_random_kernel<true,4,band64,tape>", "rollout_wide3_kernel<u64,1,true,tape>".  The
+ * pair-lane kernel stages tape_k steps of an env's actions in LDS; where that does not fit the
+ * grouped form the text says ungrouped=tape_lds, and where it does not fit at all the
+ * one-wave-per-env kernel runs (kind 2). */
+int mapf_rollout_actions_plan(const mapf_env *env, int32_t slots, char *buf, int32_t n);
+
 /* Launch the search work a committed step left pending (agent.bfsMap updates, the
  * humans' next paths) on its own; mapf_observe otherwise runs it inside the
  * observation launch.  Any later call that needs it flushes implicitly.

@@ -296,6 +296,19 @@ int mapf_rollout_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
     return kind;
 }
 
+int mapf_rollout_actions_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
+    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
+    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
+    // the pair-lane kernel where its staged tape rows fit the LDS, else the wide kernel, as the launch
+    if (rollout_random_fusable(e->d) && describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n, true)) return 1;
+    if (rollout_wide_fusable(e->d)) {
+        describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n, true);
+        return 2;
+    }
+    std::snprintf(buf, (size_t)n, "step_observe");
+    return 0;
+}
+
 int mapf_obs_band_skip(const mapf_config *cfg, int32_t unit, uint64_t byte_offset, uint8_t *skip, int32_t n) {
     if (!cfg || !skip || n < 0) return fail(MAPF_EINVAL, "null argument");
     if (unit != 0 && unit != 16 && unit != 64 && unit != 128) return fail(MAPF_EINVAL, "unit must be 0, 16, 64 or 128");
@@ -681,6 +694,61 @@ int mapf_rollout_random(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_
             ot.reward_total = adv(out->reward_total, BN);
         }
         if (int rc = step_observe_impl(e, actions_out + k * BN, out ? &ot : nullptr, 2u, obs + k * obs_t,
+                                       vec + k * BN * 4, stream))
+            return rc;
+    }
+    return MAPF_OK;
+}
+
+int mapf_rollout_actions(mapf_env *e, int32_t T, int32_t slots, const int32_t *actions_in, const mapf_step_out *out,
+                         float *obs, float *vec, void *stream) {
+    if (!e || !actions_in || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
+    if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
+    if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN)) return fail(MAPF_EINVAL, "slots: unknown bits");
+    if (!e->ready) return fail(MAPF_ESTATE, "mapf_rollout_actions before mapf_reset");
+    const size_t BN = (size_t)e->d.B * e->d.N, obs_t = BN * e->d.C * e->d.F * e->d.F;
+    if (out && out->actions_fixed && T > 0) {      // the tape is read while actions_fixed is written
+        const uintptr_t a0 = (uintptr_t)actions_in, a1 = a0 + (size_t)T * BN * 4;
+        const uintptr_t f0 = (uintptr_t)out->actions_fixed, f1 = f0 + ((slots & 1) ? (size_t)T : 1) * BN * 4;
+        if (a0 < f1 && f0 < a1) return fail(MAPF_EINVAL, "actions_in overlaps out->actions_fixed");
+    }
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    StepOut o{};
+    if (out) {
+        o.status = out->status; o.reward = out->reward; o.shadow_goals = out->shadow_goals; o.cost = out->cost;
+        o.train_valid = out->train_valid; o.actions_fixed = out->actions_fixed; o.goals_reached = out->goals_reached;
+        o.constraints = out->constraints; o.reward_total = out->reward_total;
+    }
+    if (T == 0) return MAPF_OK;
+    int32_t *tape = const_cast<int32_t *>(actions_in);      // the TAPE kernels only read it
+    if (rollout_random_fused(e)) {
+        if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
+        // the wide kernel takes what the pair-lane one does not (a tape whose staged rows pass its LDS included)
+        int rc = launch_rollout_random(e->d, T, tape, o, obs, vec, slots, e->tune, e->args, s, true);
+        if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
+            rc = launch_rollout_wide(e->d, T, tape, o, obs, vec, slots & 1, e->tune, e->args, s, true);
+        if (rc == MAPF_ESTATE)
+            return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
+                                     "(16 per handle, ArgRing; mapf_release_captures frees them)");
+        if (rc == MAPF_OK) {
+            HIPCHK(hipGetLastError());
+            return MAPF_OK;
+        }
+    }
+    // not covered by a one-launch kernel: T step_observe launches, same results
+    for (int32_t t = 0; t < T; ++t) {
+        const size_t k = (slots & 1) ? (size_t)t : 0;
+        mapf_step_out ot{};
+        if (out) {
+            auto adv = [&](auto *p, size_t n) { return p ? p + k * n : p; };
+            ot.status = adv(out->status, BN); ot.reward = adv(out->reward, BN);
+            ot.shadow_goals = adv(out->shadow_goals, (size_t)e->d.B); ot.cost = adv(out->cost, BN);
+            ot.train_valid = adv(out->train_valid, BN * 5); ot.actions_fixed = adv(out->actions_fixed, BN);
+            ot.goals_reached = adv(out->goals_reached, BN); ot.constraints = adv(out->constraints, BN);
+            ot.reward_total = adv(out->reward_total, BN);
+        }
+        if (int rc = step_observe_impl(e, tape + (size_t)t * BN, out ? &ot : nullptr, 0u, obs + k * obs_t,
                                        vec + k * BN * 4, stream))
             return rc;
     }

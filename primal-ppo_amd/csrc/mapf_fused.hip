@@ -24,6 +24,8 @@
 // the BFS channel, which is not fused).  The step of this launch reads none of
 // what they write (the path buffer it walks is the other one).
 #include <cstdio>
+#include <cstring>
+#include <type_traits>
 
 #include "mapf_step_pairs.h"
 #include "mapf_search.h"
@@ -136,7 +138,7 @@ __device__ inline void step_pairs_search_inline(const DevEnv &e, const PairsDefe
 // drain: no launch boundary, dispatch ramp or state reload per step.  Step t's
 // outputs go to slot t of the buffers when `slots` is set (rollout buffers).
 struct RolloutOut {
-    int32_t *actions;
+    int32_t *actions;   // the drawn actions (out); TAPE: the caller's [T][B][N] tape, read only
     StepOut out;
     float *obs, *vec;
     int slots;
@@ -159,8 +161,18 @@ __host__ __device__ inline bool rollout_fusable(const DevEnv &e) {
 
 // LDS of a rollout workgroup: observation layout | nibble table | 4 search scratch | 4 path copies
 __host__ __device__ inline size_t rollout_obs_lds(const DevEnv &e) { return ((obs_lds_bytes(e, 4, true) + 15) & ~(size_t)15) + 256; }
-__host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e) {
-    return rollout_obs_lds(e) + 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W) + 4 * (size_t)e.Lmax * 4;
+// TAPE: + 4 waves x TAPE_K staged rows (8 slots each, N <= 8) of the action tape (below)
+constexpr int TAPE_K = 32;
+// How a TAPE wave fetches its rows.  0 (shipped): TAPE_K rows staged in LDS at a time.  Experiment
+// builds (make variant VFLAGS=-DMAPF_TAPE_FETCH=n; DESIGN.md 9f has their numbers): 1 the step's
+// plain per-step vector load, 2 step t + 1's row loaded before step t's observation stores and
+// handed to the step through LDS.
+#ifndef MAPF_TAPE_FETCH
+#define MAPF_TAPE_FETCH 0
+#endif
+__host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, bool tape = false) {
+    return rollout_obs_lds(e) + 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W) + 4 * (size_t)e.Lmax * 4 +
+           (tape ? 4 * (size_t)TAPE_K * 8 * 4 : 0);
 }
 
 // NT: nontemporal observation stores -- for slot buffers (fresh HBM lines every step,
@@ -170,7 +182,13 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e) {
 // each can see how far the others are (pacing, below)
 // BAND: a slot-buffer launch with MAPF_SLOTS_BAND_CLEAN -- the wave leaves out the stores that lie
 // wholly inside its env's zero band (obs_band_skip; the band of every slot already holds zeros)
-template <bool NT, int SUBS, bool BAND = false>
+// TAPE: the caller's actions (mapf_rollout_actions) instead of the Philox draw.  Step t plays row
+// [t][b] of ro.actions, [T][B][N] whatever `slots` says.  A vector load in the loop is waited
+// for behind the wave's own observation stores (vmcnt counts both, in order) at every step:
+// 2-3 % where the chip is partly filled and the step's latency sets the pace.
+// So the wave stages its env's next TAPE_K rows in LDS -- the loop's one global read and one full
+// drain per TAPE_K steps -- and the step reads its actions from LDS (step_pairs_env<.., LDSACT>).
+template <bool NT, int SUBS, bool BAND = false, bool TAPE = false>
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_kernel(
 #if MAPF_ARGS_PTR      // experiment build: arguments through a device pointer (mapf_rollout_wide.hip)
     const RolloutArgs *__restrict__ args, int T) {
@@ -207,6 +225,9 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
     const size_t swl = srch::wave_lds<uint32_t, 1>(e.H, e.W);
     char *slds = qsm + rollout_obs_lds(e) + (size_t)le * swl;
     uint32_t *lpath = reinterpret_cast<uint32_t *>(qsm + rollout_obs_lds(e) + 4 * swl) + (size_t)le * e.Lmax;
+    // TAPE: this wave's TAPE_K staged rows, after the quarter's path copies
+    int32_t *trow = nullptr;
+    if constexpr (TAPE) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e)) + (size_t)le * TAPE_K * 8;
     const uint32_t mreg = obs_map_word(e, b0, nenv, (int)(threadIdx.x & 63));
     EnvRegs rs{};
     if (le < nenv) env_regs_load<8>(e, b0 + le, rs, lpath);
@@ -226,6 +247,12 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
             band_mask = obs_band_skip_mask(e, MAPF_BAND_UNIT, (size_t)(ro.obs + (size_t)(b0 + le) * e.N * e.C * e.F * e.F),
                                            (int)(threadIdx.x & 63));
     }
+#if MAPF_TAPE_FETCH == 2
+    int32_t tnext = 0;
+    if (TAPE && le < nenv && (int)(threadIdx.x & 63) < e.N && T > 0)
+        tnext = ro.actions[(size_t)(b0 + le) * e.N + (threadIdx.x & 63)];
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
     RSTAMP_BEGIN();
     const bool pacing = SUBS > 1 && ro.slack >= 0 && le < nenv;
     const bool fair = SUBS > 1 && ro.fair > 0 && le < nenv;
@@ -239,6 +266,35 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
         }
         const size_t BN = (size_t)E.B * E.N;
         const size_t s = R.slots ? (size_t)t : 0;
+#if MAPF_TAPE_FETCH == 2
+        if constexpr (TAPE) {
+            if (le < nenv && (int)(threadIdx.x & 63) < 8) as_lds(trow)[threadIdx.x & 63] = tnext;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+#elif MAPF_TAPE_FETCH == 0
+        if constexpr (TAPE) {
+            if ((t & (TAPE_K - 1)) == 0) {
+                if (le < nenv) {        // rows [t, t + TAPE_K) of this env, inside [T][B][N]
+                    // lane -> agent lane & 7 of rows (lane >> 3) + 8k; the opaque copy keeps the
+                    // addresses out of the loop's invariants (hoisted, they held 20 VGPRs through
+                    // the whole loop: 128 VGPRs and scratch in the band form)
+                    int lane = (int)(threadIdx.x & 63);
+                    asm volatile("" : "+v"(lane));
+                    const int i = lane & 7, r0 = lane >> 3, nrow = min(TAPE_K, T - t);
+                    const int32_t *src = R.actions + ((size_t)(t + r0) * E.B + (size_t)(b0 + le)) * E.N + i;
+                    int32_t v[TAPE_K / 8];
+#pragma unroll
+                    for (int k = 0; k < TAPE_K / 8; ++k)
+                        v[k] = (i < E.N && r0 + 8 * k < nrow) ? src[(size_t)(8 * k) * BN] : 0;
+#pragma unroll
+                    for (int k = 0; k < TAPE_K / 8; ++k) as_lds(trow)[lane + 64 * k] = v[k];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+#endif
         StepOut o = R.out;
         if (o.status) o.status += s * BN;
         if (o.reward) o.reward += s * BN;
@@ -250,8 +306,19 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
         if (o.constraints) o.constraints += s * BN;
         if (o.reward_total) o.reward_total += s * BN;
         PairsDeferred dfr;
-        step_pairs_env<8, true, true, true>(E, R.actions + s * BN, o, 3u, 0, blk * 256 + qt,
-                                            L, b0, RegMap{mreg, true}, dfr, &rs);
+#if MAPF_TAPE_FETCH == 1
+        step_pairs_env<8, true, true, true>(E, R.actions + (TAPE ? (size_t)t : s) * BN, o, TAPE ? 1u : 3u, 0,
+                                            blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
+#else
+        constexpr int TROW = MAPF_TAPE_FETCH == 2 ? 0 : TAPE_K - 1;      // the staged row of step t
+        step_pairs_env<8, true, true, true, TAPE>(E, TAPE ? trow + (size_t)(t & TROW) * 8 : R.actions + s * BN,
+                                                  o, TAPE ? 1u : 3u, 0, blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr,
+                                                  &rs);
+#endif
+#if MAPF_TAPE_FETCH == 2
+        if (TAPE && le < nenv && (int)(threadIdx.x & 63) < E.N && t + 1 < T)
+            tnext = R.actions[((size_t)(t + 1) * E.B + (size_t)(b0 + le)) * E.N + (threadIdx.x & 63)];
+#endif
         if (le < nenv) {
             const ObsGroup g = obs_wave_init(E, L, le, mreg);
             if (BAND && band_moves)
@@ -277,10 +344,12 @@ struct RolloutPlan {
     int grid = 0;        // workgroups
     size_t lds = 0;      // dynamic LDS request
     int sub_lds = 0, slack = -1, fair = 0, remap = 1;
+    bool tape_ungrouped = false;   // tape: the staged rows did not fit the grouped form's LDS
 };
 
-static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p) {
-    if (!rollout_random_fusable(e)) return false;
+// tape: the caller's-actions form (its staged rows take LDS; past 64 KiB the wide kernel takes over)
+static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p, bool tape = false) {
+    if (!rollout_random_fusable(e) || rollout_lds_bytes(e, tape) > 64 * 1024) return false;
     const int grid = (e.B + 3) / 4;
     // Persistent waves: every CU should hold the same number of workgroups, or the
     // CUs holding more set the pace of every step.  The LDS request caps the
@@ -288,7 +357,7 @@ static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &t
     const int ncu = device_cu_count();
     int occ = (grid + ncu - 1) / ncu;
     if (tu.roll_occ >= 1 && tu.roll_occ <= 16) occ = tu.roll_occ;
-    size_t lds = rollout_lds_bytes(e);
+    size_t lds = rollout_lds_bytes(e, tape);
     const size_t cap = ((size_t)160 * 1024 / (size_t)occ) & ~(size_t)255;
     if (occ >= 3 && cap > lds && cap <= 64 * 1024) lds = cap;
     // Slot buffers at four workgroups per CU (c2): one workgroup of all 16 waves instead,
@@ -301,10 +370,12 @@ static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &t
     // waits: a wave more than 4 steps ahead of the group's slowest env drops to priority 0, the
     // rest run at 2 -- no wave ever idles, and the youngest wave of a SIMD no longer trails
     // (13.9-14.0 -> 11.9-12.0 us per step; roll_fair 0 with roll_group 0: four workgroups, unpaced).
-    const size_t sub = (rollout_lds_bytes(e) + 15) & ~(size_t)15;
+    const size_t sub = (rollout_lds_bytes(e, tape) + 15) & ~(size_t)15;
     const int fair = tu.roll_fair >= 0 ? tu.roll_fair : (slots ? 0 : 4);
-    const bool group = occ == 4 && grid % 4 == 0 && 4 * sub + 64 <= (size_t)device_max_group_lds() &&
-                       (tu.roll_group < 0 ? slots != 0 || fair > 0 : tu.roll_group != 0);
+    const bool want_group = occ == 4 && grid % 4 == 0 && (tu.roll_group < 0 ? slots != 0 || fair > 0 : tu.roll_group != 0);
+    const bool group = want_group && 4 * sub + 64 <= (size_t)device_max_group_lds();
+    p.tape_ungrouped = tape && want_group && !group &&
+                       4 * ((rollout_lds_bytes(e) + 15) & ~(size_t)15) + 64 <= (size_t)device_max_group_lds();
     p.subs = group ? 4 : 1;
     p.grid = grid / p.subs;
     p.lds = group ? (size_t)device_max_group_lds() : lds;   // grouped: the whole CU
@@ -321,28 +392,32 @@ static bool rollout_band_form(const DevEnv &e, int slots) {
     return (slots & MAPF_SLOTS_BAND_CLEAN) && (slots & 1) && obs_zero_band(e, z0, z1) && obs_band_iters(e) <= 32;
 }
 
-void describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n) {
+bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, bool tape) {
     const bool band = rollout_band_form(e, slots);
     slots &= 1;
     RolloutPlan p;
-    if (!plan_rollout_random(e, slots, tu, p)) {
+    if (!plan_rollout_random(e, slots, tu, p, tape)) {
         std::snprintf(buf, n, "none");
-        return;
+        return false;
     }
-    char form[24] = "";
+    char form[32] = "";
     if (band) std::snprintf(form, sizeof form, ",band%d", MAPF_BAND_UNIT);
-    std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
-                  slots ? "true" : "false", p.subs, form, p.grid, 256 * p.subs, p.lds, p.subs > 1 ? p.fair : 0,
-                  p.subs > 1 ? p.slack : -1, p.remap);
+    if (tape) std::snprintf(form + std::strlen(form), sizeof form - std::strlen(form), ",tape");
+    const int k = std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
+                                slots ? "true" : "false", p.subs, form, p.grid, 256 * p.subs, p.lds, p.subs > 1 ? p.fair : 0,
+                                p.subs > 1 ? p.slack : -1, p.remap);
+    if (tape && k > 0 && (size_t)k < n)
+        std::snprintf(buf + k, n - (size_t)k, " tape_k=%d%s", TAPE_K, p.tape_ungrouped ? " ungrouped=tape_lds" : "");
+    return true;
 }
 
 // slots: the MAPF_SLOTS_* bits of mapf_rollout_random
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                          int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s) {
+                          int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, bool tape) {
     const bool band = rollout_band_form(e, slots) && ((uintptr_t)obs & 15) == 0;     // whole float4s
     slots &= 1;
     RolloutPlan p;
-    if (!plan_rollout_random(e, slots, tu, p)) return ROLLOUT_NOT_COVERED;
+    if (!plan_rollout_random(e, slots, tu, p, tape)) return ROLLOUT_NOT_COVERED;
     const RolloutOut ro{actions, out, obs, vec, slots, p.remap, p.sub_lds, p.slack, p.fair};
     auto launch = [&](auto kern) -> int {
         const dim3 gd(p.grid), bd(256 * p.subs);
@@ -356,9 +431,15 @@ int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOu
         return MAPF_OK;
     };
     (void)ring;
-    if (band) return p.subs == 4 ? launch(rollout_random_kernel<true, 4, true>) : launch(rollout_random_kernel<true, 1, true>);
-    if (p.subs == 4) return slots ? launch(rollout_random_kernel<true, 4>) : launch(rollout_random_kernel<false, 4>);
-    return slots ? launch(rollout_random_kernel<true, 1>) : launch(rollout_random_kernel<false, 1>);
+    auto pick = [&](auto tp) -> int {
+        constexpr bool TP = decltype(tp)::value;
+        if (band)
+            return p.subs == 4 ? launch(rollout_random_kernel<true, 4, true, TP>) : launch(rollout_random_kernel<true, 1, true, TP>);
+        if (p.subs == 4)
+            return slots ? launch(rollout_random_kernel<true, 4, false, TP>) : launch(rollout_random_kernel<false, 4, false, TP>);
+        return slots ? launch(rollout_random_kernel<true, 1, false, TP>) : launch(rollout_random_kernel<false, 1, false, TP>);
+    };
+    return tape ? pick(std::true_type{}) : pick(std::false_type{});
 }
 
 bool step_observe_fusable(const DevEnv &e) {

@@ -89,18 +89,22 @@ void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, 
 // (the kernel's form from the handle's tuning, mapf.h: mapf_tuning); describe_* write the
 // form launch_* would take as text (mapf_rollout_plan).  launch_/describe_rollout_random take
 // mapf_rollout_random's `slots` bits (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN), the wide ones 0 / 1.
+// tape (mapf_rollout_actions): `actions` is the caller's [T][B][N] tape, read only, played instead
+// of the random draw (the kernels' TAPE instantiations; the plan's text carries ",tape").
+// describe_rollout_random returns false (text "none") where the pair-lane kernel does not take the
+// launch -- with a tape that includes a fusable configuration whose staged rows do not fit its LDS.
 constexpr int ROLLOUT_NOT_COVERED = 1;
 bool rollout_random_fusable(const DevEnv &e);
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                           int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s);
-void describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n);
+                           int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, bool tape = false);
+bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, bool tape = false);
 // the same for up to 64 agents / per-env maps / the BFS channel: one wave per env
 // (mapf_rollout_wide.hip); used where the pair-lane rollout does not apply.  Returns MAPF_OK or
 // MAPF_ESTATE (a captured launch found no free argument slot, ArgRing).
 bool rollout_wide_fusable(const DevEnv &e);
 int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                        int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s);
-void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n);
+                        int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, bool tape = false);
+void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, bool tape = false);
 
 // Device-resident kernel argument blocks.  A persistent kernel whose arguments (DevEnv + its
 // output pointers, ~0.5 KiB) do not fit in the SGPR file kept them live from the kernarg

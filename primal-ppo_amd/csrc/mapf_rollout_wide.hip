@@ -34,7 +34,7 @@
 namespace mapf {
 
 struct WideOut {
-    int32_t *actions;
+    int32_t *actions;   // the drawn actions (out); TAPE: the caller's [T][B][N] tape, read only
     StepOut out;
     float *obs, *vec;
     int slots;
@@ -181,7 +181,11 @@ __device__ inline void wide_plain_barrier() {
 #define WIDE_BIND
 #endif
 
-template <class T, int RW, bool NT>
+// TAPE: the caller's actions (mapf_rollout_actions) instead of the Philox draw: step t plays row
+// [t] of ro.actions ([T][B][N] whatever `slots` says), each lane loading its own agent's action in
+// the step's first round of loads, beside the human's path cells -- the stepping wave already
+// waits for those there, so the tape adds a load to that round and no wait of its own.
+template <class T, int RW, bool NT, bool TAPE = false>
 __device__ __attribute__((always_inline)) inline void rollout_wide_body(const DevEnv &e, int T_steps, const WideOut &ro) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // XCD-aware env order (as the pair-lane rollout): workgroups are dealt round-robin
@@ -326,7 +330,9 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
             else __builtin_amdgcn_s_setprio(2);
         }
         StepInline inl;
-        if (stepper) step_group<WaveGroup, true, true>(e, lact + s * BN, step_out(s), 3u, 0, b, g, &inl, src, rs, have);
+        if (stepper)
+            step_group<WaveGroup, true, true>(e, lact + (TAPE ? (size_t)t : s) * BN, step_out(s), TAPE ? 1u : 3u, 0, b, g,
+                                              &inl, src, rs, have);
         WSTAMP(0);
         // A: observation t-1 done.  Nothing the observer reads from HBM was written by the step
         // (its outputs and state are not read back), so the stepper does not wait for them.
@@ -427,10 +433,10 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
     WSTAMP_END(b, role);
 }
 
-template <class T, int RW, bool NT>
+template <class T, int RW, bool NT, bool TAPE = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void rollout_wide_kernel(WIDE_PARAMS) {
     WIDE_BIND
-    rollout_wide_body<T, RW, NT>(e, T_steps, ro);
+    rollout_wide_body<T, RW, NT, TAPE>(e, T_steps, ro);
 }
 
 // Three waves per env (c4): the stepper and two observers taking alternate steps.  With one
@@ -438,10 +444,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void r
 // SIMD issuing each step's 31 KiB of stores).  Three waves per SIMD need <= 168 VGPRs:
 // the arguments come through a device pointer (ArgRing), which also frees the ~450 SGPRs the
 // by-value arguments spilled to VGPR lanes (152 VGPRs, 129 SGPR spills, no scratch).
-template <class T, int RW, bool NT>
+template <class T, int RW, bool NT, bool TAPE = false>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void rollout_wide3_kernel(
     const WideArgs *__restrict__ args, int T_steps) {
-    rollout_wide_body<T, RW, NT>(args->e, T_steps, args->ro);
+    rollout_wide_body<T, RW, NT, TAPE>(args->e, T_steps, args->ro);
 }
 
 // The three-wave form is not built for 128-bit rows spread over two lanes (maps wider than 64 cells):
@@ -463,7 +469,8 @@ struct WidePlan {
     int grid = 0, block = 0;
 };
 
-template <class T, int RW>
+// TAPE: the form of the caller's-actions kernels (their own register counts decide what fits)
+template <class T, int RW, bool TAPE = false>
 static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     WidePlan p;
     // persistent waves: every CU holds the same number of workgroups (the LDS request caps
@@ -476,12 +483,12 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     // 446 MB, measured 94 vs 124 us per step); smaller ones keep plain stores (c2, c4;
     // c4 in place, nt sc1: 6.27 -> 7.03 us per step)
     p.nt = tu.wide_nt >= 0 ? tu.wide_nt != 0 : (slots || (size_t)e.B * e.N * e.C * e.F * e.F * 4 > ((size_t)128 << 20));
-    const void *kern = p.nt ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, true>)
-                            : reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, false>);
+    const void *kern = p.nt ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, true, TAPE>)
+                            : reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, false, TAPE>);
     const void *kern3 = nullptr;
     if constexpr (wide3_form<T, RW>())
-        kern3 = p.nt ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, true>)
-                     : reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, false>);
+        kern3 = p.nt ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, true, TAPE>)
+                     : reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, false, TAPE>);
     // two waves per env where every env's pair fits at once: the VGPR budget of a SIMD
     // (512 per lane) over the waves it must hold, 4 SIMDs per CU
     const int fit = 512 / ((kernel_vgprs(kern) + 7) & ~7);
@@ -547,10 +554,10 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     return p;
 }
 
-template <class T, int RW>
+template <class T, int RW, bool TAPE>
 static int launch_wide_t(const DevEnv &e, int steps, const WideOut &ro, const mapf_tuning &tu, ArgRing &ring,
                          hipStream_t s) {
-    const WidePlan p = plan_wide_t<T, RW>(e, ro.slots, tu);
+    const WidePlan p = plan_wide_t<T, RW, TAPE>(e, ro.slots, tu);
     WideOut r = p.r;
     r.actions = ro.actions;
     r.out = ro.out;
@@ -560,12 +567,12 @@ static int launch_wide_t(const DevEnv &e, int steps, const WideOut &ro, const ma
         if (r.wpe == 3) {
             const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
             if (!args) return MAPF_ESTATE;
-            auto kern3 = p.nt ? rollout_wide3_kernel<T, RW, true> : rollout_wide3_kernel<T, RW, false>;
+            auto kern3 = p.nt ? rollout_wide3_kernel<T, RW, true, TAPE> : rollout_wide3_kernel<T, RW, false, TAPE>;
             hipLaunchKernelGGL(kern3, dim3(p.grid), dim3(p.block), p.lds, s, args, steps);
             return MAPF_OK;
         }
     }
-    auto kern = p.nt ? rollout_wide_kernel<T, RW, true> : rollout_wide_kernel<T, RW, false>;
+    auto kern = p.nt ? rollout_wide_kernel<T, RW, true, TAPE> : rollout_wide_kernel<T, RW, false, TAPE>;
 #if MAPF_ARGS_PTR
     const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
     if (!args) return MAPF_ESTATE;
@@ -597,7 +604,7 @@ bool rollout_wide_fusable(const DevEnv &e) {
 }
 
 int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                        int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s) {
+                        int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, bool tape) {
     WideOut ro{};
     ro.actions = actions;
     ro.out = out;
@@ -605,17 +612,19 @@ int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut 
     ro.vec = vec;
     ro.slots = slots;
     return with_row_type(e, [&](auto t, auto rw) {
-        return launch_wide_t<decltype(t), decltype(rw)::value>(e, T, ro, tu, ring, s);
+        return tape ? launch_wide_t<decltype(t), decltype(rw)::value, true>(e, T, ro, tu, ring, s)
+                    : launch_wide_t<decltype(t), decltype(rw)::value, false>(e, T, ro, tu, ring, s);
     });
 }
 
-void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n) {
+void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, bool tape) {
     with_row_type(e, [&](auto t, auto rw) {
-        const WidePlan p = plan_wide_t<decltype(t), decltype(rw)::value>(e, slots, tu);
-        std::snprintf(buf, n, "%s<%s,%d,%s> grid=%d block=%d lds=%zu wpe=%d epw=%d grid_mode=%d overlap=%d slack=%d "
+        const WidePlan p = tape ? plan_wide_t<decltype(t), decltype(rw)::value, true>(e, slots, tu)
+                                : plan_wide_t<decltype(t), decltype(rw)::value, false>(e, slots, tu);
+        std::snprintf(buf, n, "%s<%s,%d,%s%s> grid=%d block=%d lds=%zu wpe=%d epw=%d grid_mode=%d overlap=%d slack=%d "
                               "fair=%d prio=%d bfsobs=%d pair=%d remap=%d",
                       p.r.wpe == 3 ? "rollout_wide3_kernel" : "rollout_wide_kernel", row_name<decltype(t)>(),
-                      (int)decltype(rw)::value, p.nt ? "true" : "false", p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
+                      (int)decltype(rw)::value, p.nt ? "true" : "false", tape ? ",tape" : "", p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
                       p.r.grid, p.r.overlap, p.r.slack, p.r.fair, p.r.prio, p.r.bfsobs, p.r.pair, p.r.xcd_remap);
         return 0;
     });

@@ -159,7 +159,9 @@ __device__ inline void step_pairs_finish(const DevEnv &e, const PairsDeferred &d
 // INLINE (NP = 8, the multi-step rollout kernel): no work lists -- the search
 // items are left in dfr for step_pairs_search_inline() on the same wave.
 // RES (with INLINE): the env state lives in *rs (EnvRegs) instead of HBM.
-template <int NP, bool FEED, bool INLINE = false, bool RES = false>
+// LDSACT (the tape rollout, caller's actions): `actions` is this env's row of N actions in LDS
+// (index = agent), so the step loop reads no global memory.
+template <int NP, bool FEED, bool INLINE = false, bool RES = false, bool LDSACT = false>
 __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restrict__ actions, const StepOut &out,
                                                uint32_t flags, int slot, int gt, const ObsLds &ob, int b0,
                                                RegMap rm, PairsDeferred &dfr, EnvRegs *rs = nullptr) {
@@ -226,8 +228,14 @@ __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restr
         a_j = random_action(o, j);
         if (vi && head) actions[ai] = a_i;
     } else {
-        a_i = vi ? actions[ai] : 0;
-        a_j = vj ? actions[aj] : 0;
+        if constexpr (LDSACT) {
+            const auto row = as_lds(actions);
+            a_i = vi ? row[i] : 0;
+            a_j = vj ? row[j] : 0;
+        } else {
+            a_i = vi ? actions[ai] : 0;
+            a_j = vj ? actions[aj] : 0;
+        }
         if (vi && head && (a_i < 0 || a_i >= NA)) atomicAdd(&e.counters[C_BAD_ACTION], 1u);
         if (a_i < 0 || a_i >= NA) a_i = 0;
         if (a_j < 0 || a_j >= NA) a_j = 0;

@@ -93,6 +93,8 @@ SIGNATURES = {
     "mapf_get_tuning": (ctypes.c_int, [P, ctypes.POINTER(Tuning)]),
     "mapf_set_tuning": (ctypes.c_int, [P, ctypes.POINTER(Tuning)]),
     "mapf_rollout_plan": (ctypes.c_int, [P, I32, ctypes.c_char_p, I32]),
+    "mapf_rollout_actions": (ctypes.c_int, [P, I32, I32, P, ctypes.POINTER(StepOut), P, P, P]),
+    "mapf_rollout_actions_plan": (ctypes.c_int, [P, I32, ctypes.c_char_p, I32]),
     "mapf_flush": (ctypes.c_int, [P, P]),
     "mapf_release_captures": (ctypes.c_int, [P]),
     "mapf_random_actions": (ctypes.c_int, [P, P, P]),

@@ -137,6 +137,20 @@ class BatchedMapfGym:
         """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,false>'."""
         return self.rollout_plan(slots).split(" ")[0]
 
+    def rollout_actions_plan(self, slots=False, band_clean=False):
+        """rollout_plan for rollout_actions (mapf_rollout_actions_plan): the same text with ",tape"
+        inside the angle brackets, or "step_observe" where the call runs per-step launches."""
+        buf = ctypes.create_string_buffer(512)
+        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
+        kind = _lib.lib().mapf_rollout_actions_plan(self.h, bits, buf, 512)
+        if kind < 0:
+            _lib.check(kind)
+        return buf.value.decode()
+
+    def rollout_actions_kernel_name(self, slots=False, band_clean=False):
+        """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,tape>'."""
+        return self.rollout_actions_plan(slots, band_clean).split(" ")[0]
+
     @staticmethod
     def _make_stepout(out):
         so = _lib.StepOut()
@@ -337,7 +351,49 @@ class BatchedMapfGym:
                                                   _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
 
-    def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None):
+    def _check_tape(self, tape, T=None):
+        """An action tape: int32 [T, B, N], contiguous, on the handle's GPU (the kernels read it
+        through a raw pointer).  Returns T."""
+        if not isinstance(tape, torch.Tensor):
+            raise TypeError(f"tape: expected a torch.Tensor, got {type(tape).__name__}")
+        if tape.dim() != 3 or tuple(tape.shape[1:]) != (self.B, self.N) or (T is not None and tape.shape[0] != T):
+            raise ValueError(f"tape: shape {tuple(tape.shape)}, expected [{'T' if T is None else T}, {self.B}, {self.N}]")
+        _check(tape, torch.int32, tape.shape[0] * self.B * self.N, self.device, "tape")
+        return int(tape.shape[0])
+
+    def _rollout_buffers(self, k, obs, vec, out, slots):
+        """The output buffers of a rollout call (k = T with slots, else 1), checked: (so, out, obs, vec)."""
+        obs = self.obs if obs is None else obs
+        vec = self.vec if vec is None else vec
+        _check(obs, torch.float32, k * self.B * self.N * self.C * self.F * self.F, self.device, "obs")
+        _check(vec, torch.float32, k * self.B * self.N * 4, self.device, "vec")
+        if out is None:
+            if slots:
+                raise ValueError("slots=True needs [T]-leading output buffers (out=...)")
+            return self._stepout, self.out, obs, vec
+        for key, t in out.items():
+            ref = self.out[key]
+            _check(t, ref.dtype, k * ref.numel(), self.device, key)
+        return self._make_stepout(out), out, obs, vec
+
+    def rollout_actions(self, tape, slots=False, obs=None, vec=None, out=None, band_clean=False):
+        """T x step_observe(tape[t]) -- the caller's policy, T = tape.shape[0] steps -- as ONE launch
+        where rollout_fused (the rollout kernels' tape instantiations, rollout_actions_plan), else
+        T per-step launches; identical results.  tape: int32 [T, B, N] on the device, read by the
+        launch (not by this call), always [T]-leading; values outside 0..4 are counted as bad
+        actions and played as 0.  slots, obs, vec, out, band_clean: as rollout_random;
+        out["actions_fixed"] is what was executed and must not overlap the tape.
+        Returns (out, obs, vec)."""
+        T = self._check_tape(tape)
+        so, out, obs, vec = self._rollout_buffers(T if slots else 1, obs, vec, out, slots)
+        if T == 0:          # nothing to play (an empty tensor has no address to hand over)
+            return out, obs, vec
+        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
+        _lib.check(_lib.lib().mapf_rollout_actions(self.h, T, bits, _ptr(tape), ctypes.byref(so), _ptr(obs), _ptr(vec),
+                                                   _stream(self.device)))
+        return out, obs, vec
+
+    def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None, actions_in=None):
         """rollout_random(T, slots, ...) prepared once: the buffers are checked and the C call's
         arguments built now, on the current stream; the returned callable issues the launch with
         no per-call host work beyond one ctypes call (a 20-step rollout is ~350 us on the GPU, the
@@ -348,12 +404,19 @@ class BatchedMapfGym:
         while use_hp is off) is already clean, and the kernel leaves those stores out
         (MAPF_SLOTS_BAND_CLEAN, mapf.h).  The contract: between calls of one launcher nobody writes
         non-zeros into that band of `obs`.  Whoever does (or hands the memory to something that
-        may) calls launch.invalidate(): the next call stores everything again."""
+        may) calls launch.invalidate(): the next call stores everything again.
+
+        actions_in: an int32 [T, B, N] tape -- the launcher then issues rollout_actions(actions_in,
+        slots, ...) instead (`actions` is not used), under the same band rule.  The tape's contents
+        are read at launch time: refill the same tensor between calls to play other actions."""
         k = T if slots else 1
+        if actions_in is not None:
+            self._check_tape(actions_in, int(T))
+            actions = actions_in
         actions = self.actions if actions is None else actions
         obs = self.obs if obs is None else obs
         vec = self.vec if vec is None else vec
-        _check(actions, torch.int32, k * self.B * self.N, self.device, "actions")
+        _check(actions, torch.int32, (T if actions_in is not None else k) * self.B * self.N, self.device, "actions")
         _check(obs, torch.float32, k * self.B * self.N * self.C * self.F * self.F, self.device, "obs")
         _check(vec, torch.float32, k * self.B * self.N * 4, self.device, "vec")
         if out is None:
@@ -366,7 +429,7 @@ class BatchedMapfGym:
         args = (self.h, int(T), _lib.SLOTS if slots else 0, _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec),
                 _stream(self.device))
         clean = args[:2] + (_lib.SLOTS | _lib.SLOTS_BAND_CLEAN,) + args[3:] if slots else args
-        fn = _lib.lib().mapf_rollout_random
+        fn = _lib.lib().mapf_rollout_random if actions_in is None else _lib.lib().mapf_rollout_actions
         keep = (so, actions, obs, vec, out)
         state = [args]                  # the next call's arguments: `clean` once a call has stored the band
 

@@ -152,8 +152,31 @@ METRIC_KEYS = ("episodeReward", "episodeCostReward", "humanCollide", "staticColl
                "shadowGoals", "constraintViolations")
 
 
+def _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human_movement_type, k_predict, fix_choice):
+    """The BatchedMapfGym of one map-shape group of episodes, reset to their starts (FixedMapfGym)."""
+    from .env import BatchedMapfGym
+    n = len(infos["agentsSequence"][idx[0]])
+    S = max(len(s) for i in idx for s in infos["agentsSequence"][i])
+    HS = max(len(infos["humanSequence"][i]) for i in idx) if human_movement_type == 1 else 2
+    cfg = make_config(len(idx), H, W, num_agents=n, fov=fov, num_channel=num_channel, use_da=int(use_da),
+                      use_hp=int(use_hp), human_mode="fixed_path" if human_movement_type == 1 else "looping",
+                      goal_mode="sequence", fix_choice=fix_choice, shared_map=False, keep_bfs=False, max_seq=S,
+                      max_human_seq=HS)
+    cfg.k_predict = k_predict
+    env = BatchedMapfGym(cfg, device=device)
+    env.episodes = idx
+    maps = np.stack([np.asarray(infos["obstacleMap"][i]) for i in idx]).astype(np.int8)
+    seqs = [infos["agentsSequence"][i] for i in idx]
+    if human_movement_type == 1:
+        env.reset_fixed(maps, seqs, human_seq=[infos["humanSequence"][i] for i in idx])
+    else:
+        env.reset_fixed(maps, seqs, human_start=[infos["humanStart"][i] for i in idx],
+                        human_goal=[infos["humanGoal"][i] for i in idx])
+    return env
+
+
 def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, use_da=False, use_hp=False,
-                            human_movement_type=0, max_steps=256, k_predict=5, fix_choice=1):
+                            human_movement_type=0, max_steps=256, k_predict=5, fix_choice=1, record_actions=False):
     """evaluate() (evaluate.py:169-269) for every episode at once.
 
     policy(obs [B,N,C,F,F], vec [B,N,4], env, t) -> int32 [B,N] device actions
@@ -161,33 +184,25 @@ def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, us
     lists the episode indices of env's rows (one env per map shape).
     fix_choice: fixActions' random.choice -- 1 Philox, 0 the rotating rule.
     human_movement_type 0: LoopingHuman(humanStart, humanGoal); 1: FixedPathHuman(humanSequence).
-    Returns {metric: float64 numpy [E]} in episode order (OneEpPerformance fields)."""
-    from .env import BatchedMapfGym
+    Returns {metric: float64 numpy [E]} in episode order (OneEpPerformance fields).
+    record_actions: return (metrics, tapes) instead -- tapes[(H, W)] = the policy's actions of that
+    map-shape group (not the executed actions_fixed), int32 [max_steps, len(group), N] on the
+    device: what replay_fixed_episodes plays back."""
     device = torch.device("cuda") if device is None else torch.device(device)
     E = infos["numEpisodes"]
     res = {k: np.zeros(E, np.float64) for k in METRIC_KEYS}
+    tapes = {}
     for (H, W), idx in sorted(_groups_by_shape(infos).items()):
-        n = len(infos["agentsSequence"][idx[0]])
-        S = max(len(s) for i in idx for s in infos["agentsSequence"][i])
-        HS = max(len(infos["humanSequence"][i]) for i in idx) if human_movement_type == 1 else 2
-        cfg = make_config(len(idx), H, W, num_agents=n, fov=fov, num_channel=num_channel, use_da=int(use_da),
-                          use_hp=int(use_hp), human_mode="fixed_path" if human_movement_type == 1 else "looping",
-                          goal_mode="sequence", fix_choice=fix_choice, shared_map=False, keep_bfs=False, max_seq=S,
-                          max_human_seq=HS)
-        cfg.k_predict = k_predict
-        env = BatchedMapfGym(cfg, device=device)
-        env.episodes = idx
-        maps = np.stack([np.asarray(infos["obstacleMap"][i]) for i in idx]).astype(np.int8)
-        seqs = [infos["agentsSequence"][i] for i in idx]
-        if human_movement_type == 1:
-            env.reset_fixed(maps, seqs, human_seq=[infos["humanSequence"][i] for i in idx])
-        else:
-            env.reset_fixed(maps, seqs, human_start=[infos["humanStart"][i] for i in idx],
-                            human_goal=[infos["humanGoal"][i] for i in idx])
+        env = _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human_movement_type, k_predict,
+                         fix_choice)
+        if record_actions:
+            tapes[(H, W)] = torch.empty(max_steps, env.B, env.N, dtype=torch.int32, device=env.device)
         acc = torch.zeros((len(idx), len(METRIC_KEYS)), dtype=torch.float64, device=device)
         obs, vec = env.observe()
         for t in range(max_steps):
             acts = policy(obs, vec, env, t)
+            if record_actions:
+                tapes[(H, W)][t].copy_(acts)
             out, obs, vec = env.step_observe(acts)
             st = out["status"]
             acc[:, 0] += out["reward_total"].double().sum(1)
@@ -198,6 +213,39 @@ def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, us
             acc[:, 5] += out["goals_reached"].double().sum(1)
             acc[:, 6] += out["shadow_goals"].double()
             acc[:, 7] += out["constraints"].double().sum(1)
+        a = acc.cpu().numpy()
+        for k, key in enumerate(METRIC_KEYS):
+            res[key][idx] = a[:, k]
+        env.close()
+    return (res, tapes) if record_actions else res
+
+
+def replay_fixed_episodes(infos, tapes, device=None, num_channel=6, fov=9, use_da=False, use_hp=False,
+                          human_movement_type=0, k_predict=5, fix_choice=1):
+    """evaluate_fixed_episodes over recorded actions: tapes[(H, W)] = int32 [T, len(group), N] device
+    tensors keyed like its map-shape groups (evaluate_fixed_episodes(..., record_actions=True), or any
+    recorded or planned joint actions).  One rollout_actions launch per group into [T]-slot step
+    outputs, the OneEpPerformance sums taken once at the end in float64; the observations go to
+    scratch slots (the metrics do not read them).  Same env arguments, same {metric: float64 [E]}:
+    the integer metrics equal evaluate_fixed_episodes', the float sums up to summation order."""
+    device = torch.device("cuda") if device is None else torch.device(device)
+    E = infos["numEpisodes"]
+    res = {k: np.zeros(E, np.float64) for k in METRIC_KEYS}
+    for (H, W), idx in sorted(_groups_by_shape(infos).items()):
+        env = _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human_movement_type, k_predict,
+                         fix_choice)
+        tape = tapes[(H, W)]
+        T = int(tape.shape[0])
+        keys = ("status", "reward_total", "cost", "goals_reached", "shadow_goals", "constraints")
+        out = {k: torch.empty((T,) + tuple(env.out[k].shape), dtype=env.out[k].dtype, device=env.device) for k in keys}
+        obs = torch.empty((T,) + tuple(env.obs.shape), dtype=torch.float32, device=env.device)
+        vec = torch.empty((T,) + tuple(env.vec.shape), dtype=torch.float32, device=env.device)
+        env.rollout_actions(tape, slots=True, obs=obs, vec=vec, out=out)
+        st = out["status"]
+        acc = torch.stack([out["reward_total"].double().sum((0, 2)), out["cost"].double().sum((0, 2)),
+                           (st == -2).sum((0, 2)).double(), (st == -1).sum((0, 2)).double(),
+                           (st == -3).sum((0, 2)).double(), out["goals_reached"].double().sum((0, 2)),
+                           out["shadow_goals"].double().sum(0), out["constraints"].double().sum((0, 2))], dim=1)
         a = acc.cpu().numpy()
         for k, key in enumerate(METRIC_KEYS):
             res[key][idx] = a[:, k]
