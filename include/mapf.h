@@ -299,6 +299,25 @@ int mapf_rollout_actions(mapf_env *env, int32_t T, int32_t slots, const int32_t 
  * one-wave-per-env kernel runs (kind 2). */
 int mapf_rollout_actions_plan(const mapf_env *env, int32_t slots, char *buf, int32_t n);
 
+/* The descent policy, T steps: independent shortest-path followers, every agent one step down
+ * its own agent.bfsMap (mapf_descent_actions has the rule) -- the heuristic baseline a learned
+ * policy is compared with, and the rollout kernels' cost where goals change often.  ONE launch
+ * where mapf_rollout_random_fused says so (the same kernels' descent instantiations picking the
+ * actions in-kernel from the tiled maps), otherwise T x (mapf_descent_actions,
+ * mapf_step_observe) -- identical results.  actions_out receives the chosen actions; slots /
+ * actions_out / out / obs / vec and MAPF_SLOTS_BAND_CLEAN: as mapf_rollout_random.  Requires
+ * keep_bfs (MAPF_ESTATE otherwise).  T = 0 does nothing.  Like mapf_rollout_random the call
+ * allocates, copies and waits for nothing and may be captured. */
+int mapf_rollout_descent(mapf_env *env, int32_t T, int32_t slots, int32_t *actions_out,
+                         const mapf_step_out *out, float *obs, float *vec, void *stream);
+/* mapf_rollout_plan for mapf_rollout_descent: the same text with ",descent" inside the angle
+ * brackets, e.g. "rollout_random_kernel<true,4,descent>", "rollout_wide3_kernel<u64,1,true,descent>".
+ * The pair-lane text ends with the way the map cells are fetched (fetch=load) and, where the
+ * hand-over row does not fit the grouped form's LDS, ungrouped=descent_lds.  The wide three-wave
+ * form always says bfsobs=0: the stepping wave searches the maps it reads (wide_bfsobs is
+ * ignored).  Kind 0: "descent_actions+step_observe", the per-step launches. */
+int mapf_rollout_descent_plan(const mapf_env *env, int32_t slots, char *buf, int32_t n);
+
 /* Launch the search work a committed step left pending (agent.bfsMap updates, the
  * humans' next paths) on its own; mapf_observe otherwise runs it inside the
  * observation launch.  Any later call that needs it flushes implicitly.
@@ -320,6 +339,20 @@ int mapf_release_captures(mapf_env *env);
 
 /* Uniform random policy (Philox, counter = env clock): DEVICE int32 [B][N]. */
 int mapf_random_actions(mapf_env *env, int32_t *actions, void *stream);
+
+/* The descent policy's actions for the current state: DEVICE int32 [B][N] (requires keep_bfs,
+ * MAPF_ESTATE otherwise; flushes pending search work first, as mapf_observe does).  Agent i of an
+ * env at clock t (steps since reset), D = its agent.bfsMap, own = D[pos]: S = the moves k in 1..4
+ * whose target cell is inside the map with 0 <= D[target] < own (the BFS channel's rule); the
+ * action is 0 if own <= 0 (at the goal, or the goal unreachable) or S is empty, else
+ * mapf_descent_pick(S, t, i).  Other agents and the human are ignored: the step resolves what
+ * that causes, as for any caller's actions. */
+int mapf_descent_actions(mapf_env *env, int32_t *actions, void *stream);
+/* The pick among the descent moves, on the host (the function the kernels run): descent_mask bit
+ * k (1..4) = move k is in S; returns the first k = 1 + ((k0 + m) & 3), m = 0..3, in S, where
+ * k0 = (clock + agent) & 3 -- the rotation keeps two agents from making the same tie-break
+ * forever -- or 0 if S is empty.  Bits other than 1..4 are ignored. */
+int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent);
 
 /* Copy agent.bfsMap for every agent: DEVICE int16 [B][N][H][W] (requires keep_bfs). */
 int mapf_bfs(mapf_env *env, int16_t *dist, void *stream);

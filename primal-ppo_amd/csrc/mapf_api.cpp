@@ -300,13 +300,31 @@ int mapf_rollout_actions_plan(const mapf_env *e, int32_t slots, char *buf, int32
     if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
     if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
     // the pair-lane kernel where its staged tape rows fit the LDS, else the wide kernel, as the launch
-    if (rollout_random_fusable(e->d) && describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n, true)) return 1;
+    if (rollout_random_fusable(e->d) && describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n, ROLLOUT_TAPE)) return 1;
     if (rollout_wide_fusable(e->d)) {
-        describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n, true);
+        describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n, ROLLOUT_TAPE);
         return 2;
     }
     std::snprintf(buf, (size_t)n, "step_observe");
     return 0;
+}
+
+int mapf_rollout_descent_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
+    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
+    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
+    // the pair-lane kernel where its action rows fit the LDS, else the wide kernel, as the launch
+    if (rollout_random_fusable(e->d) && describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n, ROLLOUT_DESCENT))
+        return 1;
+    if (rollout_wide_fusable(e->d)) {
+        describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n, ROLLOUT_DESCENT);
+        return 2;
+    }
+    std::snprintf(buf, (size_t)n, "descent_actions+step_observe");
+    return 0;
+}
+
+int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent) {
+    return descent_pick(descent_mask, clock, (int)agent);
 }
 
 int mapf_obs_band_skip(const mapf_config *cfg, int32_t unit, uint64_t byte_offset, uint8_t *skip, int32_t n) {
@@ -725,9 +743,9 @@ int mapf_rollout_actions(mapf_env *e, int32_t T, int32_t slots, const int32_t *a
     if (rollout_random_fused(e)) {
         if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
         // the wide kernel takes what the pair-lane one does not (a tape whose staged rows pass its LDS included)
-        int rc = launch_rollout_random(e->d, T, tape, o, obs, vec, slots, e->tune, e->args, s, true);
+        int rc = launch_rollout_random(e->d, T, tape, o, obs, vec, slots, e->tune, e->args, s, ROLLOUT_TAPE);
         if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
-            rc = launch_rollout_wide(e->d, T, tape, o, obs, vec, slots & 1, e->tune, e->args, s, true);
+            rc = launch_rollout_wide(e->d, T, tape, o, obs, vec, slots & 1, e->tune, e->args, s, ROLLOUT_TAPE);
         if (rc == MAPF_ESTATE)
             return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
                                      "(16 per handle, ArgRing; mapf_release_captures frees them)");
@@ -749,6 +767,67 @@ int mapf_rollout_actions(mapf_env *e, int32_t T, int32_t slots, const int32_t *a
             ot.reward_total = adv(out->reward_total, BN);
         }
         if (int rc = step_observe_impl(e, tape + (size_t)t * BN, out ? &ot : nullptr, 0u, obs + k * obs_t,
+                                       vec + k * BN * 4, stream))
+            return rc;
+    }
+    return MAPF_OK;
+}
+
+int mapf_descent_actions(mapf_env *e, int32_t *actions, void *stream) {
+    if (!e || !actions) return fail(MAPF_EINVAL, "null argument");
+    if (!e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
+    if (!e->ready) return fail(MAPF_ESTATE, "mapf_descent_actions before mapf_reset");
+    HIPCHK(hipSetDevice(e->device));
+    if (int rc = flush_search(e, (hipStream_t)stream)) return rc;      // the maps of the last step's new goals
+    launch_descent_actions(e->d, actions, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+int mapf_rollout_descent(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
+                         float *obs, float *vec, void *stream) {
+    if (!e || !actions_out || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
+    if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
+    if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN)) return fail(MAPF_EINVAL, "slots: unknown bits");
+    if (!e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
+    if (!e->ready) return fail(MAPF_ESTATE, "mapf_rollout_descent before mapf_reset");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    StepOut o{};
+    if (out) {
+        o.status = out->status; o.reward = out->reward; o.shadow_goals = out->shadow_goals; o.cost = out->cost;
+        o.train_valid = out->train_valid; o.actions_fixed = out->actions_fixed; o.goals_reached = out->goals_reached;
+        o.constraints = out->constraints; o.reward_total = out->reward_total;
+    }
+    if (T == 0) return MAPF_OK;
+    if (rollout_random_fused(e)) {
+        if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
+        int rc = launch_rollout_random(e->d, T, actions_out, o, obs, vec, slots, e->tune, e->args, s, ROLLOUT_DESCENT);
+        if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
+            rc = launch_rollout_wide(e->d, T, actions_out, o, obs, vec, slots & 1, e->tune, e->args, s, ROLLOUT_DESCENT);
+        if (rc == MAPF_ESTATE)
+            return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
+                                     "(16 per handle, ArgRing; mapf_release_captures frees them)");
+        if (rc == MAPF_OK) {
+            HIPCHK(hipGetLastError());
+            return MAPF_OK;
+        }
+    }
+    // not covered by a one-launch kernel: T x (descent_actions, step_observe), same results
+    const size_t BN = (size_t)e->d.B * e->d.N, obs_t = BN * e->d.C * e->d.F * e->d.F;
+    for (int32_t t = 0; t < T; ++t) {
+        const size_t k = (slots & 1) ? (size_t)t : 0;
+        mapf_step_out ot{};
+        if (out) {
+            auto adv = [&](auto *p, size_t n) { return p ? p + k * n : p; };
+            ot.status = adv(out->status, BN); ot.reward = adv(out->reward, BN);
+            ot.shadow_goals = adv(out->shadow_goals, (size_t)e->d.B); ot.cost = adv(out->cost, BN);
+            ot.train_valid = adv(out->train_valid, BN * 5); ot.actions_fixed = adv(out->actions_fixed, BN);
+            ot.goals_reached = adv(out->goals_reached, BN); ot.constraints = adv(out->constraints, BN);
+            ot.reward_total = adv(out->reward_total, BN);
+        }
+        if (int rc = mapf_descent_actions(e, actions_out + k * BN, stream)) return rc;
+        if (int rc = step_observe_impl(e, actions_out + k * BN, out ? &ot : nullptr, 0u, obs + k * obs_t,
                                        vec + k * BN * 4, stream))
             return rc;
     }

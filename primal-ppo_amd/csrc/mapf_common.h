@@ -191,6 +191,37 @@ __host__ __device__ inline int bfs_at(int W, int r, int c) {
     return ((((r >> 3) * bfs_tw(W)) + (c >> 3)) << 6) | ((r & 7) << 3) | (c & 7);
 }
 
+// The descent policy (mapf_descent_actions, mapf_rollout_descent; include/mapf.h: mapf_descent_pick
+// has the specification): independent shortest-path followers.  mask bit k (1..4) = move k leads
+// to a cell of the agent's BFS map closer to its goal (channel 6's rule); the pick is the first
+// such move from k0 = (clock + agent) & 3 on, 0 if there is none.  The one function every kernel
+// and the host export run.
+__host__ __device__ inline int descent_pick(uint32_t mask, uint32_t clock, int agent) {
+    const uint32_t k0 = (clock + (uint32_t)agent) & 3u, m4 = (mask >> 1) & 15u;
+    const uint32_t rot = ((m4 | (m4 << 4)) >> k0) & 15u;        // bit m = move 1 + ((k0 + m) & 3)
+    return rot ? 1 + (int)((k0 + (uint32_t)__builtin_ctz(rot)) & 3u) : 0;
+}
+// The descent action of agent `agent` at cell p, from its tiled map D (bfs + ai * bfs_cells):
+// own = D[p]; stay where own <= 0 (at the goal, or the goal unreachable: no 0 <= v < own exists).
+// Five loads in flight, one wait; a neighbour past the map's edge reads the agent's own cell and
+// is masked out.
+__device__ inline int descent_action(const DevEnv &e, const int16_t *D, uint32_t p, uint32_t clock,
+                                     int agent) {
+    const int r = prow(p), c = pcol(p);
+    int v[NA];
+    bool in[NA];
+#pragma unroll
+    for (int k = 0; k < NA; ++k) {
+        const int rr = r + dr(k), cc = c + dc(k);
+        in[k] = in_map(e, rr, cc);
+        v[k] = (int)D[bfs_at(e.W, in[k] ? rr : r, in[k] ? cc : c)];
+    }
+    uint32_t mask = 0;
+#pragma unroll
+    for (int k = 1; k < NA; ++k) mask |= (uint32_t)(in[k] && v[k] >= 0 && v[k] < v[0]) << k;
+    return descent_pick(mask, clock, agent);
+}
+
 __device__ inline uint32_t *human_path(const DevEnv &e, int b, int buf) {
     return e.hpath + ((size_t)b * 2 + buf) * e.Lmax;
 }

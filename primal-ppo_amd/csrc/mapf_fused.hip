@@ -108,13 +108,19 @@ __global__ __launch_bounds__(256) void step_observe_kernel(DevEnv e, int32_t *__
 // next path.  Same items, same results as the work-list searches.
 // map: the env's padded obstacle rows in the wave's LDS; rs: the resident state,
 // whose path lengths take the searched path's.
+// PLANES (the descent experiment, MAPF_DESCENT_FETCH 1): the env's [N][2][H] LDS bit planes, kept current
+template <bool PLANES = false>
 __device__ inline void step_pairs_search_inline(const DevEnv &e, const PairsDeferred &d, char *lds,
-                                                const uint32_t *map, EnvRegs &rs) {
+                                                const uint32_t *map, EnvRegs &rs, uint32_t *planes = nullptr) {
     for (uint64_t m = d.bmask; m; m &= m - 1ull) {
         const int l = __builtin_ctzll(m);
         const uint32_t ai = (uint32_t)__builtin_amdgcn_readlane((int)d.bitem, l);
         const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)d.bgoal, l);
-        srch::search_one<uint32_t, 1>(e, false, (int)(ai / (uint32_t)e.N), ai, g, NO_CELL, 0, lds, map);
+        if constexpr (PLANES)
+            srch::search_one<uint32_t, 1, true>(e, false, (int)(ai / (uint32_t)e.N), ai, g, NO_CELL, 0, lds, map,
+                                                planes + (size_t)(ai % (uint32_t)e.N) * 2 * e.H);
+        else
+            srch::search_one<uint32_t, 1>(e, false, (int)(ai / (uint32_t)e.N), ai, g, NO_CELL, 0, lds, map);
     }
     if (d.rmask) {
         const int l = __builtin_ctzll(d.rmask);
@@ -170,9 +176,20 @@ constexpr int TAPE_K = 32;
 #ifndef MAPF_TAPE_FETCH
 #define MAPF_TAPE_FETCH 0
 #endif
-__host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, bool tape = false) {
+// DESCENT: + 4 waves x one row of 8 picked actions (the hand-over to the step's pair lanes)
+// How a DESCENT wave fetches its agents' five map cells.  0 (shipped): a plain per-step load from the
+// tiled maps.  Experiment build (make variant VFLAGS=-DMAPF_DESCENT_FETCH=1): the env's
+// maps mod 4 as two bit planes per agent in the wave's LDS ([8][2][H] words), filled from the tiled
+// maps before the loop and rewritten by the inline search, so the loop stays load-free.
+#ifndef MAPF_DESCENT_FETCH
+#define MAPF_DESCENT_FETCH 0
+#endif
+__host__ __device__ inline size_t rollout_descent_lds(const DevEnv &e) {
+    return 4 * (size_t)8 * 4 + (MAPF_DESCENT_FETCH == 1 ? 4 * (size_t)8 * 2 * e.H * 4 : 0);
+}
+__host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy = ROLLOUT_RANDOM) {
     return rollout_obs_lds(e) + 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W) + 4 * (size_t)e.Lmax * 4 +
-           (tape ? 4 * (size_t)TAPE_K * 8 * 4 : 0);
+           (policy == ROLLOUT_TAPE ? 4 * (size_t)TAPE_K * 8 * 4 : (policy == ROLLOUT_DESCENT ? rollout_descent_lds(e) : 0));
 }
 
 // NT: nontemporal observation stores -- for slot buffers (fresh HBM lines every step,
@@ -188,7 +205,12 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, bool tape =
 // 2-3 % where the chip is partly filled and the step's latency sets the pace.
 // So the wave stages its env's next TAPE_K rows in LDS -- the loop's one global read and one full
 // drain per TAPE_K steps -- and the step reads its actions from LDS (step_pairs_env<.., LDSACT>).
-template <bool NT, int SUBS, bool BAND = false, bool TAPE = false>
+// DESCENT: the descent policy (mapf_rollout_descent) instead of the Philox draw.  The env's state
+// is in registers, so each agent's head lane reads the five cells of its tiled BFS map around
+// rs.pi, picks (descent_action) and hands the action to the pair lanes through the wave's LDS row,
+// as the tape does (LDSACT); ro.actions receives the picks like the random draw's.  The five loads
+// are a plain per-step vector load: waited for behind the wave's observation stores.
+template <bool NT, int SUBS, bool BAND = false, bool TAPE = false, bool DESCENT = false>
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_kernel(
 #if MAPF_ARGS_PTR      // experiment build: arguments through a device pointer (mapf_rollout_wide.hip)
     const RolloutArgs *__restrict__ args, int T) {
@@ -228,9 +250,34 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
     // TAPE: this wave's TAPE_K staged rows, after the quarter's path copies
     int32_t *trow = nullptr;
     if constexpr (TAPE) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e)) + (size_t)le * TAPE_K * 8;
+    if constexpr (DESCENT) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e)) + (size_t)le * 8;
     const uint32_t mreg = obs_map_word(e, b0, nenv, (int)(threadIdx.x & 63));
     EnvRegs rs{};
     if (le < nenv) env_regs_load<8>(e, b0 + le, rs, lpath);
+    uint32_t *wpl = nullptr;      // MAPF_DESCENT_FETCH 1: this wave's [N][2][H] bit planes, after the quarter's action rows
+#if MAPF_DESCENT_FETCH == 1
+    if constexpr (DESCENT) {
+        wpl = reinterpret_cast<uint32_t *>(qsm + rollout_lds_bytes(e)) + 4 * 8 + (size_t)le * 8 * 2 * e.H;
+        if (le < nenv) {          // lane = row: the maps mod 4 out of the tiled maps, once per launch
+            const int row = (int)(threadIdx.x & 63);
+            for (int i = 0; i < e.N; ++i) {
+                const int16_t *Dm = e.bfs + ((size_t)(b0 + le) * e.N + i) * bfs_cells(e.H, e.W);
+                uint32_t d0 = 0, d1 = 0;
+                if (row < e.H)
+                    for (int c = 0; c < e.W; ++c) {
+                        const int v = (int)Dm[bfs_at(e.W, row, c)];
+                        if (v >= 0) { d0 |= (uint32_t)(v & 1) << c; d1 |= (uint32_t)((v >> 1) & 1) << c; }
+                    }
+                if (row < e.H) {
+                    as_lds(wpl)[(size_t)(2 * i) * e.H + row] = d0;
+                    as_lds(wpl)[(size_t)(2 * i + 1) * e.H + row] = d1;
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+#endif
     // every prologue load has landed before the loop: otherwise the compiler keeps a
     // register's load "pending" at the loop header and waits vmcnt(0) -- i.e. behind
     // all of the previous step's stores -- where the loop uses it
@@ -295,6 +342,59 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
             }
         }
 #endif
+        if constexpr (DESCENT) {
+            // The maps read here were written before the launch (visible by the launch boundary)
+            // or by this very wave, in step_pairs_search_inline of an earlier step: one wave's
+            // vector stores and loads, same CU, performed in program order -- wavefront scope, so
+            // the fence emits nothing and only keeps the compiler from moving these int16 loads
+            // over the search's uint4 stores; the loads' own vmcnt wait is the only wait.
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#if MAPF_DESCENT_FETCH == 1
+            if (le < nenv) {
+                // The grid is bipartite: a free neighbour of a reachable cell lies one level up or
+                // down, so it is in S iff (D[n] - own) & 3 == 3; obstacles and cells past the edge
+                // (planes 0) are told apart by the register map.  own == 0 is pos == goal; an
+                // unreachable own cell has unreachable neighbours (all planes 0: S empty).
+                int lane = (int)(threadIdx.x & 63);
+                asm volatile("" : "+v"(lane));
+                const int i = lane >> 3, r = prow(rs.pi), c = pcol(rs.pi);
+                const auto pl = as_lds(wpl) + (size_t)min(i, E.N - 1) * 2 * E.H;
+                auto val = [&](int rr, int cc) {
+                    rr = min(max(rr, 0), E.H - 1);
+                    cc = min(max(cc, 0), E.W - 1);
+                    return ((pl[rr] >> cc) & 1u) | (((pl[E.H + rr] >> cc) & 1u) << 1);
+                };
+                const RegMap rmap{mreg, true};
+                const uint32_t own = val(r, c);
+                uint32_t mask = 0;
+#pragma unroll
+                for (int k = 1; k < NA; ++k) {
+                    const bool obst = rmap.obstacle(E, nullptr, r + dr(k), c + dc(k));     // every lane permutes
+                    mask |= (uint32_t)(!obst && ((val(r + dr(k), c + dc(k)) - own) & 3u) == 3u) << k;
+                }
+                if ((lane & 7) == 0 && i < E.N) {
+                    const size_t ai = (size_t)(b0 + le) * E.N + i;
+                    const int a = rs.pi == rs.gi ? 0 : descent_pick(mask, rs.clock, i);
+                    as_lds(trow)[i] = a;
+                    R.actions[s * BN + ai] = a;
+                }
+            }
+#else
+            if (le < nenv) {
+                int lane = (int)(threadIdx.x & 63);
+                asm volatile("" : "+v"(lane));          // addresses stay out of the loop's invariants (as the tape's)
+                const int i = lane >> 3;
+                if ((lane & 7) == 0 && i < E.N) {
+                    const size_t ai = (size_t)(b0 + le) * E.N + i;
+                    const int a = descent_action(E, E.bfs + ai * bfs_cells(E.H, E.W), rs.pi, rs.clock, i);
+                    as_lds(trow)[i] = a;
+                    R.actions[s * BN + ai] = a;
+                }
+            }
+#endif
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
         StepOut o = R.out;
         if (o.status) o.status += s * BN;
         if (o.reward) o.reward += s * BN;
@@ -307,13 +407,16 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
         if (o.reward_total) o.reward_total += s * BN;
         PairsDeferred dfr;
 #if MAPF_TAPE_FETCH == 1
-        step_pairs_env<8, true, true, true>(E, R.actions + (TAPE ? (size_t)t : s) * BN, o, TAPE ? 1u : 3u, 0,
-                                            blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
+        if constexpr (DESCENT)
+            step_pairs_env<8, true, true, true, true>(E, trow, o, 1u, 0, blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
+        else
+            step_pairs_env<8, true, true, true>(E, R.actions + (TAPE ? (size_t)t : s) * BN, o, TAPE ? 1u : 3u, 0,
+                                                blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
 #else
         constexpr int TROW = MAPF_TAPE_FETCH == 2 ? 0 : TAPE_K - 1;      // the staged row of step t
-        step_pairs_env<8, true, true, true, TAPE>(E, TAPE ? trow + (size_t)(t & TROW) * 8 : R.actions + s * BN,
-                                                  o, TAPE ? 1u : 3u, 0, blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr,
-                                                  &rs);
+        step_pairs_env<8, true, true, true, TAPE || DESCENT>(
+            E, TAPE ? trow + (size_t)(t & TROW) * 8 : (DESCENT ? trow : R.actions + s * BN), o, TAPE || DESCENT ? 1u : 3u, 0,
+            blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
 #endif
 #if MAPF_TAPE_FETCH == 2
         if (TAPE && le < nenv && (int)(threadIdx.x & 63) < E.N && t + 1 < T)
@@ -326,7 +429,7 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
                                                (size_t)(R.obs + (s * BN + (size_t)(b0 + le) * E.N) * E.C * E.F * E.F),
                                                (int)(threadIdx.x & 63));
             obs_emit<false, NT, BAND>(E, L, R.obs + s * BN * E.C * E.F * E.F, R.vec + s * BN * 4, g, b0, false, band_mask);
-            step_pairs_search_inline(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs);
+            step_pairs_search_inline<DESCENT && MAPF_DESCENT_FETCH == 1>(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs, wpl);
             if (pacing || fair) publish_count(prog + gw, (uint32_t)(t + 1));
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -344,12 +447,13 @@ struct RolloutPlan {
     int grid = 0;        // workgroups
     size_t lds = 0;      // dynamic LDS request
     int sub_lds = 0, slack = -1, fair = 0, remap = 1;
-    bool tape_ungrouped = false;   // tape: the staged rows did not fit the grouped form's LDS
+    bool tape_ungrouped = false;   // tape / descent: their LDS rows did not fit the grouped form's LDS
 };
 
-// tape: the caller's-actions form (its staged rows take LDS; past 64 KiB the wide kernel takes over)
-static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p, bool tape = false) {
-    if (!rollout_random_fusable(e) || rollout_lds_bytes(e, tape) > 64 * 1024) return false;
+// policy ROLLOUT_TAPE / ROLLOUT_DESCENT: the caller's-actions and descent forms (their LDS rows; past
+// 64 KiB the wide kernel takes over)
+static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p, int policy = ROLLOUT_RANDOM) {
+    if (!rollout_random_fusable(e) || rollout_lds_bytes(e, policy) > 64 * 1024) return false;
     const int grid = (e.B + 3) / 4;
     // Persistent waves: every CU should hold the same number of workgroups, or the
     // CUs holding more set the pace of every step.  The LDS request caps the
@@ -357,7 +461,7 @@ static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &t
     const int ncu = device_cu_count();
     int occ = (grid + ncu - 1) / ncu;
     if (tu.roll_occ >= 1 && tu.roll_occ <= 16) occ = tu.roll_occ;
-    size_t lds = rollout_lds_bytes(e, tape);
+    size_t lds = rollout_lds_bytes(e, policy);
     const size_t cap = ((size_t)160 * 1024 / (size_t)occ) & ~(size_t)255;
     if (occ >= 3 && cap > lds && cap <= 64 * 1024) lds = cap;
     // Slot buffers at four workgroups per CU (c2): one workgroup of all 16 waves instead,
@@ -370,11 +474,11 @@ static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &t
     // waits: a wave more than 4 steps ahead of the group's slowest env drops to priority 0, the
     // rest run at 2 -- no wave ever idles, and the youngest wave of a SIMD no longer trails
     // (13.9-14.0 -> 11.9-12.0 us per step; roll_fair 0 with roll_group 0: four workgroups, unpaced).
-    const size_t sub = (rollout_lds_bytes(e, tape) + 15) & ~(size_t)15;
+    const size_t sub = (rollout_lds_bytes(e, policy) + 15) & ~(size_t)15;
     const int fair = tu.roll_fair >= 0 ? tu.roll_fair : (slots ? 0 : 4);
     const bool want_group = occ == 4 && grid % 4 == 0 && (tu.roll_group < 0 ? slots != 0 || fair > 0 : tu.roll_group != 0);
     const bool group = want_group && 4 * sub + 64 <= (size_t)device_max_group_lds();
-    p.tape_ungrouped = tape && want_group && !group &&
+    p.tape_ungrouped = policy != ROLLOUT_RANDOM && want_group && !group &&
                        4 * ((rollout_lds_bytes(e) + 15) & ~(size_t)15) + 64 <= (size_t)device_max_group_lds();
     p.subs = group ? 4 : 1;
     p.grid = grid / p.subs;
@@ -392,32 +496,36 @@ static bool rollout_band_form(const DevEnv &e, int slots) {
     return (slots & MAPF_SLOTS_BAND_CLEAN) && (slots & 1) && obs_zero_band(e, z0, z1) && obs_band_iters(e) <= 32;
 }
 
-bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, bool tape) {
+bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy) {
+    const bool tape = policy == ROLLOUT_TAPE, descent = policy == ROLLOUT_DESCENT;
     const bool band = rollout_band_form(e, slots);
     slots &= 1;
     RolloutPlan p;
-    if (!plan_rollout_random(e, slots, tu, p, tape)) {
+    if (!plan_rollout_random(e, slots, tu, p, policy)) {
         std::snprintf(buf, n, "none");
         return false;
     }
     char form[32] = "";
     if (band) std::snprintf(form, sizeof form, ",band%d", MAPF_BAND_UNIT);
     if (tape) std::snprintf(form + std::strlen(form), sizeof form - std::strlen(form), ",tape");
+    if (descent) std::snprintf(form + std::strlen(form), sizeof form - std::strlen(form), ",descent");
     const int k = std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
                                 slots ? "true" : "false", p.subs, form, p.grid, 256 * p.subs, p.lds, p.subs > 1 ? p.fair : 0,
                                 p.subs > 1 ? p.slack : -1, p.remap);
     if (tape && k > 0 && (size_t)k < n)
         std::snprintf(buf + k, n - (size_t)k, " tape_k=%d%s", TAPE_K, p.tape_ungrouped ? " ungrouped=tape_lds" : "");
+    if (descent && k > 0 && (size_t)k < n)
+        std::snprintf(buf + k, n - (size_t)k, MAPF_DESCENT_FETCH == 1 ? " fetch=lds_planes%s" : " fetch=load%s", p.tape_ungrouped ? " ungrouped=descent_lds" : "");
     return true;
 }
 
 // slots: the MAPF_SLOTS_* bits of mapf_rollout_random
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                          int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, bool tape) {
+                          int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy) {
     const bool band = rollout_band_form(e, slots) && ((uintptr_t)obs & 15) == 0;     // whole float4s
     slots &= 1;
     RolloutPlan p;
-    if (!plan_rollout_random(e, slots, tu, p, tape)) return ROLLOUT_NOT_COVERED;
+    if (!plan_rollout_random(e, slots, tu, p, policy)) return ROLLOUT_NOT_COVERED;
     const RolloutOut ro{actions, out, obs, vec, slots, p.remap, p.sub_lds, p.slack, p.fair};
     auto launch = [&](auto kern) -> int {
         const dim3 gd(p.grid), bd(256 * p.subs);
@@ -431,15 +539,17 @@ int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOu
         return MAPF_OK;
     };
     (void)ring;
-    auto pick = [&](auto tp) -> int {
-        constexpr bool TP = decltype(tp)::value;
+    auto pick = [&](auto pol) -> int {
+        constexpr bool TP = decltype(pol)::value == ROLLOUT_TAPE, DS = decltype(pol)::value == ROLLOUT_DESCENT;
         if (band)
-            return p.subs == 4 ? launch(rollout_random_kernel<true, 4, true, TP>) : launch(rollout_random_kernel<true, 1, true, TP>);
+            return p.subs == 4 ? launch(rollout_random_kernel<true, 4, true, TP, DS>) : launch(rollout_random_kernel<true, 1, true, TP, DS>);
         if (p.subs == 4)
-            return slots ? launch(rollout_random_kernel<true, 4, false, TP>) : launch(rollout_random_kernel<false, 4, false, TP>);
-        return slots ? launch(rollout_random_kernel<true, 1, false, TP>) : launch(rollout_random_kernel<false, 1, false, TP>);
+            return slots ? launch(rollout_random_kernel<true, 4, false, TP, DS>) : launch(rollout_random_kernel<false, 4, false, TP, DS>);
+        return slots ? launch(rollout_random_kernel<true, 1, false, TP, DS>) : launch(rollout_random_kernel<false, 1, false, TP, DS>);
     };
-    return tape ? pick(std::true_type{}) : pick(std::false_type{});
+    return policy == ROLLOUT_DESCENT ? pick(std::integral_constant<int, ROLLOUT_DESCENT>{})
+           : policy == ROLLOUT_TAPE  ? pick(std::integral_constant<int, ROLLOUT_TAPE>{})
+                                     : pick(std::integral_constant<int, ROLLOUT_RANDOM>{});
 }
 
 bool step_observe_fusable(const DevEnv &e) {

@@ -65,6 +65,8 @@ void launch_step(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t
 bool launch_step_pairs(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t flags, int slot,
                        hipStream_t s);   // N <= 8: one lane per agent pair; false if N > 8
 void launch_random_actions(const DevEnv &e, int32_t *actions, hipStream_t s);
+// the descent policy's actions from the state and the tiled BFS maps (keep_bfs; mapf_descent_actions)
+void launch_descent_actions(const DevEnv &e, int32_t *actions, hipStream_t s);
 // humans' next paths (replan_list[parity]) + agent BFS maps (bfs_list[parity]);
 // all = 1: every env's next path and every agent's map, 2: every env's next path,
 // 3 / 4: the step's human paths / BFS maps only
@@ -93,18 +95,22 @@ void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, 
 // of the random draw (the kernels' TAPE instantiations; the plan's text carries ",tape").
 // describe_rollout_random returns false (text "none") where the pair-lane kernel does not take the
 // launch -- with a tape that includes a fusable configuration whose staged rows do not fit its LDS.
+// policy = ROLLOUT_DESCENT (mapf_rollout_descent): the kernels' DESCENT instantiations pick every
+// action from the agents' tiled BFS maps (keep_bfs) and write it to `actions` like the random draw;
+// the plan's text carries ",descent" (and bfsobs=0 in the wide three-wave form).
 constexpr int ROLLOUT_NOT_COVERED = 1;
+constexpr int ROLLOUT_RANDOM = 0, ROLLOUT_TAPE = 1, ROLLOUT_DESCENT = 2;
 bool rollout_random_fusable(const DevEnv &e);
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                           int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, bool tape = false);
-bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, bool tape = false);
+                           int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy = ROLLOUT_RANDOM);
+bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy = ROLLOUT_RANDOM);
 // the same for up to 64 agents / per-env maps / the BFS channel: one wave per env
 // (mapf_rollout_wide.hip); used where the pair-lane rollout does not apply.  Returns MAPF_OK or
 // MAPF_ESTATE (a captured launch found no free argument slot, ArgRing).
 bool rollout_wide_fusable(const DevEnv &e);
 int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                        int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, bool tape = false);
-void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, bool tape = false);
+                        int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy = ROLLOUT_RANDOM);
+void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy = ROLLOUT_RANDOM);
 
 // Device-resident kernel argument blocks.  A persistent kernel whose arguments (DevEnv + its
 // output pointers, ~0.5 KiB) do not fit in the SGPR file kept them live from the kernarg

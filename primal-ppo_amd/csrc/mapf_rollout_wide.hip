@@ -185,7 +185,12 @@ __device__ inline void wide_plain_barrier() {
 // [t] of ro.actions ([T][B][N] whatever `slots` says), each lane loading its own agent's action in
 // the step's first round of loads, beside the human's path cells -- the stepping wave already
 // waits for those there, so the tape adds a load to that round and no wait of its own.
-template <class T, int RW, bool NT, bool TAPE = false>
+// DESCENT: the descent policy (mapf_rollout_descent): each stepping lane reads its agent's five BFS
+// map cells in that same round and picks its action (step_group<.., DESCENT>); ro.actions receives
+// the picks like the random draw's.  The maps the step rebuilds are always searched by the stepping
+// wave itself, never by the observers (bfsobs is ignored: they run up to WIDE_SNAPS steps behind),
+// so every map the step reads was written by the reading wave or before the launch.
+template <class T, int RW, bool NT, bool TAPE = false, bool DESCENT = false>
 __device__ __attribute__((always_inline)) inline void rollout_wide_body(const DevEnv &e, int T_steps, const WideOut &ro) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // XCD-aware env order (as the pair-lane rollout): workgroups are dealt round-robin
@@ -318,7 +323,7 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
     // observation, instead of on the stepper's chain (c4: 0.59 of its 4.63 us per step).  Step
     // t's maps are written after step t - 1's (ctr[3]: steps whose maps are done), so an agent's
     // later map wins; an observer that searched drains its stores before it counts.
-    const bool bfs_obs = ovl && nobs >= 2 && observing && ro.bfsobs;
+    const bool bfs_obs = !DESCENT && ovl && nobs >= 2 && observing && ro.bfsobs;
     // several observers writing the same in-place buffers, in alternation
     const bool inplace_multi = ovl && nobs >= 2 && observing && !ro.slots;
     WSTAMP_BEGIN();
@@ -331,8 +336,8 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
         }
         StepInline inl;
         if (stepper)
-            step_group<WaveGroup, true, true>(e, lact + (TAPE ? (size_t)t : s) * BN, step_out(s), TAPE ? 1u : 3u, 0, b, g,
-                                              &inl, src, rs, have);
+            step_group<WaveGroup, true, true, DESCENT>(e, lact + (TAPE ? (size_t)t : s) * BN, step_out(s),
+                                                       TAPE || DESCENT ? 1u : 3u, 0, b, g, &inl, src, rs, have);
         WSTAMP(0);
         // A: observation t-1 done.  Nothing the observer reads from HBM was written by the step
         // (its outputs and state are not read back), so the stepper does not wait for them.
@@ -433,10 +438,10 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
     WSTAMP_END(b, role);
 }
 
-template <class T, int RW, bool NT, bool TAPE = false>
+template <class T, int RW, bool NT, bool TAPE = false, bool DESCENT = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void rollout_wide_kernel(WIDE_PARAMS) {
     WIDE_BIND
-    rollout_wide_body<T, RW, NT, TAPE>(e, T_steps, ro);
+    rollout_wide_body<T, RW, NT, TAPE, DESCENT>(e, T_steps, ro);
 }
 
 // Three waves per env (c4): the stepper and two observers taking alternate steps.  With one
@@ -444,10 +449,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void r
 // SIMD issuing each step's 31 KiB of stores).  Three waves per SIMD need <= 168 VGPRs:
 // the arguments come through a device pointer (ArgRing), which also frees the ~450 SGPRs the
 // by-value arguments spilled to VGPR lanes (152 VGPRs, 129 SGPR spills, no scratch).
-template <class T, int RW, bool NT, bool TAPE = false>
+template <class T, int RW, bool NT, bool TAPE = false, bool DESCENT = false>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void rollout_wide3_kernel(
     const WideArgs *__restrict__ args, int T_steps) {
-    rollout_wide_body<T, RW, NT, TAPE>(args->e, T_steps, args->ro);
+    rollout_wide_body<T, RW, NT, TAPE, DESCENT>(args->e, T_steps, args->ro);
 }
 
 // The three-wave form is not built for 128-bit rows spread over two lanes (maps wider than 64 cells):
@@ -469,9 +474,10 @@ struct WidePlan {
     int grid = 0, block = 0;
 };
 
-// TAPE: the form of the caller's-actions kernels (their own register counts decide what fits)
-template <class T, int RW, bool TAPE = false>
+// POL (ROLLOUT_*): the form of the tape / descent kernels (their own register counts decide what fits)
+template <class T, int RW, int POL = 0>
 static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
+    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT;
     WidePlan p;
     // persistent waves: every CU holds the same number of workgroups (the LDS request caps
     // them at ceil(B / CUs) per CU, 160 KiB of LDS per CU), or the fuller CUs pace each step
@@ -483,12 +489,12 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     // 446 MB, measured 94 vs 124 us per step); smaller ones keep plain stores (c2, c4;
     // c4 in place, nt sc1: 6.27 -> 7.03 us per step)
     p.nt = tu.wide_nt >= 0 ? tu.wide_nt != 0 : (slots || (size_t)e.B * e.N * e.C * e.F * e.F * 4 > ((size_t)128 << 20));
-    const void *kern = p.nt ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, true, TAPE>)
-                            : reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, false, TAPE>);
+    const void *kern = p.nt ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, true, TAPE, DESCENT>)
+                            : reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, false, TAPE, DESCENT>);
     const void *kern3 = nullptr;
     if constexpr (wide3_form<T, RW>())
-        kern3 = p.nt ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, true, TAPE>)
-                     : reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, false, TAPE>);
+        kern3 = p.nt ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, true, TAPE, DESCENT>)
+                     : reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, false, TAPE, DESCENT>);
     // two waves per env where every env's pair fits at once: the VGPR budget of a SIMD
     // (512 per lane) over the waves it must hold, 4 SIMDs per CU
     const int fit = 512 / ((kernel_vgprs(kern) + 7) & ~7);
@@ -499,7 +505,7 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     r.slots = slots;
     r.xcd_remap = tu.xcd_remap != 0;
     r.prio = tu.wide_prio;
-    r.bfsobs = tu.wide_bfsobs;
+    r.bfsobs = DESCENT ? 0 : tu.wide_bfsobs;      // descent: the stepping wave reads the maps it rebuilt
     r.grid = 0;
     if (!pipe && wide_grid_bytes(e) <= wide_scratch_bytes<T, RW>(e)) r.grid = 2;
     else if (wide_lds_bytes<T, RW>(e, 1) <= (occ > 1 ? cap : (size_t)64 * 1024)) r.grid = 1;
@@ -554,10 +560,11 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     return p;
 }
 
-template <class T, int RW, bool TAPE>
+template <class T, int RW, int POL>
 static int launch_wide_t(const DevEnv &e, int steps, const WideOut &ro, const mapf_tuning &tu, ArgRing &ring,
                          hipStream_t s) {
-    const WidePlan p = plan_wide_t<T, RW, TAPE>(e, ro.slots, tu);
+    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT;
+    const WidePlan p = plan_wide_t<T, RW, POL>(e, ro.slots, tu);
     WideOut r = p.r;
     r.actions = ro.actions;
     r.out = ro.out;
@@ -567,12 +574,12 @@ static int launch_wide_t(const DevEnv &e, int steps, const WideOut &ro, const ma
         if (r.wpe == 3) {
             const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
             if (!args) return MAPF_ESTATE;
-            auto kern3 = p.nt ? rollout_wide3_kernel<T, RW, true, TAPE> : rollout_wide3_kernel<T, RW, false, TAPE>;
+            auto kern3 = p.nt ? rollout_wide3_kernel<T, RW, true, TAPE, DESCENT> : rollout_wide3_kernel<T, RW, false, TAPE, DESCENT>;
             hipLaunchKernelGGL(kern3, dim3(p.grid), dim3(p.block), p.lds, s, args, steps);
             return MAPF_OK;
         }
     }
-    auto kern = p.nt ? rollout_wide_kernel<T, RW, true, TAPE> : rollout_wide_kernel<T, RW, false, TAPE>;
+    auto kern = p.nt ? rollout_wide_kernel<T, RW, true, TAPE, DESCENT> : rollout_wide_kernel<T, RW, false, TAPE, DESCENT>;
 #if MAPF_ARGS_PTR
     const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
     if (!args) return MAPF_ESTATE;
@@ -604,7 +611,7 @@ bool rollout_wide_fusable(const DevEnv &e) {
 }
 
 int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                        int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, bool tape) {
+                        int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy) {
     WideOut ro{};
     ro.actions = actions;
     ro.out = out;
@@ -612,19 +619,26 @@ int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut 
     ro.vec = vec;
     ro.slots = slots;
     return with_row_type(e, [&](auto t, auto rw) {
-        return tape ? launch_wide_t<decltype(t), decltype(rw)::value, true>(e, T, ro, tu, ring, s)
-                    : launch_wide_t<decltype(t), decltype(rw)::value, false>(e, T, ro, tu, ring, s);
+        using R = decltype(t);
+        constexpr int RWV = decltype(rw)::value;
+        return policy == ROLLOUT_DESCENT ? launch_wide_t<R, RWV, ROLLOUT_DESCENT>(e, T, ro, tu, ring, s)
+               : policy == ROLLOUT_TAPE  ? launch_wide_t<R, RWV, ROLLOUT_TAPE>(e, T, ro, tu, ring, s)
+                                         : launch_wide_t<R, RWV, 0>(e, T, ro, tu, ring, s);
     });
 }
 
-void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, bool tape) {
+void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy) {
     with_row_type(e, [&](auto t, auto rw) {
-        const WidePlan p = tape ? plan_wide_t<decltype(t), decltype(rw)::value, true>(e, slots, tu)
-                                : plan_wide_t<decltype(t), decltype(rw)::value, false>(e, slots, tu);
+        using R = decltype(t);
+        constexpr int RWV = decltype(rw)::value;
+        const WidePlan p = policy == ROLLOUT_DESCENT ? plan_wide_t<R, RWV, ROLLOUT_DESCENT>(e, slots, tu)
+                           : policy == ROLLOUT_TAPE  ? plan_wide_t<R, RWV, ROLLOUT_TAPE>(e, slots, tu)
+                                                     : plan_wide_t<R, RWV, 0>(e, slots, tu);
         std::snprintf(buf, n, "%s<%s,%d,%s%s> grid=%d block=%d lds=%zu wpe=%d epw=%d grid_mode=%d overlap=%d slack=%d "
                               "fair=%d prio=%d bfsobs=%d pair=%d remap=%d",
                       p.r.wpe == 3 ? "rollout_wide3_kernel" : "rollout_wide_kernel", row_name<decltype(t)>(),
-                      (int)decltype(rw)::value, p.nt ? "true" : "false", tape ? ",tape" : "", p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
+                      (int)decltype(rw)::value, p.nt ? "true" : "false",
+                      policy == ROLLOUT_DESCENT ? ",descent" : (policy == ROLLOUT_TAPE ? ",tape" : ""), p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
                       p.r.grid, p.r.overlap, p.r.slack, p.r.fair, p.r.prio, p.r.bfsobs, p.r.pair, p.r.xcd_remap);
         return 0;
     });

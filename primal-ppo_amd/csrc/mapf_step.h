@@ -133,7 +133,10 @@ struct StepSrc {
 // lane's element (shadow_goals this env's), held in VGPRs by the caller, and `have` says which
 // outputs exist (bit k = the k-th StepOut field) -- the output bases then take no SGPRs in the
 // step loop, where they were spilled to VGPR lanes and read back at every store.
-template <class Grp, bool REGS = false, bool LANEPTR = false>
+// DESCENT (the wide rollout's descent launches, with REGS): the lane picks its agent's action
+// itself (descent_action() over its tiled BFS map) and stores it to `actions`; `flags` bit 1 is
+// then not looked at.
+template <class Grp, bool REGS = false, bool LANEPTR = false, bool DESCENT = false>
 __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e, int32_t *__restrict__ actions,
                                                                 const StepOut &out, uint32_t flags, int parity, int b,
                                                                 const Grp &g, StepInline *inl, StepSrc src,
@@ -202,6 +205,21 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
     const uint32_t gg = REGS ? rg.gg : (act ? e.goal[ai] : 0u);
     const int la = REGS ? rg.la : (act ? (int)e.last_act[ai] : -1);
     int a = 0;
+    if constexpr (DESCENT) {
+        // The five map cells load in the step's first round, beside the human's path cells (as
+        // the tape's action does).  Visibility: the caller is the wave that rebuilt this map, if
+        // anybody did since the launch began (rollout_wide_body runs bfs_maps on the stepping
+        // wave in descent launches: bfsobs = 0), so the stores and these loads are one wave's
+        // vector memory operations on the same CU, performed in program order -- wavefront
+        // scope, no wait and no cache action needed (the fence emits no instruction; it keeps
+        // the compiler from moving these int16 loads over the search's uint4 stores).  Maps
+        // written before the launch are visible by the launch boundary.
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (act) {
+            a = descent_action(e, e.bfs + ai * bfs_cells(e.H, e.W), pp, clock, i);
+            actions[oi] = a;
+        }
+    } else
     if (flags & 2u) {          // random policy fused in: same stream as random_actions_kernel
         if (act) {
             a = random_action(philox(env_id, P_ACT | ((uint32_t)(i >> 3) << 8), clock, 0u, e.seed), i);

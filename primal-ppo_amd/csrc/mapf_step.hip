@@ -28,6 +28,15 @@ __global__ __launch_bounds__(256) void random_actions_kernel(DevEnv e, int32_t *
     actions[t] = (int32_t)random_action(o, i);
 }
 
+// The descent policy (descent_action(): every agent one step down its own BFS map), one lane per
+// agent: its cell, the env's clock, then its five map cells.
+__global__ __launch_bounds__(256) void descent_actions_kernel(DevEnv e, int32_t *__restrict__ actions) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= e.B * e.N) return;
+    const int b = t / e.N, i = t - b * e.N;
+    actions[t] = (int32_t)descent_action(e, e.bfs + (size_t)t * bfs_cells(e.H, e.W), e.pos[t], e.clock[b], i);
+}
+
 void launch_step(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t flags, int parity, hipStream_t s) {
     if (!e.force_agent_lanes && launch_step_pairs(e, actions, out, flags, parity, s)) return;
     const long threads = (long)e.B * e.G;
@@ -39,6 +48,11 @@ void launch_step(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t
 void launch_random_actions(const DevEnv &e, int32_t *actions, hipStream_t s) {
     const int n = e.B * e.N;
     hipLaunchKernelGGL(random_actions_kernel, dim3((n + 255) / 256), dim3(256), 0, s, e, actions);
+}
+
+void launch_descent_actions(const DevEnv &e, int32_t *actions, hipStream_t s) {
+    const int n = e.B * e.N;
+    hipLaunchKernelGGL(descent_actions_kernel, dim3((n + 255) / 256), dim3(256), 0, s, e, actions);
 }
 
 }  // namespace mapf

@@ -95,6 +95,10 @@ SIGNATURES = {
     "mapf_rollout_plan": (ctypes.c_int, [P, I32, ctypes.c_char_p, I32]),
     "mapf_rollout_actions": (ctypes.c_int, [P, I32, I32, P, ctypes.POINTER(StepOut), P, P, P]),
     "mapf_rollout_actions_plan": (ctypes.c_int, [P, I32, ctypes.c_char_p, I32]),
+    "mapf_rollout_descent": (ctypes.c_int, [P, I32, I32, P, ctypes.POINTER(StepOut), P, P, P]),
+    "mapf_rollout_descent_plan": (ctypes.c_int, [P, I32, ctypes.c_char_p, I32]),
+    "mapf_descent_actions": (ctypes.c_int, [P, P, P]),
+    "mapf_descent_pick": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, I32]),
     "mapf_flush": (ctypes.c_int, [P, P]),
     "mapf_release_captures": (ctypes.c_int, [P]),
     "mapf_random_actions": (ctypes.c_int, [P, P, P]),

@@ -151,6 +151,21 @@ class BatchedMapfGym:
         """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,tape>'."""
         return self.rollout_actions_plan(slots, band_clean).split(" ")[0]
 
+    def rollout_descent_plan(self, slots=False, band_clean=False):
+        """rollout_plan for rollout_descent (mapf_rollout_descent_plan): the same text with ",descent"
+        inside the angle brackets (the wide three-wave form with bfsobs=0), or
+        "descent_actions+step_observe" where the call runs per-step launches."""
+        buf = ctypes.create_string_buffer(512)
+        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
+        kind = _lib.lib().mapf_rollout_descent_plan(self.h, bits, buf, 512)
+        if kind < 0:
+            _lib.check(kind)
+        return buf.value.decode()
+
+    def rollout_descent_kernel_name(self, slots=False, band_clean=False):
+        """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,descent>'."""
+        return self.rollout_descent_plan(slots, band_clean).split(" ")[0]
+
     @staticmethod
     def _make_stepout(out):
         so = _lib.StepOut()
@@ -393,7 +408,28 @@ class BatchedMapfGym:
                                                    _stream(self.device)))
         return out, obs, vec
 
-    def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None, actions_in=None):
+    def rollout_descent(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False):
+        """T x (descent_actions, step_observe) -- every agent one step down its own BFS map, the
+        heuristic baseline (mapf_rollout_descent; needs keep_bfs) -- as ONE launch where
+        rollout_fused (the rollout kernels' descent instantiations, rollout_descent_plan), else T
+        pairs of per-step launches; identical results.  `actions` receives the chosen actions;
+        slots, actions, obs, vec, out, band_clean: as rollout_random.  Returns (out, obs, vec)."""
+        T = int(T)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        k = T if slots else 1
+        actions = self.actions if actions is None else actions
+        _check(actions, torch.int32, k * self.B * self.N, self.device, "actions")
+        so, out, obs, vec = self._rollout_buffers(k, obs, vec, out, slots)
+        if T == 0:          # nothing to play (an empty tensor has no address to hand over)
+            return out, obs, vec
+        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
+        _lib.check(_lib.lib().mapf_rollout_descent(self.h, T, bits, _ptr(actions), ctypes.byref(so), _ptr(obs),
+                                                   _ptr(vec), _stream(self.device)))
+        return out, obs, vec
+
+    def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None, actions_in=None,
+                         policy="random"):
         """rollout_random(T, slots, ...) prepared once: the buffers are checked and the C call's
         arguments built now, on the current stream; the returned callable issues the launch with
         no per-call host work beyond one ctypes call (a 20-step rollout is ~350 us on the GPU, the
@@ -408,7 +444,15 @@ class BatchedMapfGym:
 
         actions_in: an int32 [T, B, N] tape -- the launcher then issues rollout_actions(actions_in,
         slots, ...) instead (`actions` is not used), under the same band rule.  The tape's contents
-        are read at launch time: refill the same tensor between calls to play other actions."""
+        are read at launch time: refill the same tensor between calls to play other actions.
+
+        policy: "random" (the default) or "descent" -- the launcher then issues rollout_descent(T,
+        slots, actions, ...) under the same band rule.  A policy other than "random" and
+        actions_in exclude each other."""
+        if policy not in ("random", "descent"):
+            raise ValueError(f"policy: expected 'random' or 'descent', got {policy!r}")
+        if policy != "random" and actions_in is not None:
+            raise ValueError("policy and actions_in are mutually exclusive")
         k = T if slots else 1
         if actions_in is not None:
             self._check_tape(actions_in, int(T))
@@ -429,7 +473,8 @@ class BatchedMapfGym:
         args = (self.h, int(T), _lib.SLOTS if slots else 0, _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec),
                 _stream(self.device))
         clean = args[:2] + (_lib.SLOTS | _lib.SLOTS_BAND_CLEAN,) + args[3:] if slots else args
-        fn = _lib.lib().mapf_rollout_random if actions_in is None else _lib.lib().mapf_rollout_actions
+        fn = (_lib.lib().mapf_rollout_actions if actions_in is not None else
+              _lib.lib().mapf_rollout_descent if policy == "descent" else _lib.lib().mapf_rollout_random)
         keep = (so, actions, obs, vec, out)
         state = [args]                  # the next call's arguments: `clean` once a call has stored the band
 
@@ -457,6 +502,14 @@ class BatchedMapfGym:
         """Free the argument slots captured rollouts of this env took (mapf_release_captures):
         only after every hipGraph holding one has been destroyed."""
         _lib.check(_lib.lib().mapf_release_captures(self.h))
+
+    def descent_actions(self, out=None):
+        """The descent policy's actions for the current state (mapf_descent_actions; needs
+        keep_bfs): int32 [B, N], every agent one step down its own BFS map, 0 at its goal."""
+        out = self.actions if out is None else out
+        _check(out, torch.int32, self.B * self.N, self.device, "actions")
+        _lib.check(_lib.lib().mapf_descent_actions(self.h, _ptr(out), _stream(self.device)))
+        return out
 
     def random_actions(self, out=None):
         out = self.actions if out is None else out

@@ -152,7 +152,8 @@ METRIC_KEYS = ("episodeReward", "episodeCostReward", "humanCollide", "staticColl
                "shadowGoals", "constraintViolations")
 
 
-def _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human_movement_type, k_predict, fix_choice):
+def _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human_movement_type, k_predict, fix_choice,
+               keep_bfs=False):
     """The BatchedMapfGym of one map-shape group of episodes, reset to their starts (FixedMapfGym)."""
     from .env import BatchedMapfGym
     n = len(infos["agentsSequence"][idx[0]])
@@ -160,7 +161,7 @@ def _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human
     HS = max(len(infos["humanSequence"][i]) for i in idx) if human_movement_type == 1 else 2
     cfg = make_config(len(idx), H, W, num_agents=n, fov=fov, num_channel=num_channel, use_da=int(use_da),
                       use_hp=int(use_hp), human_mode="fixed_path" if human_movement_type == 1 else "looping",
-                      goal_mode="sequence", fix_choice=fix_choice, shared_map=False, keep_bfs=False, max_seq=S,
+                      goal_mode="sequence", fix_choice=fix_choice, shared_map=False, keep_bfs=bool(keep_bfs), max_seq=S,
                       max_human_seq=HS)
     cfg.k_predict = k_predict
     env = BatchedMapfGym(cfg, device=device)
@@ -175,8 +176,21 @@ def _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human
     return env
 
 
+def descent_policy():
+    """The heuristic baseline as a policy(obs, vec, env, t) for evaluate_fixed_episodes: every agent
+    one step down its own BFS map (env.descent_actions, mapf_descent_actions), ignoring the other
+    agents and the human.  The env must keep the agents' BFS maps:
+    evaluate_fixed_episodes(..., keep_bfs=True)."""
+    def policy(obs, vec, env, t):
+        if not env.cfg.keep_bfs:
+            raise RuntimeError("descent_policy needs the agents' BFS maps: evaluate_fixed_episodes(..., keep_bfs=True)")
+        return env.descent_actions()
+    return policy
+
+
 def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, use_da=False, use_hp=False,
-                            human_movement_type=0, max_steps=256, k_predict=5, fix_choice=1, record_actions=False):
+                            human_movement_type=0, max_steps=256, k_predict=5, fix_choice=1, record_actions=False,
+                            keep_bfs=False):
     """evaluate() (evaluate.py:169-269) for every episode at once.
 
     policy(obs [B,N,C,F,F], vec [B,N,4], env, t) -> int32 [B,N] device actions
@@ -187,14 +201,15 @@ def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, us
     Returns {metric: float64 numpy [E]} in episode order (OneEpPerformance fields).
     record_actions: return (metrics, tapes) instead -- tapes[(H, W)] = the policy's actions of that
     map-shape group (not the executed actions_fixed), int32 [max_steps, len(group), N] on the
-    device: what replay_fixed_episodes plays back."""
+    device: what replay_fixed_episodes plays back.
+    keep_bfs: the envs keep every agent's BFS map current (descent_policy reads them)."""
     device = torch.device("cuda") if device is None else torch.device(device)
     E = infos["numEpisodes"]
     res = {k: np.zeros(E, np.float64) for k in METRIC_KEYS}
     tapes = {}
     for (H, W), idx in sorted(_groups_by_shape(infos).items()):
         env = _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human_movement_type, k_predict,
-                         fix_choice)
+                         fix_choice, keep_bfs)
         if record_actions:
             tapes[(H, W)] = torch.empty(max_steps, env.B, env.N, dtype=torch.int32, device=env.device)
         acc = torch.zeros((len(idx), len(METRIC_KEYS)), dtype=torch.float64, device=device)
