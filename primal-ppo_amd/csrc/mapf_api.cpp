@@ -286,41 +286,27 @@ int mapf_rollout_random_fused(const mapf_env *e) {
     if (!e) return 0;
     return rollout_random_fusable(e->d) ? 1 : (rollout_wide_fusable(e->d) ? 2 : 0);
 }
+// the pair-lane kernel where it takes the launch (a tape or descent: where their LDS rows fit too), else
+// the wide kernel, else the per-step form, as rollout_impl
+static int rollout_plan_impl(const mapf_env *e, int policy, int32_t slots, char *buf, int32_t n) {
+    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
+    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
+    if (rollout_random_fusable(e->d) && describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n, policy)) return 1;
+    if (rollout_wide_fusable(e->d)) {
+        describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n, policy);
+        return 2;
+    }
+    std::snprintf(buf, (size_t)n, policy == ROLLOUT_DESCENT ? "descent_actions+step_observe" : "step_observe");
+    return 0;
+}
 int mapf_rollout_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
-    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
-    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
-    const int kind = mapf_rollout_random_fused(e);
-    if (kind == 1) describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n);
-    else if (kind == 2) describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n);
-    else std::snprintf(buf, (size_t)n, "step_observe");
-    return kind;
+    return rollout_plan_impl(e, ROLLOUT_RANDOM, slots, buf, n);
 }
-
 int mapf_rollout_actions_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
-    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
-    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
-    // the pair-lane kernel where its staged tape rows fit the LDS, else the wide kernel, as the launch
-    if (rollout_random_fusable(e->d) && describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n, ROLLOUT_TAPE)) return 1;
-    if (rollout_wide_fusable(e->d)) {
-        describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n, ROLLOUT_TAPE);
-        return 2;
-    }
-    std::snprintf(buf, (size_t)n, "step_observe");
-    return 0;
+    return rollout_plan_impl(e, ROLLOUT_TAPE, slots, buf, n);
 }
-
 int mapf_rollout_descent_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
-    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
-    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
-    // the pair-lane kernel where its action rows fit the LDS, else the wide kernel, as the launch
-    if (rollout_random_fusable(e->d) && describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n, ROLLOUT_DESCENT))
-        return 1;
-    if (rollout_wide_fusable(e->d)) {
-        describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n, ROLLOUT_DESCENT);
-        return 2;
-    }
-    std::snprintf(buf, (size_t)n, "descent_actions+step_observe");
-    return 0;
+    return rollout_plan_impl(e, ROLLOUT_DESCENT, slots, buf, n);
 }
 
 int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent) {
@@ -510,17 +496,23 @@ int mapf_reset_generated(mapf_env *e, const mapf_mapgen_spec *spec, int8_t *maps
     return reset_searches(e, s);       // asynchronous: nothing on the host to keep alive
 }
 
-static int step_impl(mapf_env *e, int32_t *actions, const mapf_step_out *out, uint32_t flags, void *stream) {
-    if (!e || !actions) return fail(MAPF_EINVAL, "null argument");
-    if (!e->ready) return fail(MAPF_ESTATE, "mapf_step before mapf_reset");
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
+// the device pointers of a mapf_step_out (NULL: none)
+static StepOut step_out_of(const mapf_step_out *out) {
     StepOut o{};
     if (out) {
         o.status = out->status; o.reward = out->reward; o.shadow_goals = out->shadow_goals; o.cost = out->cost;
         o.train_valid = out->train_valid; o.actions_fixed = out->actions_fixed; o.goals_reached = out->goals_reached;
         o.constraints = out->constraints; o.reward_total = out->reward_total;
     }
+    return o;
+}
+
+static int step_impl(mapf_env *e, int32_t *actions, const mapf_step_out *out, uint32_t flags, void *stream) {
+    if (!e || !actions) return fail(MAPF_EINVAL, "null argument");
+    if (!e->ready) return fail(MAPF_ESTATE, "mapf_step before mapf_reset");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    const StepOut o = step_out_of(out);
     if (e->pending >= 0) {             // previous step's search work was not observed-through
         if (int rc = join_deferred(e, s, true)) return rc;
         launch_search(e->d, e->pending, 0, s);
@@ -638,12 +630,7 @@ static int step_observe_impl(mapf_env *e, int32_t *actions, const mapf_step_out 
     hipStream_t s = (hipStream_t)stream;
     if (int rc = join_deferred(e, s, true)) return rc;
     ++e->nsteps;
-    StepOut o{};
-    if (out) {
-        o.status = out->status; o.reward = out->reward; o.shadow_goals = out->shadow_goals; o.cost = out->cost;
-        o.train_valid = out->train_valid; o.actions_fixed = out->actions_fixed; o.goals_reached = out->goals_reached;
-        o.constraints = out->constraints; o.reward_total = out->reward_total;
-    }
+    const StepOut o = step_out_of(out);
     const bool host = observe_hosts_search(e->d);
     int nsearch = 0, sslot = 0;
     if (e->pending >= 0) {
@@ -672,80 +659,45 @@ int mapf_step_observe_random(mapf_env *e, int32_t *actions_out, const mapf_step_
     return step_observe_impl(e, actions_out, out, 2u, obs, vec, stream);
 }
 
-int mapf_rollout_random(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
-                        float *obs, float *vec, void *stream) {
-    if (!e || !actions_out || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
-    if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
-    if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN)) return fail(MAPF_EINVAL, "slots: unknown bits");
-    if (!e->ready) return fail(MAPF_ESTATE, "mapf_rollout_random before mapf_reset");
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    StepOut o{};
-    if (out) {
-        o.status = out->status; o.reward = out->reward; o.shadow_goals = out->shadow_goals; o.cost = out->cost;
-        o.train_valid = out->train_valid; o.actions_fixed = out->actions_fixed; o.goals_reached = out->goals_reached;
-        o.constraints = out->constraints; o.reward_total = out->reward_total;
-    }
-    if (T == 0) return MAPF_OK;
-    if (rollout_random_fused(e)) {
-        if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
-        int rc = launch_rollout_random(e->d, T, actions_out, o, obs, vec, slots, e->tune, e->args, s);
-        if (rc == ROLLOUT_NOT_COVERED)      // the wide kernels store everything (MAPF_SLOTS_BAND_CLEAN ignored)
-            rc = launch_rollout_wide(e->d, T, actions_out, o, obs, vec, slots & 1, e->tune, e->args, s);
-        if (rc != MAPF_OK)
-            return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
-                                     "(16 per handle, ArgRing; mapf_release_captures frees them)");
-        HIPCHK(hipGetLastError());
-        return MAPF_OK;
-    }
-    // not covered by the one-launch kernel: T step_observe launches, same results
-    const size_t BN = (size_t)e->d.B * e->d.N, obs_t = BN * e->d.C * e->d.F * e->d.F;
-    for (int32_t t = 0; t < T; ++t) {
-        const size_t k = (slots & 1) ? (size_t)t : 0;
-        mapf_step_out ot{};
-        if (out) {
-            auto adv = [&](auto *p, size_t n) { return p ? p + k * n : p; };
-            ot.status = adv(out->status, BN); ot.reward = adv(out->reward, BN);
-            ot.shadow_goals = adv(out->shadow_goals, (size_t)e->d.B); ot.cost = adv(out->cost, BN);
-            ot.train_valid = adv(out->train_valid, BN * 5); ot.actions_fixed = adv(out->actions_fixed, BN);
-            ot.goals_reached = adv(out->goals_reached, BN); ot.constraints = adv(out->constraints, BN);
-            ot.reward_total = adv(out->reward_total, BN);
-        }
-        if (int rc = step_observe_impl(e, actions_out + k * BN, out ? &ot : nullptr, 2u, obs + k * obs_t,
-                                       vec + k * BN * 4, stream))
-            return rc;
-    }
-    return MAPF_OK;
+// slot k of rollout output buffers (NULL members stay NULL)
+static mapf_step_out step_out_slot(const mapf_step_out &out, size_t k, const DevEnv &d) {
+    const size_t BN = (size_t)d.B * d.N;
+    auto adv = [&](auto *p, size_t n) { return p ? p + k * n : p; };
+    mapf_step_out ot{};
+    ot.status = adv(out.status, BN); ot.reward = adv(out.reward, BN);
+    ot.shadow_goals = adv(out.shadow_goals, (size_t)d.B); ot.cost = adv(out.cost, BN);
+    ot.train_valid = adv(out.train_valid, BN * 5); ot.actions_fixed = adv(out.actions_fixed, BN);
+    ot.goals_reached = adv(out.goals_reached, BN); ot.constraints = adv(out.constraints, BN);
+    ot.reward_total = adv(out.reward_total, BN);
+    return ot;
 }
 
-int mapf_rollout_actions(mapf_env *e, int32_t T, int32_t slots, const int32_t *actions_in, const mapf_step_out *out,
-                         float *obs, float *vec, void *stream) {
-    if (!e || !actions_in || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
+// mapf_rollout_random / _actions / _descent (`name`, for the error text).  policy (ROLLOUT_*) says
+// where the actions come from; `actions` is the caller's tape with ROLLOUT_TAPE (read only), else out.
+static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, int32_t slots, int32_t *actions,
+                        const mapf_step_out *out, float *obs, float *vec, void *stream) {
+    if (!e || !actions || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
     if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
     if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN)) return fail(MAPF_EINVAL, "slots: unknown bits");
-    if (!e->ready) return fail(MAPF_ESTATE, "mapf_rollout_actions before mapf_reset");
+    if (policy == ROLLOUT_DESCENT && !e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
+    if (!e->ready) return fail(MAPF_ESTATE, std::string(name) + " before mapf_reset");
     const size_t BN = (size_t)e->d.B * e->d.N, obs_t = BN * e->d.C * e->d.F * e->d.F;
-    if (out && out->actions_fixed && T > 0) {      // the tape is read while actions_fixed is written
-        const uintptr_t a0 = (uintptr_t)actions_in, a1 = a0 + (size_t)T * BN * 4;
+    if (policy == ROLLOUT_TAPE && out && out->actions_fixed && T > 0) {      // the tape is read while actions_fixed is written
+        const uintptr_t a0 = (uintptr_t)actions, a1 = a0 + (size_t)T * BN * 4;
         const uintptr_t f0 = (uintptr_t)out->actions_fixed, f1 = f0 + ((slots & 1) ? (size_t)T : 1) * BN * 4;
         if (a0 < f1 && f0 < a1) return fail(MAPF_EINVAL, "actions_in overlaps out->actions_fixed");
     }
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    StepOut o{};
-    if (out) {
-        o.status = out->status; o.reward = out->reward; o.shadow_goals = out->shadow_goals; o.cost = out->cost;
-        o.train_valid = out->train_valid; o.actions_fixed = out->actions_fixed; o.goals_reached = out->goals_reached;
-        o.constraints = out->constraints; o.reward_total = out->reward_total;
-    }
     if (T == 0) return MAPF_OK;
-    int32_t *tape = const_cast<int32_t *>(actions_in);      // the TAPE kernels only read it
     if (rollout_random_fused(e)) {
         if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
-        // the wide kernel takes what the pair-lane one does not (a tape whose staged rows pass its LDS included)
-        int rc = launch_rollout_random(e->d, T, tape, o, obs, vec, slots, e->tune, e->args, s, ROLLOUT_TAPE);
+        // the wide kernels take what the pair-lane one does not (a tape or descent whose LDS rows pass its
+        // LDS included); they store everything (MAPF_SLOTS_BAND_CLEAN ignored)
+        const StepOut o = step_out_of(out);
+        int rc = launch_rollout_random(e->d, T, actions, o, obs, vec, slots, e->tune, e->args, s, policy);
         if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
-            rc = launch_rollout_wide(e->d, T, tape, o, obs, vec, slots & 1, e->tune, e->args, s, ROLLOUT_TAPE);
+            rc = launch_rollout_wide(e->d, T, actions, o, obs, vec, slots & 1, e->tune, e->args, s, policy);
         if (rc == MAPF_ESTATE)
             return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
                                      "(16 per handle, ArgRing; mapf_release_captures frees them)");
@@ -753,24 +705,37 @@ int mapf_rollout_actions(mapf_env *e, int32_t T, int32_t slots, const int32_t *a
             HIPCHK(hipGetLastError());
             return MAPF_OK;
         }
+        // Still ROLLOUT_NOT_COVERED: pair-lane fusable, but the tape's or descent's rows pass its LDS and
+        // the wide kernel does not apply.  Never a random launch: its pair-lane kernel declines exactly
+        // where !rollout_random_fusable, and rollout_random_fused then means the wide one applies.
     }
-    // not covered by a one-launch kernel: T step_observe launches, same results
+    // not covered by a one-launch kernel: T step_observe launches (descent: each after its
+    // descent_actions), same results.  The tape plays row t whatever `slots` says.
     for (int32_t t = 0; t < T; ++t) {
         const size_t k = (slots & 1) ? (size_t)t : 0;
         mapf_step_out ot{};
-        if (out) {
-            auto adv = [&](auto *p, size_t n) { return p ? p + k * n : p; };
-            ot.status = adv(out->status, BN); ot.reward = adv(out->reward, BN);
-            ot.shadow_goals = adv(out->shadow_goals, (size_t)e->d.B); ot.cost = adv(out->cost, BN);
-            ot.train_valid = adv(out->train_valid, BN * 5); ot.actions_fixed = adv(out->actions_fixed, BN);
-            ot.goals_reached = adv(out->goals_reached, BN); ot.constraints = adv(out->constraints, BN);
-            ot.reward_total = adv(out->reward_total, BN);
+        if (out) ot = step_out_slot(*out, k, e->d);
+        int32_t *act = actions + (policy == ROLLOUT_TAPE ? (size_t)t : k) * BN;
+        if (policy == ROLLOUT_DESCENT) {
+            if (int rc = mapf_descent_actions(e, act, stream)) return rc;
         }
-        if (int rc = step_observe_impl(e, tape + (size_t)t * BN, out ? &ot : nullptr, 0u, obs + k * obs_t,
+        if (int rc = step_observe_impl(e, act, out ? &ot : nullptr, policy == ROLLOUT_RANDOM ? 2u : 0u, obs + k * obs_t,
                                        vec + k * BN * 4, stream))
             return rc;
     }
     return MAPF_OK;
+}
+
+int mapf_rollout_random(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
+                        float *obs, float *vec, void *stream) {
+    return rollout_impl(e, ROLLOUT_RANDOM, "mapf_rollout_random", T, slots, actions_out, out, obs, vec, stream);
+}
+
+int mapf_rollout_actions(mapf_env *e, int32_t T, int32_t slots, const int32_t *actions_in, const mapf_step_out *out,
+                         float *obs, float *vec, void *stream) {
+    // the TAPE kernels only read it
+    return rollout_impl(e, ROLLOUT_TAPE, "mapf_rollout_actions", T, slots, const_cast<int32_t *>(actions_in), out, obs,
+                        vec, stream);
 }
 
 int mapf_descent_actions(mapf_env *e, int32_t *actions, void *stream) {
@@ -786,52 +751,7 @@ int mapf_descent_actions(mapf_env *e, int32_t *actions, void *stream) {
 
 int mapf_rollout_descent(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
                          float *obs, float *vec, void *stream) {
-    if (!e || !actions_out || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
-    if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
-    if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN)) return fail(MAPF_EINVAL, "slots: unknown bits");
-    if (!e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
-    if (!e->ready) return fail(MAPF_ESTATE, "mapf_rollout_descent before mapf_reset");
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    StepOut o{};
-    if (out) {
-        o.status = out->status; o.reward = out->reward; o.shadow_goals = out->shadow_goals; o.cost = out->cost;
-        o.train_valid = out->train_valid; o.actions_fixed = out->actions_fixed; o.goals_reached = out->goals_reached;
-        o.constraints = out->constraints; o.reward_total = out->reward_total;
-    }
-    if (T == 0) return MAPF_OK;
-    if (rollout_random_fused(e)) {
-        if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
-        int rc = launch_rollout_random(e->d, T, actions_out, o, obs, vec, slots, e->tune, e->args, s, ROLLOUT_DESCENT);
-        if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
-            rc = launch_rollout_wide(e->d, T, actions_out, o, obs, vec, slots & 1, e->tune, e->args, s, ROLLOUT_DESCENT);
-        if (rc == MAPF_ESTATE)
-            return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
-                                     "(16 per handle, ArgRing; mapf_release_captures frees them)");
-        if (rc == MAPF_OK) {
-            HIPCHK(hipGetLastError());
-            return MAPF_OK;
-        }
-    }
-    // not covered by a one-launch kernel: T x (descent_actions, step_observe), same results
-    const size_t BN = (size_t)e->d.B * e->d.N, obs_t = BN * e->d.C * e->d.F * e->d.F;
-    for (int32_t t = 0; t < T; ++t) {
-        const size_t k = (slots & 1) ? (size_t)t : 0;
-        mapf_step_out ot{};
-        if (out) {
-            auto adv = [&](auto *p, size_t n) { return p ? p + k * n : p; };
-            ot.status = adv(out->status, BN); ot.reward = adv(out->reward, BN);
-            ot.shadow_goals = adv(out->shadow_goals, (size_t)e->d.B); ot.cost = adv(out->cost, BN);
-            ot.train_valid = adv(out->train_valid, BN * 5); ot.actions_fixed = adv(out->actions_fixed, BN);
-            ot.goals_reached = adv(out->goals_reached, BN); ot.constraints = adv(out->constraints, BN);
-            ot.reward_total = adv(out->reward_total, BN);
-        }
-        if (int rc = mapf_descent_actions(e, actions_out + k * BN, stream)) return rc;
-        if (int rc = step_observe_impl(e, actions_out + k * BN, out ? &ot : nullptr, 0u, obs + k * obs_t,
-                                       vec + k * BN * 4, stream))
-            return rc;
-    }
-    return MAPF_OK;
+    return rollout_impl(e, ROLLOUT_DESCENT, "mapf_rollout_descent", T, slots, actions_out, out, obs, vec, stream);
 }
 
 int mapf_release_captures(mapf_env *e) {

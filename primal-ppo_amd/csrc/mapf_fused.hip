@@ -24,7 +24,6 @@
 // the BFS channel, which is not fused).  The step of this launch reads none of
 // what they write (the path buffer it walks is the other one).
 #include <cstdio>
-#include <cstring>
 #include <type_traits>
 
 #include "mapf_step_pairs.h"
@@ -108,19 +107,13 @@ __global__ __launch_bounds__(256) void step_observe_kernel(DevEnv e, int32_t *__
 // next path.  Same items, same results as the work-list searches.
 // map: the env's padded obstacle rows in the wave's LDS; rs: the resident state,
 // whose path lengths take the searched path's.
-// PLANES (the descent experiment, MAPF_DESCENT_FETCH 1): the env's [N][2][H] LDS bit planes, kept current
-template <bool PLANES = false>
 __device__ inline void step_pairs_search_inline(const DevEnv &e, const PairsDeferred &d, char *lds,
-                                                const uint32_t *map, EnvRegs &rs, uint32_t *planes = nullptr) {
+                                                const uint32_t *map, EnvRegs &rs) {
     for (uint64_t m = d.bmask; m; m &= m - 1ull) {
         const int l = __builtin_ctzll(m);
         const uint32_t ai = (uint32_t)__builtin_amdgcn_readlane((int)d.bitem, l);
         const uint32_t g = (uint32_t)__builtin_amdgcn_readlane((int)d.bgoal, l);
-        if constexpr (PLANES)
-            srch::search_one<uint32_t, 1, true>(e, false, (int)(ai / (uint32_t)e.N), ai, g, NO_CELL, 0, lds, map,
-                                                planes + (size_t)(ai % (uint32_t)e.N) * 2 * e.H);
-        else
-            srch::search_one<uint32_t, 1>(e, false, (int)(ai / (uint32_t)e.N), ai, g, NO_CELL, 0, lds, map);
+        srch::search_one<uint32_t, 1>(e, false, (int)(ai / (uint32_t)e.N), ai, g, NO_CELL, 0, lds, map);
     }
     if (d.rmask) {
         const int l = __builtin_ctzll(d.rmask);
@@ -168,28 +161,11 @@ __host__ __device__ inline bool rollout_fusable(const DevEnv &e) {
 // LDS of a rollout workgroup: observation layout | nibble table | 4 search scratch | 4 path copies
 __host__ __device__ inline size_t rollout_obs_lds(const DevEnv &e) { return ((obs_lds_bytes(e, 4, true) + 15) & ~(size_t)15) + 256; }
 // TAPE: + 4 waves x TAPE_K staged rows (8 slots each, N <= 8) of the action tape (below)
-constexpr int TAPE_K = 32;
-// How a TAPE wave fetches its rows.  0 (shipped): TAPE_K rows staged in LDS at a time.  Experiment
-// builds (make variant VFLAGS=-DMAPF_TAPE_FETCH=n; DESIGN.md 9f has their numbers): 1 the step's
-// plain per-step vector load, 2 step t + 1's row loaded before step t's observation stores and
-// handed to the step through LDS.
-#ifndef MAPF_TAPE_FETCH
-#define MAPF_TAPE_FETCH 0
-#endif
 // DESCENT: + 4 waves x one row of 8 picked actions (the hand-over to the step's pair lanes)
-// How a DESCENT wave fetches its agents' five map cells.  0 (shipped): a plain per-step load from the
-// tiled maps.  Experiment build (make variant VFLAGS=-DMAPF_DESCENT_FETCH=1): the env's
-// maps mod 4 as two bit planes per agent in the wave's LDS ([8][2][H] words), filled from the tiled
-// maps before the loop and rewritten by the inline search, so the loop stays load-free.
-#ifndef MAPF_DESCENT_FETCH
-#define MAPF_DESCENT_FETCH 0
-#endif
-__host__ __device__ inline size_t rollout_descent_lds(const DevEnv &e) {
-    return 4 * (size_t)8 * 4 + (MAPF_DESCENT_FETCH == 1 ? 4 * (size_t)8 * 2 * e.H * 4 : 0);
-}
-__host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy = ROLLOUT_RANDOM) {
+constexpr int TAPE_K = 32;
+__host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy) {
     return rollout_obs_lds(e) + 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W) + 4 * (size_t)e.Lmax * 4 +
-           (policy == ROLLOUT_TAPE ? 4 * (size_t)TAPE_K * 8 * 4 : (policy == ROLLOUT_DESCENT ? rollout_descent_lds(e) : 0));
+           (policy == ROLLOUT_TAPE ? 4 * (size_t)TAPE_K * 8 * 4 : (policy == ROLLOUT_DESCENT ? 4 * (size_t)8 * 4 : 0));
 }
 
 // NT: nontemporal observation stores -- for slot buffers (fresh HBM lines every step,
@@ -210,7 +186,7 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy 
 // rs.pi, picks (descent_action) and hands the action to the pair lanes through the wave's LDS row,
 // as the tape does (LDSACT); ro.actions receives the picks like the random draw's.  The five loads
 // are a plain per-step vector load: waited for behind the wave's observation stores.
-template <bool NT, int SUBS, bool BAND = false, bool TAPE = false, bool DESCENT = false>
+template <bool NT, int SUBS, bool BAND, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_kernel(
 #if MAPF_ARGS_PTR      // experiment build: arguments through a device pointer (mapf_rollout_wide.hip)
     const RolloutArgs *__restrict__ args, int T) {
@@ -221,6 +197,7 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
 #endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int E = 4;                     // envs per workgroup, one per wave
+    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT;
     // XCD-aware env order: workgroups are dealt round-robin over the 8 XCDs, so workgroup w
     // takes env block (w % 8) * (grid / 8) + w / 8 -- each XCD owns one contiguous range of
     // envs, and the output lines that several envs share (status: 16 envs per 128-B line)
@@ -247,37 +224,13 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
     const size_t swl = srch::wave_lds<uint32_t, 1>(e.H, e.W);
     char *slds = qsm + rollout_obs_lds(e) + (size_t)le * swl;
     uint32_t *lpath = reinterpret_cast<uint32_t *>(qsm + rollout_obs_lds(e) + 4 * swl) + (size_t)le * e.Lmax;
-    // TAPE: this wave's TAPE_K staged rows, after the quarter's path copies
+    // TAPE: this wave's TAPE_K staged rows, after the quarter's path copies; DESCENT: its one row of picks
     int32_t *trow = nullptr;
-    if constexpr (TAPE) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e)) + (size_t)le * TAPE_K * 8;
-    if constexpr (DESCENT) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e)) + (size_t)le * 8;
+    if constexpr (TAPE) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e, ROLLOUT_RANDOM)) + (size_t)le * TAPE_K * 8;
+    if constexpr (DESCENT) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e, ROLLOUT_RANDOM)) + (size_t)le * 8;
     const uint32_t mreg = obs_map_word(e, b0, nenv, (int)(threadIdx.x & 63));
     EnvRegs rs{};
     if (le < nenv) env_regs_load<8>(e, b0 + le, rs, lpath);
-    uint32_t *wpl = nullptr;      // MAPF_DESCENT_FETCH 1: this wave's [N][2][H] bit planes, after the quarter's action rows
-#if MAPF_DESCENT_FETCH == 1
-    if constexpr (DESCENT) {
-        wpl = reinterpret_cast<uint32_t *>(qsm + rollout_lds_bytes(e)) + 4 * 8 + (size_t)le * 8 * 2 * e.H;
-        if (le < nenv) {          // lane = row: the maps mod 4 out of the tiled maps, once per launch
-            const int row = (int)(threadIdx.x & 63);
-            for (int i = 0; i < e.N; ++i) {
-                const int16_t *Dm = e.bfs + ((size_t)(b0 + le) * e.N + i) * bfs_cells(e.H, e.W);
-                uint32_t d0 = 0, d1 = 0;
-                if (row < e.H)
-                    for (int c = 0; c < e.W; ++c) {
-                        const int v = (int)Dm[bfs_at(e.W, row, c)];
-                        if (v >= 0) { d0 |= (uint32_t)(v & 1) << c; d1 |= (uint32_t)((v >> 1) & 1) << c; }
-                    }
-                if (row < e.H) {
-                    as_lds(wpl)[(size_t)(2 * i) * e.H + row] = d0;
-                    as_lds(wpl)[(size_t)(2 * i + 1) * e.H + row] = d1;
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-#endif
     // every prologue load has landed before the loop: otherwise the compiler keeps a
     // register's load "pending" at the loop header and waits vmcnt(0) -- i.e. behind
     // all of the previous step's stores -- where the loop uses it
@@ -294,12 +247,6 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
             band_mask = obs_band_skip_mask(e, MAPF_BAND_UNIT, (size_t)(ro.obs + (size_t)(b0 + le) * e.N * e.C * e.F * e.F),
                                            (int)(threadIdx.x & 63));
     }
-#if MAPF_TAPE_FETCH == 2
-    int32_t tnext = 0;
-    if (TAPE && le < nenv && (int)(threadIdx.x & 63) < e.N && T > 0)
-        tnext = ro.actions[(size_t)(b0 + le) * e.N + (threadIdx.x & 63)];
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
     RSTAMP_BEGIN();
     const bool pacing = SUBS > 1 && ro.slack >= 0 && le < nenv;
     const bool fair = SUBS > 1 && ro.fair > 0 && le < nenv;
@@ -313,13 +260,6 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
         }
         const size_t BN = (size_t)E.B * E.N;
         const size_t s = R.slots ? (size_t)t : 0;
-#if MAPF_TAPE_FETCH == 2
-        if constexpr (TAPE) {
-            if (le < nenv && (int)(threadIdx.x & 63) < 8) as_lds(trow)[threadIdx.x & 63] = tnext;
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-#elif MAPF_TAPE_FETCH == 0
         if constexpr (TAPE) {
             if ((t & (TAPE_K - 1)) == 0) {
                 if (le < nenv) {        // rows [t, t + TAPE_K) of this env, inside [T][B][N]
@@ -341,7 +281,6 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
                 __builtin_amdgcn_wave_barrier();
             }
         }
-#endif
         if constexpr (DESCENT) {
             // The maps read here were written before the launch (visible by the launch boundary)
             // or by this very wave, in step_pairs_search_inline of an earlier step: one wave's
@@ -349,37 +288,6 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
             // the fence emits nothing and only keeps the compiler from moving these int16 loads
             // over the search's uint4 stores; the loads' own vmcnt wait is the only wait.
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#if MAPF_DESCENT_FETCH == 1
-            if (le < nenv) {
-                // The grid is bipartite: a free neighbour of a reachable cell lies one level up or
-                // down, so it is in S iff (D[n] - own) & 3 == 3; obstacles and cells past the edge
-                // (planes 0) are told apart by the register map.  own == 0 is pos == goal; an
-                // unreachable own cell has unreachable neighbours (all planes 0: S empty).
-                int lane = (int)(threadIdx.x & 63);
-                asm volatile("" : "+v"(lane));
-                const int i = lane >> 3, r = prow(rs.pi), c = pcol(rs.pi);
-                const auto pl = as_lds(wpl) + (size_t)min(i, E.N - 1) * 2 * E.H;
-                auto val = [&](int rr, int cc) {
-                    rr = min(max(rr, 0), E.H - 1);
-                    cc = min(max(cc, 0), E.W - 1);
-                    return ((pl[rr] >> cc) & 1u) | (((pl[E.H + rr] >> cc) & 1u) << 1);
-                };
-                const RegMap rmap{mreg, true};
-                const uint32_t own = val(r, c);
-                uint32_t mask = 0;
-#pragma unroll
-                for (int k = 1; k < NA; ++k) {
-                    const bool obst = rmap.obstacle(E, nullptr, r + dr(k), c + dc(k));     // every lane permutes
-                    mask |= (uint32_t)(!obst && ((val(r + dr(k), c + dc(k)) - own) & 3u) == 3u) << k;
-                }
-                if ((lane & 7) == 0 && i < E.N) {
-                    const size_t ai = (size_t)(b0 + le) * E.N + i;
-                    const int a = rs.pi == rs.gi ? 0 : descent_pick(mask, rs.clock, i);
-                    as_lds(trow)[i] = a;
-                    R.actions[s * BN + ai] = a;
-                }
-            }
-#else
             if (le < nenv) {
                 int lane = (int)(threadIdx.x & 63);
                 asm volatile("" : "+v"(lane));          // addresses stay out of the loop's invariants (as the tape's)
@@ -391,7 +299,6 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
                     R.actions[s * BN + ai] = a;
                 }
             }
-#endif
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
@@ -406,22 +313,9 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
         if (o.constraints) o.constraints += s * BN;
         if (o.reward_total) o.reward_total += s * BN;
         PairsDeferred dfr;
-#if MAPF_TAPE_FETCH == 1
-        if constexpr (DESCENT)
-            step_pairs_env<8, true, true, true, true>(E, trow, o, 1u, 0, blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
-        else
-            step_pairs_env<8, true, true, true>(E, R.actions + (TAPE ? (size_t)t : s) * BN, o, TAPE ? 1u : 3u, 0,
-                                                blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
-#else
-        constexpr int TROW = MAPF_TAPE_FETCH == 2 ? 0 : TAPE_K - 1;      // the staged row of step t
         step_pairs_env<8, true, true, true, TAPE || DESCENT>(
-            E, TAPE ? trow + (size_t)(t & TROW) * 8 : (DESCENT ? trow : R.actions + s * BN), o, TAPE || DESCENT ? 1u : 3u, 0,
+            E, TAPE ? trow + (size_t)(t & (TAPE_K - 1)) * 8 : (DESCENT ? trow : R.actions + s * BN), o, TAPE || DESCENT ? 1u : 3u, 0,
             blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
-#endif
-#if MAPF_TAPE_FETCH == 2
-        if (TAPE && le < nenv && (int)(threadIdx.x & 63) < E.N && t + 1 < T)
-            tnext = R.actions[((size_t)(t + 1) * E.B + (size_t)(b0 + le)) * E.N + (threadIdx.x & 63)];
-#endif
         if (le < nenv) {
             const ObsGroup g = obs_wave_init(E, L, le, mreg);
             if (BAND && band_moves)
@@ -429,7 +323,7 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
                                                (size_t)(R.obs + (s * BN + (size_t)(b0 + le) * E.N) * E.C * E.F * E.F),
                                                (int)(threadIdx.x & 63));
             obs_emit<false, NT, BAND>(E, L, R.obs + s * BN * E.C * E.F * E.F, R.vec + s * BN * 4, g, b0, false, band_mask);
-            step_pairs_search_inline<DESCENT && MAPF_DESCENT_FETCH == 1>(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs, wpl);
+            step_pairs_search_inline(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs);
             if (pacing || fair) publish_count(prog + gw, (uint32_t)(t + 1));
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -439,7 +333,7 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
     if (le < nenv) RSTAMP_END(b0 + le);
 }
 
-bool rollout_random_fusable(const DevEnv &e) { return rollout_fusable(e) && rollout_lds_bytes(e) <= 64 * 1024; }
+bool rollout_random_fusable(const DevEnv &e) { return rollout_fusable(e) && rollout_lds_bytes(e, ROLLOUT_RANDOM) <= 64 * 1024; }
 
 // The pair-lane rollout's launch form for this handle's tuning (mapf.h: mapf_tuning).
 struct RolloutPlan {
@@ -452,7 +346,7 @@ struct RolloutPlan {
 
 // policy ROLLOUT_TAPE / ROLLOUT_DESCENT: the caller's-actions and descent forms (their LDS rows; past
 // 64 KiB the wide kernel takes over)
-static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p, int policy = ROLLOUT_RANDOM) {
+static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p, int policy) {
     if (!rollout_random_fusable(e) || rollout_lds_bytes(e, policy) > 64 * 1024) return false;
     const int grid = (e.B + 3) / 4;
     // Persistent waves: every CU should hold the same number of workgroups, or the
@@ -479,7 +373,7 @@ static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &t
     const bool want_group = occ == 4 && grid % 4 == 0 && (tu.roll_group < 0 ? slots != 0 || fair > 0 : tu.roll_group != 0);
     const bool group = want_group && 4 * sub + 64 <= (size_t)device_max_group_lds();
     p.tape_ungrouped = policy != ROLLOUT_RANDOM && want_group && !group &&
-                       4 * ((rollout_lds_bytes(e) + 15) & ~(size_t)15) + 64 <= (size_t)device_max_group_lds();
+                       4 * ((rollout_lds_bytes(e, ROLLOUT_RANDOM) + 15) & ~(size_t)15) + 64 <= (size_t)device_max_group_lds();
     p.subs = group ? 4 : 1;
     p.grid = grid / p.subs;
     p.lds = group ? (size_t)device_max_group_lds() : lds;   // grouped: the whole CU
@@ -497,7 +391,6 @@ static bool rollout_band_form(const DevEnv &e, int slots) {
 }
 
 bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy) {
-    const bool tape = policy == ROLLOUT_TAPE, descent = policy == ROLLOUT_DESCENT;
     const bool band = rollout_band_form(e, slots);
     slots &= 1;
     RolloutPlan p;
@@ -505,17 +398,17 @@ bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, 
         std::snprintf(buf, n, "none");
         return false;
     }
-    char form[32] = "";
-    if (band) std::snprintf(form, sizeof form, ",band%d", MAPF_BAND_UNIT);
-    if (tape) std::snprintf(form + std::strlen(form), sizeof form - std::strlen(form), ",tape");
-    if (descent) std::snprintf(form + std::strlen(form), sizeof form - std::strlen(form), ",descent");
-    const int k = std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
-                                slots ? "true" : "false", p.subs, form, p.grid, 256 * p.subs, p.lds, p.subs > 1 ? p.fair : 0,
-                                p.subs > 1 ? p.slack : -1, p.remap);
-    if (tape && k > 0 && (size_t)k < n)
-        std::snprintf(buf + k, n - (size_t)k, " tape_k=%d%s", TAPE_K, p.tape_ungrouped ? " ungrouped=tape_lds" : "");
-    if (descent && k > 0 && (size_t)k < n)
-        std::snprintf(buf + k, n - (size_t)k, MAPF_DESCENT_FETCH == 1 ? " fetch=lds_planes%s" : " fetch=load%s", p.tape_ungrouped ? " ungrouped=descent_lds" : "");
+    char band_tag[16] = "";
+    if (band) std::snprintf(band_tag, sizeof band_tag, ",band%d", MAPF_BAND_UNIT);
+    const int k = std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
+                                slots ? "true" : "false", p.subs, band_tag, rollout_policy_tag(policy), p.grid, 256 * p.subs,
+                                p.lds, p.subs > 1 ? p.fair : 0, p.subs > 1 ? p.slack : -1, p.remap);
+    if (k > 0 && (size_t)k < n) {
+        if (policy == ROLLOUT_TAPE)
+            std::snprintf(buf + k, n - (size_t)k, " tape_k=%d%s", TAPE_K, p.tape_ungrouped ? " ungrouped=tape_lds" : "");
+        if (policy == ROLLOUT_DESCENT)
+            std::snprintf(buf + k, n - (size_t)k, " fetch=load%s", p.tape_ungrouped ? " ungrouped=descent_lds" : "");
+    }
     return true;
 }
 
@@ -539,17 +432,14 @@ int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOu
         return MAPF_OK;
     };
     (void)ring;
-    auto pick = [&](auto pol) -> int {
-        constexpr bool TP = decltype(pol)::value == ROLLOUT_TAPE, DS = decltype(pol)::value == ROLLOUT_DESCENT;
+    return with_policy(policy, [&](auto pol) -> int {
+        constexpr int POL = decltype(pol)::value;
         if (band)
-            return p.subs == 4 ? launch(rollout_random_kernel<true, 4, true, TP, DS>) : launch(rollout_random_kernel<true, 1, true, TP, DS>);
+            return p.subs == 4 ? launch(rollout_random_kernel<true, 4, true, POL>) : launch(rollout_random_kernel<true, 1, true, POL>);
         if (p.subs == 4)
-            return slots ? launch(rollout_random_kernel<true, 4, false, TP, DS>) : launch(rollout_random_kernel<false, 4, false, TP, DS>);
-        return slots ? launch(rollout_random_kernel<true, 1, false, TP, DS>) : launch(rollout_random_kernel<false, 1, false, TP, DS>);
-    };
-    return policy == ROLLOUT_DESCENT ? pick(std::integral_constant<int, ROLLOUT_DESCENT>{})
-           : policy == ROLLOUT_TAPE  ? pick(std::integral_constant<int, ROLLOUT_TAPE>{})
-                                     : pick(std::integral_constant<int, ROLLOUT_RANDOM>{});
+            return slots ? launch(rollout_random_kernel<true, 4, false, POL>) : launch(rollout_random_kernel<false, 4, false, POL>);
+        return slots ? launch(rollout_random_kernel<true, 1, false, POL>) : launch(rollout_random_kernel<false, 1, false, POL>);
+    });
 }
 
 bool step_observe_fusable(const DevEnv &e) {

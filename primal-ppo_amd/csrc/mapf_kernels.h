@@ -3,6 +3,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include "mapf.h"
@@ -91,26 +92,39 @@ void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, 
 // (the kernel's form from the handle's tuning, mapf.h: mapf_tuning); describe_* write the
 // form launch_* would take as text (mapf_rollout_plan).  launch_/describe_rollout_random take
 // mapf_rollout_random's `slots` bits (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN), the wide ones 0 / 1.
-// tape (mapf_rollout_actions): `actions` is the caller's [T][B][N] tape, read only, played instead
-// of the random draw (the kernels' TAPE instantiations; the plan's text carries ",tape").
+// policy: where the actions come from, the kernels' POL template parameter.
+//   ROLLOUT_RANDOM (mapf_rollout_random): the in-kernel Philox draw, written to `actions`.
+//   ROLLOUT_TAPE (mapf_rollout_actions): `actions` is the caller's [T][B][N] tape, read only, played
+//     instead of the draw; the plan's text carries ",tape".
+//   ROLLOUT_DESCENT (mapf_rollout_descent): every action is picked from the agents' tiled BFS maps
+//     (keep_bfs) and written to `actions` like the draw; the plan's text carries ",descent" (and
+//     bfsobs=0 in the wide three-wave form).
 // describe_rollout_random returns false (text "none") where the pair-lane kernel does not take the
-// launch -- with a tape that includes a fusable configuration whose staged rows do not fit its LDS.
-// policy = ROLLOUT_DESCENT (mapf_rollout_descent): the kernels' DESCENT instantiations pick every
-// action from the agents' tiled BFS maps (keep_bfs) and write it to `actions` like the random draw;
-// the plan's text carries ",descent" (and bfsobs=0 in the wide three-wave form).
+// launch -- with a tape or descent that includes a fusable configuration whose LDS rows do not fit.
 constexpr int ROLLOUT_NOT_COVERED = 1;
 constexpr int ROLLOUT_RANDOM = 0, ROLLOUT_TAPE = 1, ROLLOUT_DESCENT = 2;
+// f(std::integral_constant<int, policy>{}): the runtime policy as a template argument
+template <class F>
+inline auto with_policy(int policy, F f) {
+    if (policy == ROLLOUT_DESCENT) return f(std::integral_constant<int, ROLLOUT_DESCENT>{});
+    if (policy == ROLLOUT_TAPE) return f(std::integral_constant<int, ROLLOUT_TAPE>{});
+    return f(std::integral_constant<int, ROLLOUT_RANDOM>{});
+}
+// the policy's mark inside the angle brackets of the plan text
+inline const char *rollout_policy_tag(int policy) {
+    return policy == ROLLOUT_DESCENT ? ",descent" : (policy == ROLLOUT_TAPE ? ",tape" : "");
+}
 bool rollout_random_fusable(const DevEnv &e);
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                           int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy = ROLLOUT_RANDOM);
-bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy = ROLLOUT_RANDOM);
+                           int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy);
+bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy);
 // the same for up to 64 agents / per-env maps / the BFS channel: one wave per env
 // (mapf_rollout_wide.hip); used where the pair-lane rollout does not apply.  Returns MAPF_OK or
 // MAPF_ESTATE (a captured launch found no free argument slot, ArgRing).
 bool rollout_wide_fusable(const DevEnv &e);
 int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                        int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy = ROLLOUT_RANDOM);
-void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy = ROLLOUT_RANDOM);
+                        int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy);
+void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy);
 
 // Device-resident kernel argument blocks.  A persistent kernel whose arguments (DevEnv + its
 // output pointers, ~0.5 KiB) do not fit in the SGPR file kept them live from the kernarg

@@ -190,8 +190,9 @@ __device__ inline void wide_plain_barrier() {
 // the picks like the random draw's.  The maps the step rebuilds are always searched by the stepping
 // wave itself, never by the observers (bfsobs is ignored: they run up to WIDE_SNAPS steps behind),
 // so every map the step reads was written by the reading wave or before the launch.
-template <class T, int RW, bool NT, bool TAPE = false, bool DESCENT = false>
+template <class T, int RW, bool NT, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
 __device__ __attribute__((always_inline)) inline void rollout_wide_body(const DevEnv &e, int T_steps, const WideOut &ro) {
+    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // XCD-aware env order (as the pair-lane rollout): workgroups are dealt round-robin
     // over the 8 XCDs, so each XCD owns one contiguous range of envs
@@ -438,10 +439,10 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
     WSTAMP_END(b, role);
 }
 
-template <class T, int RW, bool NT, bool TAPE = false, bool DESCENT = false>
+template <class T, int RW, bool NT, int POL>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void rollout_wide_kernel(WIDE_PARAMS) {
     WIDE_BIND
-    rollout_wide_body<T, RW, NT, TAPE, DESCENT>(e, T_steps, ro);
+    rollout_wide_body<T, RW, NT, POL>(e, T_steps, ro);
 }
 
 // Three waves per env (c4): the stepper and two observers taking alternate steps.  With one
@@ -449,10 +450,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void r
 // SIMD issuing each step's 31 KiB of stores).  Three waves per SIMD need <= 168 VGPRs:
 // the arguments come through a device pointer (ArgRing), which also frees the ~450 SGPRs the
 // by-value arguments spilled to VGPR lanes (152 VGPRs, 129 SGPR spills, no scratch).
-template <class T, int RW, bool NT, bool TAPE = false, bool DESCENT = false>
+template <class T, int RW, bool NT, int POL>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void rollout_wide3_kernel(
     const WideArgs *__restrict__ args, int T_steps) {
-    rollout_wide_body<T, RW, NT, TAPE, DESCENT>(args->e, T_steps, args->ro);
+    rollout_wide_body<T, RW, NT, POL>(args->e, T_steps, args->ro);
 }
 
 // The three-wave form is not built for 128-bit rows spread over two lanes (maps wider than 64 cells):
@@ -475,9 +476,8 @@ struct WidePlan {
 };
 
 // POL (ROLLOUT_*): the form of the tape / descent kernels (their own register counts decide what fits)
-template <class T, int RW, int POL = 0>
+template <class T, int RW, int POL>
 static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
-    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT;
     WidePlan p;
     // persistent waves: every CU holds the same number of workgroups (the LDS request caps
     // them at ceil(B / CUs) per CU, 160 KiB of LDS per CU), or the fuller CUs pace each step
@@ -489,12 +489,12 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     // 446 MB, measured 94 vs 124 us per step); smaller ones keep plain stores (c2, c4;
     // c4 in place, nt sc1: 6.27 -> 7.03 us per step)
     p.nt = tu.wide_nt >= 0 ? tu.wide_nt != 0 : (slots || (size_t)e.B * e.N * e.C * e.F * e.F * 4 > ((size_t)128 << 20));
-    const void *kern = p.nt ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, true, TAPE, DESCENT>)
-                            : reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, false, TAPE, DESCENT>);
+    const void *kern = p.nt ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, true, POL>)
+                            : reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, false, POL>);
     const void *kern3 = nullptr;
     if constexpr (wide3_form<T, RW>())
-        kern3 = p.nt ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, true, TAPE, DESCENT>)
-                     : reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, false, TAPE, DESCENT>);
+        kern3 = p.nt ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, true, POL>)
+                     : reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, false, POL>);
     // two waves per env where every env's pair fits at once: the VGPR budget of a SIMD
     // (512 per lane) over the waves it must hold, 4 SIMDs per CU
     const int fit = 512 / ((kernel_vgprs(kern) + 7) & ~7);
@@ -505,7 +505,7 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     r.slots = slots;
     r.xcd_remap = tu.xcd_remap != 0;
     r.prio = tu.wide_prio;
-    r.bfsobs = DESCENT ? 0 : tu.wide_bfsobs;      // descent: the stepping wave reads the maps it rebuilt
+    r.bfsobs = POL == ROLLOUT_DESCENT ? 0 : tu.wide_bfsobs;      // descent: the stepping wave reads the maps it rebuilt
     r.grid = 0;
     if (!pipe && wide_grid_bytes(e) <= wide_scratch_bytes<T, RW>(e)) r.grid = 2;
     else if (wide_lds_bytes<T, RW>(e, 1) <= (occ > 1 ? cap : (size_t)64 * 1024)) r.grid = 1;
@@ -563,7 +563,6 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
 template <class T, int RW, int POL>
 static int launch_wide_t(const DevEnv &e, int steps, const WideOut &ro, const mapf_tuning &tu, ArgRing &ring,
                          hipStream_t s) {
-    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT;
     const WidePlan p = plan_wide_t<T, RW, POL>(e, ro.slots, tu);
     WideOut r = p.r;
     r.actions = ro.actions;
@@ -574,12 +573,12 @@ static int launch_wide_t(const DevEnv &e, int steps, const WideOut &ro, const ma
         if (r.wpe == 3) {
             const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
             if (!args) return MAPF_ESTATE;
-            auto kern3 = p.nt ? rollout_wide3_kernel<T, RW, true, TAPE, DESCENT> : rollout_wide3_kernel<T, RW, false, TAPE, DESCENT>;
+            auto kern3 = p.nt ? rollout_wide3_kernel<T, RW, true, POL> : rollout_wide3_kernel<T, RW, false, POL>;
             hipLaunchKernelGGL(kern3, dim3(p.grid), dim3(p.block), p.lds, s, args, steps);
             return MAPF_OK;
         }
     }
-    auto kern = p.nt ? rollout_wide_kernel<T, RW, true, TAPE, DESCENT> : rollout_wide_kernel<T, RW, false, TAPE, DESCENT>;
+    auto kern = p.nt ? rollout_wide_kernel<T, RW, true, POL> : rollout_wide_kernel<T, RW, false, POL>;
 #if MAPF_ARGS_PTR
     const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
     if (!args) return MAPF_ESTATE;
@@ -621,9 +620,7 @@ int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut 
     return with_row_type(e, [&](auto t, auto rw) {
         using R = decltype(t);
         constexpr int RWV = decltype(rw)::value;
-        return policy == ROLLOUT_DESCENT ? launch_wide_t<R, RWV, ROLLOUT_DESCENT>(e, T, ro, tu, ring, s)
-               : policy == ROLLOUT_TAPE  ? launch_wide_t<R, RWV, ROLLOUT_TAPE>(e, T, ro, tu, ring, s)
-                                         : launch_wide_t<R, RWV, 0>(e, T, ro, tu, ring, s);
+        return with_policy(policy, [&](auto pol) { return launch_wide_t<R, RWV, decltype(pol)::value>(e, T, ro, tu, ring, s); });
     });
 }
 
@@ -631,14 +628,12 @@ void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, ch
     with_row_type(e, [&](auto t, auto rw) {
         using R = decltype(t);
         constexpr int RWV = decltype(rw)::value;
-        const WidePlan p = policy == ROLLOUT_DESCENT ? plan_wide_t<R, RWV, ROLLOUT_DESCENT>(e, slots, tu)
-                           : policy == ROLLOUT_TAPE  ? plan_wide_t<R, RWV, ROLLOUT_TAPE>(e, slots, tu)
-                                                     : plan_wide_t<R, RWV, 0>(e, slots, tu);
+        const WidePlan p = with_policy(policy, [&](auto pol) { return plan_wide_t<R, RWV, decltype(pol)::value>(e, slots, tu); });
         std::snprintf(buf, n, "%s<%s,%d,%s%s> grid=%d block=%d lds=%zu wpe=%d epw=%d grid_mode=%d overlap=%d slack=%d "
                               "fair=%d prio=%d bfsobs=%d pair=%d remap=%d",
                       p.r.wpe == 3 ? "rollout_wide3_kernel" : "rollout_wide_kernel", row_name<decltype(t)>(),
                       (int)decltype(rw)::value, p.nt ? "true" : "false",
-                      policy == ROLLOUT_DESCENT ? ",descent" : (policy == ROLLOUT_TAPE ? ",tape" : ""), p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
+                      rollout_policy_tag(policy), p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
                       p.r.grid, p.r.overlap, p.r.slack, p.r.fair, p.r.prio, p.r.bfsobs, p.r.pair, p.r.xcd_remap);
         return 0;
     });

@@ -315,11 +315,9 @@ __host__ __device__ inline size_t wave_lds(int H, int W) {
 //                   its length into hlen[b][buf]; returns that length (0 for a BFS map).
 // `lds` = wave_lds<T, RW>(H, W) bytes of this wave's LDS; `map` = the env's padded
 // obstacle rows if the caller holds a copy (e.g. in LDS), else read from HBM.
-// PLANES (u32 rows, one lane per row; the pair-lane rollout's descent experiment): a BFS map's
-// distance bits 0 and 1 also go to LDS, planes[row] and planes[H + row].
-template <class T, int RW, bool PLANES = false>
+template <class T, int RW>
 __device__ __attribute__((always_inline)) inline int search_one(const DevEnv &e, bool replan, int b, uint32_t ai, uint32_t sr_cell, uint32_t stop_cell,
-                          int buf, char *lds, const uint32_t *map = nullptr, uint32_t *planes = nullptr) {
+                          int buf, char *lds, const uint32_t *map = nullptr) {
     const int lane = lane_id();
     const int W = e.W, H = e.H;
     int len = 0;
@@ -345,12 +343,6 @@ __device__ __attribute__((always_inline)) inline int search_one(const DevEnv &e,
             {
                 T V[RW], D[K][RW];
                 const int maxd = bfs_planes<T, RW, K>(fre, sr, sc, -1, -1, V, D);
-                if constexpr (PLANES && sizeof(T) == 4 && RW == 1) {
-                    if (lane < H) {
-                        as_lds(planes)[lane] = (uint32_t)D[0][0];
-                        as_lds(planes)[H + lane] = (uint32_t)D[1][0];
-                    }
-                }
                 if (sizeof(T) == 4 || maxd < (1 << K)) {
                     planes_to_tiles<T, RW, K>(V, fre, D, 32 - __builtin_clz((unsigned)maxd | 1u), H, W, dst);
                     done = true;

@@ -123,15 +123,23 @@ class BatchedMapfGym:
         _lib.check(_lib.lib().mapf_set_tuning(self.h, ctypes.byref(t)))
         self._query_forms()
 
-    def rollout_plan(self, slots=False, band_clean=False):
-        """The kernel (template instantiation + form) mapf_rollout_random launches now, as text
-        (band_clean: for a slots launch with MAPF_SLOTS_BAND_CLEAN)."""
+    @staticmethod
+    def _slot_bits(slots, band_clean):
+        """The `slots` argument of the mapf_rollout_* calls (MAPF_SLOTS_*, mapf.h)."""
+        return (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
+
+    def _plan(self, fn, slots, band_clean):
+        """The text of one of the mapf_rollout_*plan calls."""
         buf = ctypes.create_string_buffer(512)
-        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
-        kind = _lib.lib().mapf_rollout_plan(self.h, bits, buf, 512)
+        kind = fn(self.h, self._slot_bits(slots, band_clean), buf, 512)
         if kind < 0:
             _lib.check(kind)
         return buf.value.decode()
+
+    def rollout_plan(self, slots=False, band_clean=False):
+        """The kernel (template instantiation + form) mapf_rollout_random launches now, as text
+        (band_clean: for a slots launch with MAPF_SLOTS_BAND_CLEAN)."""
+        return self._plan(_lib.lib().mapf_rollout_plan, slots, band_clean)
 
     def rollout_kernel_name(self, slots=False):
         """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,false>'."""
@@ -140,12 +148,7 @@ class BatchedMapfGym:
     def rollout_actions_plan(self, slots=False, band_clean=False):
         """rollout_plan for rollout_actions (mapf_rollout_actions_plan): the same text with ",tape"
         inside the angle brackets, or "step_observe" where the call runs per-step launches."""
-        buf = ctypes.create_string_buffer(512)
-        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
-        kind = _lib.lib().mapf_rollout_actions_plan(self.h, bits, buf, 512)
-        if kind < 0:
-            _lib.check(kind)
-        return buf.value.decode()
+        return self._plan(_lib.lib().mapf_rollout_actions_plan, slots, band_clean)
 
     def rollout_actions_kernel_name(self, slots=False, band_clean=False):
         """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,tape>'."""
@@ -155,12 +158,7 @@ class BatchedMapfGym:
         """rollout_plan for rollout_descent (mapf_rollout_descent_plan): the same text with ",descent"
         inside the angle brackets (the wide three-wave form with bfsobs=0), or
         "descent_actions+step_observe" where the call runs per-step launches."""
-        buf = ctypes.create_string_buffer(512)
-        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
-        kind = _lib.lib().mapf_rollout_descent_plan(self.h, bits, buf, 512)
-        if kind < 0:
-            _lib.check(kind)
-        return buf.value.decode()
+        return self._plan(_lib.lib().mapf_rollout_descent_plan, slots, band_clean)
 
     def rollout_descent_kernel_name(self, slots=False, band_clean=False):
         """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,descent>'."""
@@ -345,25 +343,9 @@ class BatchedMapfGym:
             _, fn, h, so, pa, po, pv = fast
             _lib.check(fn(h, int(T), 0, pa, so, po, pv, _stream(self.device)))
             return self.out, self.obs, self.vec
-        k = T if slots else 1
-        actions = self.actions if actions is None else actions
-        obs = self.obs if obs is None else obs
-        vec = self.vec if vec is None else vec
-        _check(actions, torch.int32, k * self.B * self.N, self.device, "actions")
-        _check(obs, torch.float32, k * self.B * self.N * self.C * self.F * self.F, self.device, "obs")
-        _check(vec, torch.float32, k * self.B * self.N * 4, self.device, "vec")
-        if out is None:
-            if slots:
-                raise ValueError("slots=True needs [T]-leading output buffers (out=...)")
-            so, out = self._stepout, self.out
-        else:
-            for key, t in out.items():
-                ref = self.out[key]
-                _check(t, ref.dtype, k * ref.numel(), self.device, key)
-            so = self._make_stepout(out)
-        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
-        _lib.check(_lib.lib().mapf_rollout_random(self.h, int(T), bits, _ptr(actions), ctypes.byref(so),
-                                                  _ptr(obs), _ptr(vec), _stream(self.device)))
+        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions)
+        _lib.check(_lib.lib().mapf_rollout_random(self.h, int(T), self._slot_bits(slots, band_clean), _ptr(actions),
+                                                  ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
 
     def _check_tape(self, tape, T=None):
@@ -376,8 +358,15 @@ class BatchedMapfGym:
         _check(tape, torch.int32, tape.shape[0] * self.B * self.N, self.device, "tape")
         return int(tape.shape[0])
 
-    def _rollout_buffers(self, k, obs, vec, out, slots):
-        """The output buffers of a rollout call (k = T with slots, else 1), checked: (so, out, obs, vec)."""
+    def _rollout_buffers(self, k, slots, obs, vec, out, actions=None, tape=None):
+        """The buffers of a rollout call (k = T with slots, else 1), defaulted and checked in the order
+        actions, obs, vec, out: (actions, so, out, obs, vec).  tape: a tape _check_tape has passed,
+        handed back in the actions' place."""
+        if tape is not None:
+            actions = tape
+        else:
+            actions = self.actions if actions is None else actions
+            _check(actions, torch.int32, k * self.B * self.N, self.device, "actions")
         obs = self.obs if obs is None else obs
         vec = self.vec if vec is None else vec
         _check(obs, torch.float32, k * self.B * self.N * self.C * self.F * self.F, self.device, "obs")
@@ -385,11 +374,11 @@ class BatchedMapfGym:
         if out is None:
             if slots:
                 raise ValueError("slots=True needs [T]-leading output buffers (out=...)")
-            return self._stepout, self.out, obs, vec
+            return actions, self._stepout, self.out, obs, vec
         for key, t in out.items():
             ref = self.out[key]
             _check(t, ref.dtype, k * ref.numel(), self.device, key)
-        return self._make_stepout(out), out, obs, vec
+        return actions, self._make_stepout(out), out, obs, vec
 
     def rollout_actions(self, tape, slots=False, obs=None, vec=None, out=None, band_clean=False):
         """T x step_observe(tape[t]) -- the caller's policy, T = tape.shape[0] steps -- as ONE launch
@@ -400,12 +389,11 @@ class BatchedMapfGym:
         out["actions_fixed"] is what was executed and must not overlap the tape.
         Returns (out, obs, vec)."""
         T = self._check_tape(tape)
-        so, out, obs, vec = self._rollout_buffers(T if slots else 1, obs, vec, out, slots)
+        tape, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, tape=tape)
         if T == 0:          # nothing to play (an empty tensor has no address to hand over)
             return out, obs, vec
-        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
-        _lib.check(_lib.lib().mapf_rollout_actions(self.h, T, bits, _ptr(tape), ctypes.byref(so), _ptr(obs), _ptr(vec),
-                                                   _stream(self.device)))
+        _lib.check(_lib.lib().mapf_rollout_actions(self.h, T, self._slot_bits(slots, band_clean), _ptr(tape),
+                                                   ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
 
     def rollout_descent(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False):
@@ -417,15 +405,11 @@ class BatchedMapfGym:
         T = int(T)
         if T < 0:
             raise ValueError("T must be >= 0")
-        k = T if slots else 1
-        actions = self.actions if actions is None else actions
-        _check(actions, torch.int32, k * self.B * self.N, self.device, "actions")
-        so, out, obs, vec = self._rollout_buffers(k, obs, vec, out, slots)
+        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions)
         if T == 0:          # nothing to play (an empty tensor has no address to hand over)
             return out, obs, vec
-        bits = (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
-        _lib.check(_lib.lib().mapf_rollout_descent(self.h, T, bits, _ptr(actions), ctypes.byref(so), _ptr(obs),
-                                                   _ptr(vec), _stream(self.device)))
+        _lib.check(_lib.lib().mapf_rollout_descent(self.h, T, self._slot_bits(slots, band_clean), _ptr(actions),
+                                                   ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
 
     def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None, actions_in=None,
@@ -453,26 +437,13 @@ class BatchedMapfGym:
             raise ValueError(f"policy: expected 'random' or 'descent', got {policy!r}")
         if policy != "random" and actions_in is not None:
             raise ValueError("policy and actions_in are mutually exclusive")
-        k = T if slots else 1
         if actions_in is not None:
             self._check_tape(actions_in, int(T))
-            actions = actions_in
-        actions = self.actions if actions is None else actions
-        obs = self.obs if obs is None else obs
-        vec = self.vec if vec is None else vec
-        _check(actions, torch.int32, (T if actions_in is not None else k) * self.B * self.N, self.device, "actions")
-        _check(obs, torch.float32, k * self.B * self.N * self.C * self.F * self.F, self.device, "obs")
-        _check(vec, torch.float32, k * self.B * self.N * 4, self.device, "vec")
-        if out is None:
-            if slots:
-                raise ValueError("slots=True needs [T]-leading output buffers (out=...)")
-            out = self.out
-        for key, t in out.items():
-            _check(t, self.out[key].dtype, k * self.out[key].numel(), self.device, key)
-        so = self._make_stepout(out)
-        args = (self.h, int(T), _lib.SLOTS if slots else 0, _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec),
+        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
+                                                           tape=actions_in)
+        args = (self.h, int(T), self._slot_bits(slots, False), _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec),
                 _stream(self.device))
-        clean = args[:2] + (_lib.SLOTS | _lib.SLOTS_BAND_CLEAN,) + args[3:] if slots else args
+        clean = args[:2] + (self._slot_bits(slots, True),) + args[3:]
         fn = (_lib.lib().mapf_rollout_actions if actions_in is not None else
               _lib.lib().mapf_rollout_descent if policy == "descent" else _lib.lib().mapf_rollout_random)
         keep = (so, actions, obs, vec, out)
