@@ -215,6 +215,12 @@ int mapf_step_observe_random(mapf_env *env, int32_t *actions_out, const mapf_ste
  * nothing about its content, so only the caller can make this promise. */
 #define MAPF_SLOTS 1
 #define MAPF_SLOTS_BAND_CLEAN 2
+/* MAPF_SLOTS_OBS_BITS (bit 2), on mapf_rollout_random / _actions / _descent: `obs` points at the
+ * packed observation buffer uint32 [T or 1][B][N][WPA] ("Packed observations" below) instead of
+ * float [T or 1][B][N][C][F][F]; every other buffer is unchanged.  Orthogonal to MAPF_SLOTS.  With it
+ * MAPF_SLOTS_BAND_CLEAN is ignored (packed zeros cost nothing to write), and the mapf_rollout_*plan
+ * texts carry ",bits" inside the angle brackets. */
+#define MAPF_SLOTS_OBS_BITS 4
 int mapf_rollout_random(mapf_env *env, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
                         float *obs, float *vec, void *stream);
 /* Which kernel mapf_rollout_random runs for this configuration (0: T per-step
@@ -718,6 +724,39 @@ int mapf_conv_select(int32_t impl);
  * conv and mapf_nhwc_bias_relu in one launch. */
 int mapf_conv_first_f32(const float *x_nchw, const uint16_t *w, const uint16_t *bias, uint16_t *y, int64_t nimg,
                         int32_t Cin, int32_t H, int32_t W, int32_t Cout, void *stream);
+
+/* ---- Packed observations: one bit per cell ----
+ * Every observation value is 0.0 or 1.0.  With CFF = num_channel * fov * fov and WPA = ceil(CFF / 32),
+ * an agent's packed observation is WPA little-endian uint32 words: bit k % 32 of word k / 32 is float
+ * k of its [C][F][F] block (1 for 1.0f); the 32 * WPA - CFF padding bits of the last word are 0 and
+ * always written.  Buffers are uint32 [..][N][WPA] wherever the float calls have float
+ * [..][N][C][F][F] (c2: 92 B per agent against 2,904); `vec` is unchanged.  In numpy:
+ * np.packbits(obs.reshape(A, CFF) != 0, axis=1, bitorder="little"), zero-padded to 4 * WPA bytes.
+ *
+ * mapf_obs_bits_words: WPA of a configuration (host only, no device call; <= 0 arguments give 0).
+ * mapf_observe_bits / mapf_step_observe_bits: mapf_observe / mapf_step_observe writing
+ * bits [B][N][WPA] on the device.  Where the float call would fork the pending search beside the
+ * observe launch (wide maps, the BFS channel) and rewrite channel 6 as floats afterwards, the packed
+ * call joins the search on the caller's stream before it observes, as mapf_tuning.serial_search = 1
+ * does for the float call: there is no packed BFS fixup.
+ * mapf_obs_pack_host / mapf_obs_unpack_host: the format on the host (obs [n_agents][C][F][F] floats,
+ * non-zero packs as 1; bits [n_agents][WPA]), through the function the kernels run.
+ * mapf_unpack_obs: bits [n_agents][WPA] on the device -> dst [n_agents][C][F][F] as 0 / 1 in fp32
+ * (dst_f16 = 0) or fp16 (1); dst needs 4-byte alignment only.  Launches nothing for n_agents = 0;
+ * capturable.
+ * mapf_conv_first_bits: mapf_conv_first_f32 reading the packed observation (bits [nimg][WPA], one
+ * image per agent, Cin = num_channel, H = W = fov); its output is bit-identical to
+ * mapf_conv_first_f32 on the unpacked floats. */
+int32_t mapf_obs_bits_words(const mapf_config *cfg);
+int mapf_observe_bits(mapf_env *env, uint32_t *bits, float *vec, void *stream);
+int mapf_step_observe_bits(mapf_env *env, const int32_t *actions, const mapf_step_out *out, uint32_t *bits, float *vec,
+                           void *stream);
+int mapf_obs_pack_host(const float *obs, int64_t n_agents, int32_t C, int32_t F, uint32_t *bits);
+int mapf_obs_unpack_host(const uint32_t *bits, int64_t n_agents, int32_t C, int32_t F, float *obs);
+int mapf_unpack_obs(const uint32_t *bits, void *dst, int64_t n_agents, int32_t C, int32_t F, int32_t dst_f16,
+                    void *stream);
+int mapf_conv_first_bits(const uint32_t *bits, const uint16_t *w, const uint16_t *bias, uint16_t *y, int64_t nimg,
+                         int32_t Cin, int32_t H, int32_t W, int32_t Cout, void *stream);
 
 /* mapf_ppo_loss with coef[6] in DEVICE memory (captured-graph updates: the Lagrangian term changes
  * every update without re-capturing). */

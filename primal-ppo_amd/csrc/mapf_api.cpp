@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -293,10 +294,11 @@ static int rollout_plan_impl(const mapf_env *e, int policy, int32_t slots, char 
     if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
     if (rollout_random_fusable(e->d) && describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n, policy)) return 1;
     if (rollout_wide_fusable(e->d)) {
-        describe_rollout_wide(e->d, slots & 1, e->tune, buf, (size_t)n, policy);
+        describe_rollout_wide(e->d, slots & (MAPF_SLOTS | MAPF_SLOTS_OBS_BITS), e->tune, buf, (size_t)n, policy);
         return 2;
     }
-    std::snprintf(buf, (size_t)n, policy == ROLLOUT_DESCENT ? "descent_actions+step_observe" : "step_observe");
+    std::snprintf(buf, (size_t)n, "%s%s", policy == ROLLOUT_DESCENT ? "descent_actions+step_observe" : "step_observe",
+                  (slots & MAPF_SLOTS_OBS_BITS) ? "_bits" : "");
     return 0;
 }
 int mapf_rollout_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
@@ -311,6 +313,43 @@ int mapf_rollout_descent_plan(const mapf_env *e, int32_t slots, char *buf, int32
 
 int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent) {
     return descent_pick(descent_mask, clock, (int)agent);
+}
+
+int32_t mapf_obs_bits_words(const mapf_config *cfg) {
+    if (!cfg || cfg->num_channel < 1 || cfg->fov < 1) return 0;
+    return obs_bits_words(cfg->num_channel, cfg->fov);
+}
+
+// The format on the host.  Agents go through in chunks: each chunk's floats become the contiguous
+// bit-stream the kernels hold in LDS (bit k*CFF + j = float j of agent k, plus the spare word), and
+// every output word is obs_bits_word of it -- the function obs_emit<.., OBS_BITS> stores with.
+int mapf_obs_pack_host(const float *obs, int64_t n_agents, int32_t C, int32_t F, uint32_t *bits) {
+    if (n_agents < 0 || C < 1 || F < 1 || C > 64 || F > 64) return fail(MAPF_EINVAL, "n_agents, C or F out of range");
+    if (n_agents == 0) return MAPF_OK;
+    if (!obs || !bits) return fail(MAPF_EINVAL, "null argument");
+    const int CFF = C * F * F, WPA = obs_bits_words(C, F);
+    constexpr int CHUNK = 256;
+    std::vector<uint32_t> stream(((size_t)CHUNK * CFF + 31) / 32 + 1);
+    for (int64_t a0 = 0; a0 < n_agents; a0 += CHUNK) {
+        const int K = (int)std::min<int64_t>(CHUNK, n_agents - a0);
+        std::fill(stream.begin(), stream.end(), 0u);
+        const float *src = obs + (size_t)a0 * CFF;
+        for (size_t q = 0; q < (size_t)K * CFF; ++q)
+            if (src[q] != 0.f) stream[q >> 5] |= 1u << (q & 31);
+        for (int k = 0; k < K; ++k)
+            for (int w = 0; w < WPA; ++w) bits[((size_t)a0 + k) * WPA + w] = obs_bits_word(stream.data(), CFF, k, w);
+    }
+    return MAPF_OK;
+}
+
+int mapf_obs_unpack_host(const uint32_t *bits, int64_t n_agents, int32_t C, int32_t F, float *obs) {
+    if (n_agents < 0 || C < 1 || F < 1 || C > 64 || F > 64) return fail(MAPF_EINVAL, "n_agents, C or F out of range");
+    if (n_agents == 0) return MAPF_OK;
+    if (!obs || !bits) return fail(MAPF_EINVAL, "null argument");
+    const int CFF = C * F * F, WPA = obs_bits_words(C, F);
+    for (int64_t a = 0; a < n_agents; ++a)
+        for (int j = 0; j < CFF; ++j) obs[(size_t)a * CFF + j] = (float)obs_bits_get(bits + (size_t)a * WPA, j);
+    return MAPF_OK;
 }
 
 int mapf_obs_band_skip(const mapf_config *cfg, int32_t unit, uint64_t byte_offset, uint8_t *skip, int32_t n) {
@@ -597,7 +636,8 @@ static int observe_with_search(mapf_env *e, float *obs, float *vec, hipStream_t 
     return MAPF_OK;
 }
 
-int mapf_observe(mapf_env *e, float *obs, float *vec, void *stream) {
+// bits: obs is the packed uint32 [B][N][WPA] buffer (mapf_observe_bits)
+static int observe_impl(mapf_env *e, float *obs, float *vec, void *stream, bool bits) {
     if (!e || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
     if (!e->ready) return fail(MAPF_ESTATE, "mapf_observe before mapf_reset");
     HIPCHK(hipSetDevice(e->device));
@@ -605,7 +645,9 @@ int mapf_observe(mapf_env *e, float *obs, float *vec, void *stream) {
     int nsearch = 0, parity = 0;
     if (e->pending >= 0) {
         if (!observe_hosts_search(e->d) || e->d.C >= 7) {   // wide grids / BFS channel: search beside the launch
-            if (!e->tune.serial_search) return observe_with_search(e, obs, vec, s);
+            // the forked form ends in launch_bfs_fixup, which rewrites channel 6 as FLOATS (32 times a
+            // packed buffer's size): a packed call always joins the search first (mapf.h)
+            if (!e->tune.serial_search && !bits) return observe_with_search(e, obs, vec, s);
             if (int rc = flush_search(e, s)) return rc;
         } else {                       // search work rides in the observe launch
             nsearch = e->d.search_blocks;
@@ -613,18 +655,23 @@ int mapf_observe(mapf_env *e, float *obs, float *vec, void *stream) {
             e->pending = -1;
         }
     }
-    launch_observe(e->d, obs, vec, nsearch, parity, s);
+    launch_observe(e->d, obs, vec, nsearch, parity, s, bits);
     HIPCHK(hipGetLastError());
     return MAPF_OK;
 }
 
+int mapf_observe(mapf_env *e, float *obs, float *vec, void *stream) { return observe_impl(e, obs, vec, stream, false); }
+int mapf_observe_bits(mapf_env *e, uint32_t *bits, float *vec, void *stream) {
+    return observe_impl(e, reinterpret_cast<float *>(bits), vec, stream, true);
+}
+
 static int step_observe_impl(mapf_env *e, int32_t *actions, const mapf_step_out *out, uint32_t flags, float *obs,
-                             float *vec, void *stream) {
+                             float *vec, void *stream, bool bits = false) {
     if (!e || !actions || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
     if (!e->ready) return fail(MAPF_ESTATE, "mapf_step_observe before mapf_reset");
     if (!step_observe_fusable(e->d)) {          // two launches, same results
         if (int rc = step_impl(e, actions, out, MAPF_STEP_COMMIT | flags, stream)) return rc;
-        return mapf_observe(e, obs, vec, stream);
+        return observe_impl(e, obs, vec, stream, bits);
     }
     HIPCHK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
@@ -639,7 +686,7 @@ static int step_observe_impl(mapf_env *e, int32_t *actions, const mapf_step_out 
         e->pending = -1;
     }
     const int parity = e->parity;
-    launch_step_observe(e->d, actions, o, MAPF_STEP_COMMIT | flags, parity, obs, vec, nsearch, sslot, s);
+    launch_step_observe(e->d, actions, o, MAPF_STEP_COMMIT | flags, parity, obs, vec, nsearch, sslot, s, bits);
     if (e->d.human_mode != 0 || e->d.keep_bfs) {
         if (host) e->pending = parity;             // rides in the next launch
         else launch_search(e->d, parity, 0, s);
@@ -652,6 +699,11 @@ static int step_observe_impl(mapf_env *e, int32_t *actions, const mapf_step_out 
 int mapf_step_observe(mapf_env *e, const int32_t *actions, const mapf_step_out *out, float *obs, float *vec,
                       void *stream) {
     return step_observe_impl(e, const_cast<int32_t *>(actions), out, 0u, obs, vec, stream);
+}
+
+int mapf_step_observe_bits(mapf_env *e, const int32_t *actions, const mapf_step_out *out, uint32_t *bits, float *vec,
+                           void *stream) {
+    return step_observe_impl(e, const_cast<int32_t *>(actions), out, 0u, reinterpret_cast<float *>(bits), vec, stream, true);
 }
 
 int mapf_step_observe_random(mapf_env *e, int32_t *actions_out, const mapf_step_out *out, float *obs, float *vec,
@@ -678,10 +730,14 @@ static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, in
                         const mapf_step_out *out, float *obs, float *vec, void *stream) {
     if (!e || !actions || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
     if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
-    if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN)) return fail(MAPF_EINVAL, "slots: unknown bits");
+    if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN | MAPF_SLOTS_OBS_BITS)) return fail(MAPF_EINVAL, "slots: unknown bits");
     if (policy == ROLLOUT_DESCENT && !e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
     if (!e->ready) return fail(MAPF_ESTATE, std::string(name) + " before mapf_reset");
-    const size_t BN = (size_t)e->d.B * e->d.N, obs_t = BN * e->d.C * e->d.F * e->d.F;
+    // with MAPF_SLOTS_OBS_BITS `obs` is the packed buffer (uint32 behind the float pointer): a slot is
+    // B * N * WPA words, and every launch below is told so
+    const bool bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
+    const size_t BN = (size_t)e->d.B * e->d.N;
+    const size_t obs_t = bits ? BN * (size_t)obs_bits_words(e->d.C, e->d.F) : BN * e->d.C * e->d.F * e->d.F;
     if (policy == ROLLOUT_TAPE && out && out->actions_fixed && T > 0) {      // the tape is read while actions_fixed is written
         const uintptr_t a0 = (uintptr_t)actions, a1 = a0 + (size_t)T * BN * 4;
         const uintptr_t f0 = (uintptr_t)out->actions_fixed, f1 = f0 + ((slots & 1) ? (size_t)T : 1) * BN * 4;
@@ -697,7 +753,8 @@ static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, in
         const StepOut o = step_out_of(out);
         int rc = launch_rollout_random(e->d, T, actions, o, obs, vec, slots, e->tune, e->args, s, policy);
         if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
-            rc = launch_rollout_wide(e->d, T, actions, o, obs, vec, slots & 1, e->tune, e->args, s, policy);
+            rc = launch_rollout_wide(e->d, T, actions, o, obs, vec, slots & (MAPF_SLOTS | MAPF_SLOTS_OBS_BITS), e->tune,
+                                     e->args, s, policy);
         if (rc == MAPF_ESTATE)
             return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
                                      "(16 per handle, ArgRing; mapf_release_captures frees them)");
@@ -720,7 +777,7 @@ static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, in
             if (int rc = mapf_descent_actions(e, act, stream)) return rc;
         }
         if (int rc = step_observe_impl(e, act, out ? &ot : nullptr, policy == ROLLOUT_RANDOM ? 2u : 0u, obs + k * obs_t,
-                                       vec + k * BN * 4, stream))
+                                       vec + k * BN * 4, stream, bits))
             return rc;
     }
     return MAPF_OK;

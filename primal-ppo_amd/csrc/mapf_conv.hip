@@ -27,6 +27,7 @@
 
 #include "mapf.h"
 #include "mapf_common.h"
+#include "mapf_obs_bits.h"
 
 namespace mapf {
 namespace conv {
@@ -629,7 +630,10 @@ __device__ inline int div_small(int a, int b, float rb) {    // a / b for 0 <= a
     return q;
 }
 
-template <int COUT>
+// BITS (mapf_conv_first_bits): `in` is the packed observation (mapf_obs_bits.h: uint32 [nimg][WPA],
+// WPA = ceil(C * H * W / 32)); the staging loop writes fp16 1.0 (0x3C00) or 0 for bit k of the
+// image's block -- what the cast of the float 1.0 / 0.0 gives -- and everything after it is the same code.
+template <int COUT, bool BITS = false>
 __global__ __launch_bounds__(256) void conv_first_kernel(const float *__restrict__ in, const uint16_t *__restrict__ w,
                                                          const uint16_t *__restrict__ bias, uint16_t *__restrict__ out,
                                                          int M, int C, int H, int W, int nimg) {
@@ -666,6 +670,16 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const float *__restrict
     __syncthreads();
     const float *src = in + (size_t)img_lo * C * HW;
     const int count = n * C * HW;
+    if constexpr (BITS) {
+        const int CHW = C * HW, WPA = (CHW + 31) >> 5;
+        const float rCHW = 1.f / (float)CHW;
+        const uint32_t *bsrc = reinterpret_cast<const uint32_t *>(in) + (size_t)img_lo * WPA;
+        for (int e = t; e < count; e += 256) {
+            const int ic = div_small(e, HW, rHW), rem = e - ic * HW, y = div_small(rem, W, rW), x = rem - y * W;
+            const int il = div_small(e, CHW, rCHW);
+            Img[ic * PP + (y + 1) * PW + x + 1] = obs_bits_get(bsrc + (size_t)il * WPA, e - il * CHW) ? (uint16_t)0x3C00 : (uint16_t)0;
+        }
+    } else
     for (int e = t; e < count; e += 256) {
         const int ic = div_small(e, HW, rHW), rem = e - ic * HW, y = div_small(rem, W, rW), x = rem - y * W;
         Img[ic * PP + (y + 1) * PW + x + 1] = (uint16_t)f2h(src[e]);
@@ -790,8 +804,8 @@ int mapf_conv_select(int32_t impl) {
     return MAPF_OK;
 }
 
-int mapf_conv_first_f32(const float *x_nchw, const uint16_t *w, const uint16_t *bias, uint16_t *y, int64_t nimg,
-                        int32_t Cin, int32_t H, int32_t W, int32_t Cout, void *stream) {
+static int conv_first_launch(const float *x_nchw, const uint16_t *w, const uint16_t *bias, uint16_t *y, int64_t nimg,
+                             int32_t Cin, int32_t H, int32_t W, int32_t Cout, void *stream, bool bits) {
     if (!x_nchw || !w || !bias || !y) return MAPF_EINVAL;
     if (nimg < 1 || Cin < 1 || Cin > 7 || H < 1 || W < 1 || Cout != 128) return MAPF_EINVAL;
     const int64_t M64 = nimg * H * W;
@@ -802,9 +816,23 @@ int mapf_conv_first_f32(const float *x_nchw, const uint16_t *w, const uint16_t *
     const int64_t nmax = 127 / HW + 2;                 // images one 128-pixel tile can touch
     const size_t lds = (size_t)128 * 128 + (size_t)Cout * 128 + (size_t)(nmax * Cin * (H + 2) * (W + 2) * 2 + 3) / 4 * 4;
     if (lds > 64 * 1024) return MAPF_EINVAL;
+    if (bits)
+        hipLaunchKernelGGL((conv::conv_first_kernel<128, true>), dim3((M + 127) / 128), dim3(256), lds, (hipStream_t)stream,
+                           x_nchw, w, bias, y, M, (int)Cin, (int)H, (int)W, (int)nimg);
+    else
     hipLaunchKernelGGL(conv::conv_first_kernel<128>, dim3((M + 127) / 128), dim3(256), lds, (hipStream_t)stream, x_nchw,
                        w, bias, y, M, (int)Cin, (int)H, (int)W, (int)nimg);
     return hipGetLastError() == hipSuccess ? MAPF_OK : MAPF_EDEVICE;
+}
+
+int mapf_conv_first_f32(const float *x_nchw, const uint16_t *w, const uint16_t *bias, uint16_t *y, int64_t nimg,
+                        int32_t Cin, int32_t H, int32_t W, int32_t Cout, void *stream) {
+    return conv_first_launch(x_nchw, w, bias, y, nimg, Cin, H, W, Cout, stream, false);
+}
+
+int mapf_conv_first_bits(const uint32_t *bits, const uint16_t *w, const uint16_t *bias, uint16_t *y, int64_t nimg,
+                         int32_t Cin, int32_t H, int32_t W, int32_t Cout, void *stream) {
+    return conv_first_launch(reinterpret_cast<const float *>(bits), w, bias, y, nimg, Cin, H, W, Cout, stream, true);
 }
 
 }  // extern "C"

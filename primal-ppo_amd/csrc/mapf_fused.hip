@@ -37,7 +37,9 @@ __host__ __device__ inline bool fused_per_wave(const DevEnv &e) {
     return e.G == 8 && regmap_fits(e) && ((e.N * e.C * e.F * e.F) & 3) == 0;
 }
 
-template <int NP, bool HOST>
+// BITS: `obs` is the packed uint32 [B][N][WPA] buffer (mapf_obs_bits.h); the launch then has no
+// zero-band workgroups (nband = 0: launch_np), whose float4 stores would overrun it.
+template <int NP, bool HOST, bool BITS = false>
 __global__ __launch_bounds__(256) void step_observe_kernel(DevEnv e, int32_t *__restrict__ actions, StepOut out,
                                                            uint32_t flags, int slot, float *__restrict__ obs,
                                                            float *__restrict__ vec, int nsearch, int sslot, int nband) {
@@ -90,13 +92,13 @@ __global__ __launch_bounds__(256) void step_observe_kernel(DevEnv e, int32_t *__
         if (le < nenv) {
             const ObsGroup g = obs_wave_init(e, L, le, mreg);
             TL_STAMP(2);
-            obs_emit<false>(e, L, obs, vec, g, b0, nband > 0);
+            obs_emit<false, BITS ? OBS_BITS : OBS_PLAIN>(e, L, obs, vec, g, b0, nband > 0);
         }
     } else {
         obs_init(e, L, E, b0, nenv, mreg);
         __syncthreads();
         TL_STAMP(2);
-        obs_emit<false>(e, L, obs, vec, obs_workgroup(L, nenv), b0, nband > 0);
+        obs_emit<false, BITS ? OBS_BITS : OBS_PLAIN>(e, L, obs, vec, obs_workgroup(L, nenv), b0, nband > 0);
     }
     step_pairs_finish(e, dfr, slot);
     TL_STAMP(3);
@@ -168,9 +170,12 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy)
            (policy == ROLLOUT_TAPE ? 4 * (size_t)TAPE_K * 8 * 4 : (policy == ROLLOUT_DESCENT ? 4 * (size_t)8 * 4 : 0));
 }
 
-// NT: nontemporal observation stores -- for slot buffers (fresh HBM lines every step,
+// ST (OBS_*, mapf_observe.h): OBS_NT, nontemporal observation stores -- for slot buffers (fresh HBM lines every step,
 // measured faster); re-written [B]-leading buffers keep plain stores (their lines
 // stay cache-resident between steps, measured faster).
+// ST = OBS_BITS: ro.obs is the packed uint32 [T or 1][B][N][WPA] buffer (MAPF_SLOTS_OBS_BITS), slots
+// or in place alike (plain stores: the slices are partial lines L2 merges, like the step outputs');
+// never with BAND.
 // SUBS 4-env quarters per workgroup: SUBS = 4 puts all 16 waves of a CU in one workgroup, so
 // each can see how far the others are (pacing, below)
 // BAND: a slot-buffer launch with MAPF_SLOTS_BAND_CLEAN -- the wave leaves out the stores that lie
@@ -186,7 +191,7 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy)
 // rs.pi, picks (descent_action) and hands the action to the pair lanes through the wave's LDS row,
 // as the tape does (LDSACT); ro.actions receives the picks like the random draw's.  The five loads
 // are a plain per-step vector load: waited for behind the wave's observation stores.
-template <bool NT, int SUBS, bool BAND, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
+template <int ST, int SUBS, bool BAND, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_kernel(
 #if MAPF_ARGS_PTR      // experiment build: arguments through a device pointer (mapf_rollout_wide.hip)
     const RolloutArgs *__restrict__ args, int T) {
@@ -322,7 +327,11 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
                 band_mask = obs_band_skip_mask(E, MAPF_BAND_UNIT,
                                                (size_t)(R.obs + (s * BN + (size_t)(b0 + le) * E.N) * E.C * E.F * E.F),
                                                (int)(threadIdx.x & 63));
-            obs_emit<false, NT, BAND>(E, L, R.obs + s * BN * E.C * E.F * E.F, R.vec + s * BN * 4, g, b0, false, band_mask);
+            // a slot of the packed buffer is B * N * WPA words, not B * N * CFF floats
+            float *ob;
+            if constexpr (ST == OBS_BITS) ob = R.obs + s * BN * (size_t)obs_bits_words(E.C, E.F);
+            else ob = R.obs + s * BN * E.C * E.F * E.F;
+            obs_emit<false, ST, BAND>(E, L, ob, R.vec + s * BN * 4, g, b0, false, band_mask);
             step_pairs_search_inline(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs);
             if (pacing || fair) publish_count(prog + gw, (uint32_t)(t + 1));
         }
@@ -391,7 +400,8 @@ static bool rollout_band_form(const DevEnv &e, int slots) {
 }
 
 bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy) {
-    const bool band = rollout_band_form(e, slots);
+    const bool bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
+    const bool band = !bits && rollout_band_form(e, slots);      // packed zeros cost nothing to write
     slots &= 1;
     RolloutPlan p;
     if (!plan_rollout_random(e, slots, tu, p, policy)) {
@@ -400,6 +410,7 @@ bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, 
     }
     char band_tag[16] = "";
     if (band) std::snprintf(band_tag, sizeof band_tag, ",band%d", MAPF_BAND_UNIT);
+    if (bits) std::snprintf(band_tag, sizeof band_tag, ",bits");
     const int k = std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
                                 slots ? "true" : "false", p.subs, band_tag, rollout_policy_tag(policy), p.grid, 256 * p.subs,
                                 p.lds, p.subs > 1 ? p.fair : 0, p.subs > 1 ? p.slack : -1, p.remap);
@@ -415,7 +426,8 @@ bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, 
 // slots: the MAPF_SLOTS_* bits of mapf_rollout_random
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
                           int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy) {
-    const bool band = rollout_band_form(e, slots) && ((uintptr_t)obs & 15) == 0;     // whole float4s
+    const bool bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
+    const bool band = !bits && rollout_band_form(e, slots) && ((uintptr_t)obs & 15) == 0;     // whole float4s
     slots &= 1;
     RolloutPlan p;
     if (!plan_rollout_random(e, slots, tu, p, policy)) return ROLLOUT_NOT_COVERED;
@@ -434,6 +446,8 @@ int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOu
     (void)ring;
     return with_policy(policy, [&](auto pol) -> int {
         constexpr int POL = decltype(pol)::value;
+        if (bits)      // one instantiation for slots and in place (ro.slots is a run-time field)
+            return p.subs == 4 ? launch(rollout_random_kernel<OBS_BITS, 4, false, POL>) : launch(rollout_random_kernel<OBS_BITS, 1, false, POL>);
         if (band)
             return p.subs == 4 ? launch(rollout_random_kernel<true, 4, true, POL>) : launch(rollout_random_kernel<true, 1, true, POL>);
         if (p.subs == 4)
@@ -450,14 +464,15 @@ bool step_observe_fusable(const DevEnv &e) {
 
 template <int NP>
 static void launch_np(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t flags, int slot, float *obs,
-                      float *vec, int nsearch, int sslot, hipStream_t s) {
+                      float *vec, int nsearch, int sslot, hipStream_t s, bool bits) {
     constexpr int E = 256 / (NP * NP);
     const bool per_wave = NP == 8 && fused_per_wave(e);
     // zero-band workgroups: whole float4s only, so the step workgroups' slices
     // and the buffer must be 16-B aligned
     int z0, z1, nband = 0;
     const size_t slice = (size_t)E * e.N * e.C * e.F * e.F;
-    if (e.band_blocks > 0 && obs_zero_band(e, z0, z1) && (slice & 3) == 0 && ((uintptr_t)obs & 15) == 0)
+    // (never in a packed launch: the band workgroups store float4s)
+    if (!bits && e.band_blocks > 0 && obs_zero_band(e, z0, z1) && (slice & 3) == 0 && ((uintptr_t)obs & 15) == 0)
         nband = e.band_blocks;
     const int grid = (e.B + E - 1) / E + nsearch + nband;
     size_t lds = obs_lds_bytes(e, E, per_wave);
@@ -465,22 +480,30 @@ static void launch_np(const DevEnv &e, int32_t *actions, const StepOut &out, uin
     if (nsearch > 0) {
         const size_t sl = 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W);
         if (sl > lds) lds = sl;
+        if (bits)
+            hipLaunchKernelGGL((step_observe_kernel<NP, true, true>), dim3(grid), dim3(256), lds, s, e, actions, out,
+                               flags, slot, obs, vec, nsearch, sslot, nband);
+        else
         hipLaunchKernelGGL((step_observe_kernel<NP, true>), dim3(grid), dim3(256), lds, s, e, actions, out, flags,
                            slot, obs, vec, nsearch, sslot, nband);
     } else {
+        if (bits)
+            hipLaunchKernelGGL((step_observe_kernel<NP, false, true>), dim3(grid), dim3(256), lds, s, e, actions, out,
+                               flags, slot, obs, vec, 0, 0, nband);
+        else
         hipLaunchKernelGGL((step_observe_kernel<NP, false>), dim3(grid), dim3(256), lds, s, e, actions, out, flags,
                            slot, obs, vec, 0, 0, nband);
     }
 }
 
 void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t flags, int slot,
-                         float *obs, float *vec, int nsearch, int sslot, hipStream_t s) {
+                         float *obs, float *vec, int nsearch, int sslot, hipStream_t s, bool bits) {
     if (!observe_hosts_search(e)) nsearch = 0;
     switch (e.G) {
-        case 1: launch_np<1>(e, actions, out, flags, slot, obs, vec, nsearch, sslot, s); break;
-        case 2: launch_np<2>(e, actions, out, flags, slot, obs, vec, nsearch, sslot, s); break;
-        case 4: launch_np<4>(e, actions, out, flags, slot, obs, vec, nsearch, sslot, s); break;
-        default: launch_np<8>(e, actions, out, flags, slot, obs, vec, nsearch, sslot, s); break;
+        case 1: launch_np<1>(e, actions, out, flags, slot, obs, vec, nsearch, sslot, s, bits); break;
+        case 2: launch_np<2>(e, actions, out, flags, slot, obs, vec, nsearch, sslot, s, bits); break;
+        case 4: launch_np<4>(e, actions, out, flags, slot, obs, vec, nsearch, sslot, s, bits); break;
+        default: launch_np<8>(e, actions, out, flags, slot, obs, vec, nsearch, sslot, s, bits); break;
     }
 }
 

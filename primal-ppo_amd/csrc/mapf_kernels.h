@@ -77,7 +77,8 @@ void launch_bfs_export(const DevEnv &e, int16_t *dist, hipStream_t s);
 // plan every human's next path from the state (promote: buffer hcur^1 becomes current first)
 void launch_plan(const DevEnv &e, int promote, hipStream_t s);
 // observations; the first nsearch workgroups run the search work of `parity`
-void launch_observe(const DevEnv &e, float *obs, float *vec, int nsearch, int parity, hipStream_t s);
+// bits (here and in launch_step_observe): obs is the packed uint32 [B][N][WPA] buffer (mapf_obs_bits.h)
+void launch_observe(const DevEnv &e, float *obs, float *vec, int nsearch, int parity, hipStream_t s, bool bits = false);
 bool observe_hosts_search(const DevEnv &e);
 // after a concurrent search: rewrite the BFS channel of the agents in bfs_list[parity]
 void launch_bfs_fixup(const DevEnv &e, int parity, float *obs, hipStream_t s);
@@ -85,13 +86,15 @@ void launch_bfs_fixup(const DevEnv &e, int parity, float *obs, hipStream_t s);
 // workgroups run the search work of list slot sslot (the previous step's)
 bool step_observe_fusable(const DevEnv &e);
 void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t flags, int slot,
-                         float *obs, float *vec, int nsearch, int sslot, hipStream_t s);
+                         float *obs, float *vec, int nsearch, int sslot, hipStream_t s, bool bits = false);
 // T committed random-policy steps + observations in one launch (mapf_fused.hip): MAPF_OK;
 // ROLLOUT_NOT_COVERED (nothing launched) if the configuration is not covered; MAPF_ESTATE
 // (nothing launched) if a captured launch found no free argument slot (ArgRing)
 // (the kernel's form from the handle's tuning, mapf.h: mapf_tuning); describe_* write the
 // form launch_* would take as text (mapf_rollout_plan).  launch_/describe_rollout_random take
-// mapf_rollout_random's `slots` bits (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN), the wide ones 0 / 1.
+// mapf_rollout_random's `slots` bits (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN | MAPF_SLOTS_OBS_BITS), the
+// wide ones MAPF_SLOTS | MAPF_SLOTS_OBS_BITS.  With MAPF_SLOTS_OBS_BITS `obs` is the packed uint32
+// buffer, the kernels' OBS_BITS instantiations write it, and the plan's text carries ",bits".
 // policy: where the actions come from, the kernels' POL template parameter.
 //   ROLLOUT_RANDOM (mapf_rollout_random): the in-kernel Philox draw, written to `actions`.
 //   ROLLOUT_TAPE (mapf_rollout_actions): `actions` is the caller's [T][B][N] tape, read only, played

@@ -25,8 +25,14 @@
 //                  4 stream -> float4 stores (coalesced, 1 KiB per wave instruction)
 #pragma once
 #include "mapf_common.h"
+#include "mapf_obs_bits.h"
 
 namespace mapf {
+
+// How phase 4 of obs_emit writes the observation (a template argument: OBS_PLAIN and OBS_NT are
+// the former `bool NT`'s false and true).  OBS_BITS: `obs` is the packed uint32 [..][N][WPA] buffer
+// (mapf_obs_bits.h) instead of float [..][N][C][F][F].
+constexpr int OBS_PLAIN = 0, OBS_NT = 1, OBS_BITS = 2;
 
 // LDS carve-up of an observing workgroup (E envs).  per_env: every env has its
 // own word-aligned bit-stream (stride swe words) and its own copy of the map
@@ -231,8 +237,9 @@ __device__ inline void obs_zero_band_store(const DevEnv &e, float *__restrict__ 
 // that follows obs_init and the agents' staging.  skip_band: the zero band's
 // whole float4s were written by obs_zero_band_store in this launch.
 // BFSCH = false compiles the BFS channel (C = 7) out (the fused launch never
-// has it: step_observe_fusable).  NT: the table-driven store loop (L.lut) uses
-// nontemporal stores.  BAND: the one-wave table loop skips the stores of `band_mask`
+// has it: step_observe_fusable).  ST (OBS_*): OBS_NT, the table-driven store loop (L.lut) uses
+// nontemporal stores; OBS_BITS, phase 4 writes the packed words instead of floats (`obs` is then
+// the uint32 buffer; skip_band and band_mask are ignored: nothing else writes a packed buffer).  BAND: the one-wave table loop skips the stores of `band_mask`
 // (bit k = this lane's iteration k, obs_band_skip_mask); BAND = false compiles the test out.
 // The threads that observe a run of the workgroup's envs together: the whole
 // workgroup (workgroup barriers) or one wave observing its own env (per_env
@@ -275,7 +282,7 @@ __device__ inline ObsGroup obs_wave_init(const DevEnv &e, const ObsLds &L, int l
     return g;
 }
 
-template <bool BFSCH = true, bool NT = false, bool BAND = false>
+template <bool BFSCH = true, int ST = OBS_PLAIN, bool BAND = false>
 __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restrict__ obs, float *__restrict__ vec,
                                 const ObsGroup &G, int b0, bool skip_band = false, uint32_t band_mask = 0) {
     using namespace obsd;
@@ -432,6 +439,31 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
     if (G.diag == 2) return;
 #endif
 
+    // ---- phase 4, packed: the group's K * WPA words, agent-aligned out of the env-contiguous stream
+    // (obs_bits_word), stored coalesced -- a packed slice is WPA / CFF of the float one, so a
+    // float-sized write here would overrun the buffer 32 times: this branch never falls through ----
+    if constexpr (ST == OBS_BITS) {
+        const int WPA = obs_bits_words(C, F), nw = K * WPA;
+        uint32_t *dw = reinterpret_cast<uint32_t *>(obs) + (size_t)b0 * N * WPA;
+        if (((N * WPA) & 3) == 0 && ((uintptr_t)dw & 15) == 0) {     // every env's slice: whole, aligned uint4s
+            for (int q = tid; q < (nw >> 2); q += nt) {
+                int k = (4 * q) / WPA, w = 4 * q - k * WPA;
+                uint32_t v[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    v[j] = obs_bits_word(stream, CFF, k, w);
+                    if (++w == WPA) { w = 0; ++k; }
+                }
+                reinterpret_cast<uint4 *>(dw)[q] = make_uint4(v[0], v[1], v[2], v[3]);
+            }
+        } else {
+            for (int i = tid; i < nw; i += nt) {
+                const int k = i / WPA;
+                dw[i] = obs_bits_word(stream, CFF, k, i - k * WPA);
+            }
+        }
+        return;
+    }
     // ---- phase 4: bit-stream -> float stores ----
     const size_t total = (size_t)K * CFF;
     float *dst = obs + (size_t)b0 * N * CFF;
@@ -448,7 +480,7 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
             const float4 f = L.lut[__builtin_amdgcn_ubfe(*swp, sh, 4)];
             if (BAND && (band_mask & 1u)) {
                 // inside the clean zero band: nothing to store
-            } else if constexpr (NT) {   // streaming stores (rollout slot buffers: not re-read by this launch)
+            } else if constexpr (ST == OBS_NT) {   // streaming stores (rollout slot buffers: not re-read by this launch)
                 typedef float v4f __attribute__((ext_vector_type(4)));
 #if defined(MAPF_SLOT_STORE) && MAPF_SLOT_STORE == 1     // store-policy experiment: nt only (round 2's)
                 __builtin_nontemporal_store(v4f{f.x, f.y, f.z, f.w}, reinterpret_cast<v4f *>(dp));

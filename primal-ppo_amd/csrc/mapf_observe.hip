@@ -13,7 +13,8 @@ namespace mapf {
 // Only the narrow-row search (W <= 32, H <= 64: configs c1-c3) is hosted: its
 // register footprint matches the observation role's; wider grids search in
 // their own launch so the observation workgroups keep their occupancy.
-template <bool HOST>
+// BITS: `obs` is the packed uint32 [B][N][WPA] buffer (mapf_obs_bits.h).
+template <bool HOST, bool BITS = false>
 __global__ __launch_bounds__(256) void observe_kernel(DevEnv e, float *__restrict__ obs, float *__restrict__ vec,
                                                       int nsearch, int parity) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -42,7 +43,7 @@ __global__ __launch_bounds__(256) void observe_kernel(DevEnv e, float *__restric
     TL_STAMP(1);
     __syncthreads();
     TL_STAMP(2);
-    obs_emit(e, L, obs, vec, obs_workgroup(L, nenv), b0);
+    obs_emit<true, BITS ? OBS_BITS : OBS_PLAIN>(e, L, obs, vec, obs_workgroup(L, nenv), b0);
     TL_STAMP(3);
 }
 
@@ -83,16 +84,20 @@ size_t observe_lds(const DevEnv &e) { return ((obs_lds_bytes(e, e.obs_envs) + 15
 
 bool observe_hosts_search(const DevEnv &e) { return e.W <= 32 && e.H <= 64; }
 
-void launch_observe(const DevEnv &e, float *obs, float *vec, int nsearch, int parity, hipStream_t s) {
+// bits: obs is the packed buffer (the caller never follows a packed launch with launch_bfs_fixup,
+// which writes floats)
+void launch_observe(const DevEnv &e, float *obs, float *vec, int nsearch, int parity, hipStream_t s, bool bits) {
     if (!observe_hosts_search(e)) nsearch = 0;
     const int grid = (e.B + e.obs_envs - 1) / e.obs_envs + nsearch;
     size_t lds = observe_lds(e);
     if (nsearch > 0) {
         const size_t sl = 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W);
         if (sl > lds) lds = sl;
-        hipLaunchKernelGGL(observe_kernel<true>, dim3(grid), dim3(256), lds, s, e, obs, vec, nsearch, parity);
+        if (bits) hipLaunchKernelGGL((observe_kernel<true, true>), dim3(grid), dim3(256), lds, s, e, obs, vec, nsearch, parity);
+        else hipLaunchKernelGGL(observe_kernel<true>, dim3(grid), dim3(256), lds, s, e, obs, vec, nsearch, parity);
     } else {
-        hipLaunchKernelGGL(observe_kernel<false>, dim3(grid), dim3(256), lds, s, e, obs, vec, 0, parity);
+        if (bits) hipLaunchKernelGGL((observe_kernel<false, true>), dim3(grid), dim3(256), lds, s, e, obs, vec, 0, parity);
+        else hipLaunchKernelGGL(observe_kernel<false>, dim3(grid), dim3(256), lds, s, e, obs, vec, 0, parity);
     }
 }
 

@@ -190,7 +190,10 @@ __device__ inline void wide_plain_barrier() {
 // the picks like the random draw's.  The maps the step rebuilds are always searched by the stepping
 // wave itself, never by the observers (bfsobs is ignored: they run up to WIDE_SNAPS steps behind),
 // so every map the step reads was written by the reading wave or before the launch.
-template <class T, int RW, bool NT, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
+// ST (OBS_*, mapf_observe.h): plain or nontemporal float stores, or OBS_BITS: ro.obs is the packed
+// uint32 [T or 1][B][N][WPA] buffer (MAPF_SLOTS_OBS_BITS) and every observation written by the loop
+// -- the three-wave in-place form's last-step re-store included -- is the packed one.
+template <class T, int RW, int ST, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
 __device__ __attribute__((always_inline)) inline void rollout_wide_body(const DevEnv &e, int T_steps, const WideOut &ro) {
     constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -266,6 +269,7 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
     const StepSrc src{L.mapc, lcost, grid};   // obstacle tests, cost table, neighbour grid in LDS
     const WaveGroup g;                     // the env is the whole wave: exchanges by v_readlane
     const size_t BN = (size_t)e.B * e.N, CFF = (size_t)e.C * e.F * e.F;
+    const size_t OPA = ST == OBS_BITS ? (size_t)obs_bits_words(e.C, e.F) : CFF;   // buffer elements per agent
     // this lane's output elements as VGPR pointers (step_group<.., LANEPTR>): the nine output
     // bases and the actions base would otherwise hold 20 SGPRs through the loop -- spilled to
     // VGPR lanes and read back (v_readlane pairs) at every store.  Slot buffers advance them
@@ -389,7 +393,7 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
 #else
             const ObsGroup G{lane, 64, 0, 1, L.stream, L.mapc, true};
 #endif
-            obs_emit<true, NT>(e, Lt, ro.obs + s * BN * CFF, ro.vec + s * BN * 4, G, b, false);
+            obs_emit<true, ST>(e, Lt, ro.obs + s * BN * OPA, ro.vec + s * BN * 4, G, b, false);
             wide_sync();
             uint64_t bm = 0;
             uint32_t mygoal = 0;
@@ -433,16 +437,16 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
 #else
         const ObsGroup G{lane, 64, 0, 1, L.stream, L.mapc, true};
 #endif
-        obs_emit<true, NT>(e, Lt, ro.obs, ro.vec, G, b, false);
+        obs_emit<true, ST>(e, Lt, ro.obs, ro.vec, G, b, false);     // (packed in a packed launch)
     }
     if (stepper) step_regs_store(e, b, lane, rs);
     WSTAMP_END(b, role);
 }
 
-template <class T, int RW, bool NT, int POL>
+template <class T, int RW, int ST, int POL>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void rollout_wide_kernel(WIDE_PARAMS) {
     WIDE_BIND
-    rollout_wide_body<T, RW, NT, POL>(e, T_steps, ro);
+    rollout_wide_body<T, RW, ST, POL>(e, T_steps, ro);
 }
 
 // Three waves per env (c4): the stepper and two observers taking alternate steps.  With one
@@ -450,10 +454,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void r
 // SIMD issuing each step's 31 KiB of stores).  Three waves per SIMD need <= 168 VGPRs:
 // the arguments come through a device pointer (ArgRing), which also frees the ~450 SGPRs the
 // by-value arguments spilled to VGPR lanes (152 VGPRs, 129 SGPR spills, no scratch).
-template <class T, int RW, bool NT, int POL>
+template <class T, int RW, int ST, int POL>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void rollout_wide3_kernel(
     const WideArgs *__restrict__ args, int T_steps) {
-    rollout_wide_body<T, RW, NT, POL>(args->e, T_steps, args->ro);
+    rollout_wide_body<T, RW, ST, POL>(args->e, T_steps, args->ro);
 }
 
 // The three-wave form is not built for 128-bit rows spread over two lanes (maps wider than 64 cells):
@@ -470,6 +474,7 @@ static bool wide_fits(const DevEnv &e) { return wide_lds_bytes<T, RW>(e) <= 64 *
 // The launch form for this handle's tuning (mapf.h: mapf_tuning; the measured defaults below)
 struct WidePlan {
     bool nt = false;     // nontemporal observation stores
+    bool bits = false;   // packed observations (OBS_BITS; never nt: plain stores of partial lines, as the step outputs)
     WideOut r{};         // the form fields (no pointers)
     size_t lds = 0;
     int grid = 0, block = 0;
@@ -479,6 +484,8 @@ struct WidePlan {
 template <class T, int RW, int POL>
 static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     WidePlan p;
+    p.bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
+    slots &= 1;
     // persistent waves: every CU holds the same number of workgroups (the LDS request caps
     // them at ceil(B / CUs) per CU, 160 KiB of LDS per CU), or the fuller CUs pace each step
     const int ncu = device_cu_count();
@@ -489,11 +496,13 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     // 446 MB, measured 94 vs 124 us per step); smaller ones keep plain stores (c2, c4;
     // c4 in place, nt sc1: 6.27 -> 7.03 us per step)
     p.nt = tu.wide_nt >= 0 ? tu.wide_nt != 0 : (slots || (size_t)e.B * e.N * e.C * e.F * e.F * 4 > ((size_t)128 << 20));
-    const void *kern = p.nt ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, true, POL>)
+    if (p.bits) p.nt = false;
+    // (the packed kernels' own register counts decide their form, as each policy's do)
+    const void *kern = p.bits ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, OBS_BITS, POL>) : p.nt ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, true, POL>)
                             : reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, false, POL>);
     const void *kern3 = nullptr;
     if constexpr (wide3_form<T, RW>())
-        kern3 = p.nt ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, true, POL>)
+        kern3 = p.bits ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, OBS_BITS, POL>) : p.nt ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, true, POL>)
                      : reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, false, POL>);
     // two waves per env where every env's pair fits at once: the VGPR budget of a SIMD
     // (512 per lane) over the waves it must hold, 4 SIMDs per CU
@@ -563,7 +572,7 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
 template <class T, int RW, int POL>
 static int launch_wide_t(const DevEnv &e, int steps, const WideOut &ro, const mapf_tuning &tu, ArgRing &ring,
                          hipStream_t s) {
-    const WidePlan p = plan_wide_t<T, RW, POL>(e, ro.slots, tu);
+    const WidePlan p = plan_wide_t<T, RW, POL>(e, ro.slots, tu);     // ro.slots: MAPF_SLOTS | MAPF_SLOTS_OBS_BITS
     WideOut r = p.r;
     r.actions = ro.actions;
     r.out = ro.out;
@@ -573,12 +582,14 @@ static int launch_wide_t(const DevEnv &e, int steps, const WideOut &ro, const ma
         if (r.wpe == 3) {
             const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
             if (!args) return MAPF_ESTATE;
-            auto kern3 = p.nt ? rollout_wide3_kernel<T, RW, true, POL> : rollout_wide3_kernel<T, RW, false, POL>;
+            auto kern3 = p.bits ? rollout_wide3_kernel<T, RW, OBS_BITS, POL>
+                                : (p.nt ? rollout_wide3_kernel<T, RW, true, POL> : rollout_wide3_kernel<T, RW, false, POL>);
             hipLaunchKernelGGL(kern3, dim3(p.grid), dim3(p.block), p.lds, s, args, steps);
             return MAPF_OK;
         }
     }
-    auto kern = p.nt ? rollout_wide_kernel<T, RW, true, POL> : rollout_wide_kernel<T, RW, false, POL>;
+    auto kern = p.bits ? rollout_wide_kernel<T, RW, OBS_BITS, POL>
+                       : (p.nt ? rollout_wide_kernel<T, RW, true, POL> : rollout_wide_kernel<T, RW, false, POL>);
 #if MAPF_ARGS_PTR
     const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
     if (!args) return MAPF_ESTATE;
@@ -629,10 +640,10 @@ void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, ch
         using R = decltype(t);
         constexpr int RWV = decltype(rw)::value;
         const WidePlan p = with_policy(policy, [&](auto pol) { return plan_wide_t<R, RWV, decltype(pol)::value>(e, slots, tu); });
-        std::snprintf(buf, n, "%s<%s,%d,%s%s> grid=%d block=%d lds=%zu wpe=%d epw=%d grid_mode=%d overlap=%d slack=%d "
+        std::snprintf(buf, n, "%s<%s,%d,%s%s%s> grid=%d block=%d lds=%zu wpe=%d epw=%d grid_mode=%d overlap=%d slack=%d "
                               "fair=%d prio=%d bfsobs=%d pair=%d remap=%d",
                       p.r.wpe == 3 ? "rollout_wide3_kernel" : "rollout_wide_kernel", row_name<decltype(t)>(),
-                      (int)decltype(rw)::value, p.nt ? "true" : "false",
+                      (int)decltype(rw)::value, p.nt ? "true" : "false", p.bits ? ",bits" : "",
                       rollout_policy_tag(policy), p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
                       p.r.grid, p.r.overlap, p.r.slack, p.r.fair, p.r.prio, p.r.bfsobs, p.r.pair, p.r.xcd_remap);
         return 0;

@@ -34,7 +34,7 @@ class MapGenSpec(ctypes.Structure):
 
 
 MAPS_WAREHOUSE, MAPS_RANDOM = 0, 1
-SLOTS, SLOTS_BAND_CLEAN = 1, 2          # mapf_rollout_random's `slots` bits
+SLOTS, SLOTS_BAND_CLEAN, SLOTS_OBS_BITS = 1, 2, 4          # mapf_rollout_random's `slots` bits
 
 
 class StepOut(ctypes.Structure):
@@ -163,6 +163,14 @@ SIGNATURES = {
     "mapf_conv_nhwc_pool_f16": (ctypes.c_int, [P, P, P, P, I64, I32, I32, I32, I32, I32, I32, P]),
     "mapf_conv_first_f32": (ctypes.c_int, [P, P, P, P, I64, I32, I32, I32, I32, P]),
     "mapf_conv_select": (ctypes.c_int, [I32]),
+    # packed observations, one bit per cell (mapf.h: "Packed observations")
+    "mapf_obs_bits_words": (I32, [ctypes.POINTER(MapfConfig)]),
+    "mapf_observe_bits": (ctypes.c_int, [P, P, P, P]),
+    "mapf_step_observe_bits": (ctypes.c_int, [P, P, ctypes.POINTER(StepOut), P, P, P]),
+    "mapf_obs_pack_host": (ctypes.c_int, [P, I64, I32, I32, P]),
+    "mapf_obs_unpack_host": (ctypes.c_int, [P, I64, I32, I32, P]),
+    "mapf_unpack_obs": (ctypes.c_int, [P, P, I64, I32, I32, I32, P]),
+    "mapf_conv_first_bits": (ctypes.c_int, [P, P, P, P, I64, I32, I32, I32, I32, P]),
     "mapf_conv_nhwc_f16": (ctypes.c_int, [P, P, P, P, I64, I32, I32, I32, I32, I32, I32, I32, P]),
     "mapf_attention_f16": (ctypes.c_int, [P, P, P, P, I64, I32, I32, I64, I64, I64, I64, I32, I32, ctypes.c_float, P]),
     "mapf_attention_bwd_f16": (ctypes.c_int, [P, P, P, P, P, P, P, P, I64, I32, I32, I64, I64, I64, I64, I64, I64, I32,

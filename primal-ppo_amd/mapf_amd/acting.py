@@ -43,15 +43,24 @@ def forward_fused(net, obs, vector):
     activation, LayerNorm written straight as the fp16 the next linear reads, dropout
     + residual add, GELU + dropout, tokeniser + positional embedding + dropout in one
     pass.  Dropout masks come from the kernels' counter-hash stream (seeded from torch's
-    CPU generator), not from torch's."""
+    CPU generator), not from torch's.
+    obs: float [..., C, F, F], or the packed observation int32 [..., WPA] (one bit per cell): conv1
+    then reads the bits (mapf_conv_first_bits, bit-identical to conv1 on the unpacked floats)."""
     dev = obs.device
+    packed = obs.dtype == torch.int32
     seeds = iter(torch.randint(0, 2 ** 62, (16,), dtype=torch.int64).tolist())
     h16 = lambda t, view=None: half(net, t, view)  # noqa: E731
     lin = lambda m, x: lin16(net, m, x)  # noqa: E731
     cl = torch.channels_last
     with torch.autocast(device_type="cuda"):
         F_ = net.fov or obs.shape[-1]
-        x = obs.reshape(-1, net.num_channel, F_, F_)
+        if packed:
+            x = obs.reshape(-1, obs.shape[-1]).contiguous()          # [agents, WPA]
+            if not (net.own_conv and net.num_channel <= 7 and net.conv1.weight.shape[0] == 128):
+                from .env import unpack_obs                           # no packed reader: a float scratch tensor
+                x, packed = unpack_obs(x, net.num_channel, F_), False
+        else:
+            x = obs.reshape(-1, net.num_channel, F_, F_)
         v = vector.reshape(-1, NetParameters.VECTOR_LEN)
 
         def conv(x, m, pool=False):        # F.relu(conv(x)) (+ pool): bias and ReLU in the epilogue kernel
@@ -96,7 +105,11 @@ def forward_fused(net, obs, vector):
             call("mapf_nhwc_bias_relu", y, b, B_ * H_ * W_, C_)
             return y
 
-        if (net.own_conv and net.num_channel <= 7 and net.conv1.weight.shape[0] == 128 and
+        if packed:
+            x1 = torch.empty((x.shape[0], 128, F_, F_), dtype=torch.float16, device=dev, memory_format=cl)
+            call("mapf_conv_first_bits", x, h16(net.conv1.weight, "k64"), h16(net.conv1.bias), x1, x.shape[0],
+                 net.num_channel, F_, F_, 128)
+        elif (net.own_conv and net.num_channel <= 7 and net.conv1.weight.shape[0] == 128 and
                 x.dtype == torch.float32 and x.is_contiguous()):
             # conv1 from the fp32 NCHW observation: cast, im2col, MFMA, bias + ReLU in one launch
             x1 = torch.empty((x.shape[0], 128, F_, F_), dtype=torch.float16, device=dev, memory_format=cl)

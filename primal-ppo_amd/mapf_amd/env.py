@@ -66,6 +66,7 @@ class BatchedMapfGym:
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
         self.B, self.N, self.H, self.W = cfg.num_envs, cfg.num_agents, cfg.height, cfg.width
         self.F, self.C = cfg.fov, cfg.num_channel
+        self.obs_words = int(_lib.lib().mapf_obs_bits_words(ctypes.byref(cfg)))   # WPA: uint32 words per packed agent
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().mapf_create(ctypes.byref(cfg), self.device.index, ctypes.byref(h)))
@@ -124,45 +125,47 @@ class BatchedMapfGym:
         self._query_forms()
 
     @staticmethod
-    def _slot_bits(slots, band_clean):
+    def _slot_bits(slots, band_clean, obs_bits=False):
         """The `slots` argument of the mapf_rollout_* calls (MAPF_SLOTS_*, mapf.h)."""
-        return (_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0
+        return ((_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0) | \
+            (_lib.SLOTS_OBS_BITS if obs_bits else 0)
 
-    def _plan(self, fn, slots, band_clean):
+    def _plan(self, fn, slots, band_clean, obs_bits=False):
         """The text of one of the mapf_rollout_*plan calls."""
         buf = ctypes.create_string_buffer(512)
-        kind = fn(self.h, self._slot_bits(slots, band_clean), buf, 512)
+        kind = fn(self.h, self._slot_bits(slots, band_clean, obs_bits), buf, 512)
         if kind < 0:
             _lib.check(kind)
         return buf.value.decode()
 
-    def rollout_plan(self, slots=False, band_clean=False):
+    def rollout_plan(self, slots=False, band_clean=False, obs_bits=False):
         """The kernel (template instantiation + form) mapf_rollout_random launches now, as text
-        (band_clean: for a slots launch with MAPF_SLOTS_BAND_CLEAN)."""
-        return self._plan(_lib.lib().mapf_rollout_plan, slots, band_clean)
+        (band_clean: for a slots launch with MAPF_SLOTS_BAND_CLEAN; obs_bits: for a packed launch,
+        MAPF_SLOTS_OBS_BITS -- ",bits" inside the angle brackets; the same for the plans below)."""
+        return self._plan(_lib.lib().mapf_rollout_plan, slots, band_clean, obs_bits)
 
-    def rollout_kernel_name(self, slots=False):
+    def rollout_kernel_name(self, slots=False, obs_bits=False):
         """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,false>'."""
-        return self.rollout_plan(slots).split(" ")[0]
+        return self.rollout_plan(slots, obs_bits=obs_bits).split(" ")[0]
 
-    def rollout_actions_plan(self, slots=False, band_clean=False):
+    def rollout_actions_plan(self, slots=False, band_clean=False, obs_bits=False):
         """rollout_plan for rollout_actions (mapf_rollout_actions_plan): the same text with ",tape"
         inside the angle brackets, or "step_observe" where the call runs per-step launches."""
-        return self._plan(_lib.lib().mapf_rollout_actions_plan, slots, band_clean)
+        return self._plan(_lib.lib().mapf_rollout_actions_plan, slots, band_clean, obs_bits)
 
-    def rollout_actions_kernel_name(self, slots=False, band_clean=False):
+    def rollout_actions_kernel_name(self, slots=False, band_clean=False, obs_bits=False):
         """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,tape>'."""
-        return self.rollout_actions_plan(slots, band_clean).split(" ")[0]
+        return self.rollout_actions_plan(slots, band_clean, obs_bits).split(" ")[0]
 
-    def rollout_descent_plan(self, slots=False, band_clean=False):
+    def rollout_descent_plan(self, slots=False, band_clean=False, obs_bits=False):
         """rollout_plan for rollout_descent (mapf_rollout_descent_plan): the same text with ",descent"
         inside the angle brackets (the wide three-wave form with bfsobs=0), or
         "descent_actions+step_observe" where the call runs per-step launches."""
-        return self._plan(_lib.lib().mapf_rollout_descent_plan, slots, band_clean)
+        return self._plan(_lib.lib().mapf_rollout_descent_plan, slots, band_clean, obs_bits)
 
-    def rollout_descent_kernel_name(self, slots=False, band_clean=False):
+    def rollout_descent_kernel_name(self, slots=False, band_clean=False, obs_bits=False):
         """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,descent>'."""
-        return self.rollout_descent_plan(slots, band_clean).split(" ")[0]
+        return self.rollout_descent_plan(slots, band_clean, obs_bits).split(" ")[0]
 
     @staticmethod
     def _make_stepout(out):
@@ -302,6 +305,38 @@ class BatchedMapfGym:
         _lib.check(_lib.lib().mapf_observe(self.h, _ptr(obs), _ptr(vec), _stream(self.device)))
         return obs, vec
 
+    def _bits_buffer(self, bits, k=1):
+        """A packed observation buffer: int32 [k*B, N, WPA] elements (the default: this env's own
+        [B, N, WPA], allocated on first use)."""
+        if bits is None:
+            if getattr(self, "bits", None) is None:
+                self.bits = torch.zeros(self.B, self.N, self.obs_words, dtype=torch.int32, device=self.device)
+            bits = self.bits
+        return _check(bits, torch.int32, k * self.B * self.N * self.obs_words, self.device, "bits")
+
+    def observe_bits(self, bits=None, vec=None):
+        """observe() writing the packed observation (mapf_observe_bits): bits int32 [B, N, WPA]
+        (WPA = obs_words; one bit per cell, unpack_obs gives the floats back), vec [B, N, 4]."""
+        bits = self._bits_buffer(bits)
+        vec = self.vec if vec is None else vec
+        _check(vec, torch.float32, self.B * self.N * 4, self.device, "vec")
+        _lib.check(_lib.lib().mapf_observe_bits(self.h, _ptr(bits), _ptr(vec), _stream(self.device)))
+        return bits, vec
+
+    def step_observe_bits(self, actions=None, bits=None, vec=None, out=None):
+        """step_observe() writing the packed observation (mapf_step_observe_bits).
+        Returns (out, bits, vec)."""
+        if actions is None:
+            actions = self.actions
+        bits = self._bits_buffer(bits)
+        vec = self.vec if vec is None else vec
+        _check(actions, torch.int32, self.B * self.N, self.device, "actions")
+        _check(vec, torch.float32, self.B * self.N * 4, self.device, "vec")
+        so = self._stepout if out is None else self._make_stepout(self._check_out(out))
+        _lib.check(_lib.lib().mapf_step_observe_bits(self.h, _ptr(actions), ctypes.byref(so), _ptr(bits), _ptr(vec),
+                                                     _stream(self.device)))
+        return (self.out if out is None else out), bits, vec
+
     def step_observe(self, actions=None, obs=None, vec=None, random_policy=False, out=None):
         """Committed step + getAllObservations in one launch (mapf_step_observe): the same
         outputs as step() followed by observe().  random_policy: draw the actions on device
@@ -321,7 +356,8 @@ class BatchedMapfGym:
         _lib.check(fn(self.h, _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return (self.out if out is None else out), obs, vec
 
-    def rollout_random(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False):
+    def rollout_random(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False,
+                       obs_bits=False):
         """T x step_observe(random_policy=True) -- runner.py:64-100 with the uniform random
         policy, T times -- as ONE launch where mapf_rollout_random_fused (each wave owns an
         env and loops step -> observe -> its search work).  slots: step t writes slot t of
@@ -330,8 +366,10 @@ class BatchedMapfGym:
         band_clean (with slots): the caller's promise that the zero band of every slot of `obs`
         (channel 5 while use_hp is off) already holds zeros, e.g. from an earlier call on the same
         buffer without it; the launch then need not store it (MAPF_SLOTS_BAND_CLEAN, mapf.h).
+        obs_bits: `obs` is the packed observation buffer, int32 [T, B, N, WPA] (slots) or [B, N, WPA]
+        (default: this env's own), one bit per cell (MAPF_SLOTS_OBS_BITS; band_clean is then ignored).
         Returns (out, obs, vec)."""
-        if not slots and actions is None and obs is None and vec is None and out is None:
+        if not obs_bits and not slots and actions is None and obs is None and vec is None and out is None:
             # the default [B]-leading buffers (checked at construction): the call's arguments are
             # built once -- a 20-step rollout takes ~300 us on the GPU, so the host's ~8 us of
             # argument checks and ctypes wrapping per call were 2-3 % of it
@@ -343,8 +381,9 @@ class BatchedMapfGym:
             _, fn, h, so, pa, po, pv = fast
             _lib.check(fn(h, int(T), 0, pa, so, po, pv, _stream(self.device)))
             return self.out, self.obs, self.vec
-        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions)
-        _lib.check(_lib.lib().mapf_rollout_random(self.h, int(T), self._slot_bits(slots, band_clean), _ptr(actions),
+        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
+                                                           obs_bits=obs_bits)
+        _lib.check(_lib.lib().mapf_rollout_random(self.h, int(T), self._slot_bits(slots, band_clean, obs_bits), _ptr(actions),
                                                   ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
 
@@ -358,18 +397,21 @@ class BatchedMapfGym:
         _check(tape, torch.int32, tape.shape[0] * self.B * self.N, self.device, "tape")
         return int(tape.shape[0])
 
-    def _rollout_buffers(self, k, slots, obs, vec, out, actions=None, tape=None):
+    def _rollout_buffers(self, k, slots, obs, vec, out, actions=None, tape=None, obs_bits=False):
         """The buffers of a rollout call (k = T with slots, else 1), defaulted and checked in the order
         actions, obs, vec, out: (actions, so, out, obs, vec).  tape: a tape _check_tape has passed,
-        handed back in the actions' place."""
+        handed back in the actions' place.  obs_bits: obs is the packed int32 [k*B, N, WPA] buffer."""
         if tape is not None:
             actions = tape
         else:
             actions = self.actions if actions is None else actions
             _check(actions, torch.int32, k * self.B * self.N, self.device, "actions")
-        obs = self.obs if obs is None else obs
         vec = self.vec if vec is None else vec
-        _check(obs, torch.float32, k * self.B * self.N * self.C * self.F * self.F, self.device, "obs")
+        if obs_bits:
+            obs = self._bits_buffer(obs, k)
+        else:
+            obs = self.obs if obs is None else obs
+            _check(obs, torch.float32, k * self.B * self.N * self.C * self.F * self.F, self.device, "obs")
         _check(vec, torch.float32, k * self.B * self.N * 4, self.device, "vec")
         if out is None:
             if slots:
@@ -380,40 +422,43 @@ class BatchedMapfGym:
             _check(t, ref.dtype, k * ref.numel(), self.device, key)
         return actions, self._make_stepout(out), out, obs, vec
 
-    def rollout_actions(self, tape, slots=False, obs=None, vec=None, out=None, band_clean=False):
+    def rollout_actions(self, tape, slots=False, obs=None, vec=None, out=None, band_clean=False, obs_bits=False):
         """T x step_observe(tape[t]) -- the caller's policy, T = tape.shape[0] steps -- as ONE launch
         where rollout_fused (the rollout kernels' tape instantiations, rollout_actions_plan), else
         T per-step launches; identical results.  tape: int32 [T, B, N] on the device, read by the
         launch (not by this call), always [T]-leading; values outside 0..4 are counted as bad
-        actions and played as 0.  slots, obs, vec, out, band_clean: as rollout_random;
+        actions and played as 0.  slots, obs, vec, out, band_clean, obs_bits: as rollout_random;
         out["actions_fixed"] is what was executed and must not overlap the tape.
         Returns (out, obs, vec)."""
         T = self._check_tape(tape)
-        tape, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, tape=tape)
+        tape, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, tape=tape,
+                                                        obs_bits=obs_bits)
         if T == 0:          # nothing to play (an empty tensor has no address to hand over)
             return out, obs, vec
-        _lib.check(_lib.lib().mapf_rollout_actions(self.h, T, self._slot_bits(slots, band_clean), _ptr(tape),
+        _lib.check(_lib.lib().mapf_rollout_actions(self.h, T, self._slot_bits(slots, band_clean, obs_bits), _ptr(tape),
                                                    ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
 
-    def rollout_descent(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False):
+    def rollout_descent(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False,
+                        obs_bits=False):
         """T x (descent_actions, step_observe) -- every agent one step down its own BFS map, the
         heuristic baseline (mapf_rollout_descent; needs keep_bfs) -- as ONE launch where
         rollout_fused (the rollout kernels' descent instantiations, rollout_descent_plan), else T
         pairs of per-step launches; identical results.  `actions` receives the chosen actions;
-        slots, actions, obs, vec, out, band_clean: as rollout_random.  Returns (out, obs, vec)."""
+        slots, actions, obs, vec, out, band_clean, obs_bits: as rollout_random.  Returns (out, obs, vec)."""
         T = int(T)
         if T < 0:
             raise ValueError("T must be >= 0")
-        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions)
+        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
+                                                           obs_bits=obs_bits)
         if T == 0:          # nothing to play (an empty tensor has no address to hand over)
             return out, obs, vec
-        _lib.check(_lib.lib().mapf_rollout_descent(self.h, T, self._slot_bits(slots, band_clean), _ptr(actions),
+        _lib.check(_lib.lib().mapf_rollout_descent(self.h, T, self._slot_bits(slots, band_clean, obs_bits), _ptr(actions),
                                                    ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
 
     def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None, actions_in=None,
-                         policy="random"):
+                         policy="random", obs_bits=False):
         """rollout_random(T, slots, ...) prepared once: the buffers are checked and the C call's
         arguments built now, on the current stream; the returned callable issues the launch with
         no per-call host work beyond one ctypes call (a 20-step rollout is ~350 us on the GPU, the
@@ -432,7 +477,10 @@ class BatchedMapfGym:
 
         policy: "random" (the default) or "descent" -- the launcher then issues rollout_descent(T,
         slots, actions, ...) under the same band rule.  A policy other than "random" and
-        actions_in exclude each other."""
+        actions_in exclude each other.
+
+        obs_bits: `obs` is the packed int32 buffer (as rollout_random); every call stores every word
+        (the band rule does not apply)."""
         if policy not in ("random", "descent"):
             raise ValueError(f"policy: expected 'random' or 'descent', got {policy!r}")
         if policy != "random" and actions_in is not None:
@@ -440,10 +488,10 @@ class BatchedMapfGym:
         if actions_in is not None:
             self._check_tape(actions_in, int(T))
         actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
-                                                           tape=actions_in)
-        args = (self.h, int(T), self._slot_bits(slots, False), _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec),
-                _stream(self.device))
-        clean = args[:2] + (self._slot_bits(slots, True),) + args[3:]
+                                                           tape=actions_in, obs_bits=obs_bits)
+        args = (self.h, int(T), self._slot_bits(slots, False, obs_bits), _ptr(actions), ctypes.byref(so), _ptr(obs),
+                _ptr(vec), _stream(self.device))
+        clean = args[:2] + (self._slot_bits(slots, not obs_bits, obs_bits),) + args[3:]
         fn = (_lib.lib().mapf_rollout_actions if actions_in is not None else
               _lib.lib().mapf_rollout_descent if policy == "descent" else _lib.lib().mapf_rollout_random)
         keep = (so, actions, obs, vec, out)
@@ -552,6 +600,69 @@ class BatchedMapfGym:
                 keep[n] = a
                 setattr(s, n, a.ctypes.data)
         _lib.check(_lib.lib().mapf_set_state(self.h, ctypes.byref(s), _stream(self.device)))
+
+
+def obs_words(C, F):
+    """WPA: uint32 words of one agent's packed observation (ceil(C * F * F / 32))."""
+    return (int(C) * int(F) * int(F) + 31) // 32
+
+
+def is_packed_obs(obs, C, F):
+    """A packed observation: int32 with last dimension WPA (floats are never int32)."""
+    return isinstance(obs, torch.Tensor) and obs.dtype == torch.int32 and obs.dim() >= 1 and \
+        obs.shape[-1] == obs_words(C, F)
+
+
+def pack_obs(obs, C, F):
+    """Host form of the packed format (mapf_obs_pack_host, the function the kernels store with):
+    obs [..., C, F, F] float32 (a CPU tensor or array; non-zero packs as 1) -> int32 [..., WPA] on the CPU."""
+    o = torch.as_tensor(obs, dtype=torch.float32, device="cpu").contiguous()
+    C, F = int(C), int(F)
+    if o.dim() < 3 or tuple(o.shape[-3:]) != (C, F, F):
+        raise ValueError(f"pack_obs: shape {tuple(o.shape)}, expected [..., {C}, {F}, {F}]")
+    lead = tuple(o.shape[:-3])
+    n = o.numel() // (C * F * F)
+    bits = torch.zeros(lead + (obs_words(C, F),), dtype=torch.int32)
+    _lib.check(_lib.lib().mapf_obs_pack_host(_ptr(o), n, C, F, _ptr(bits)))
+    return bits
+
+
+def unpack_obs(bits, C, F, dtype=torch.float32, out=None):
+    """bits int32 [..., WPA] -> [..., C, F, F] of 0 / 1 in `dtype` (float32 or float16).  On the GPU one
+    HIP launch (mapf_unpack_obs; capturable, `out` may be any 4-byte aligned contiguous view); on the CPU
+    torch bit operations (unpack_obs_host is the library's own host form)."""
+    C, F = int(C), int(F)
+    W, CFF = obs_words(C, F), C * F * F
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int32 or bits.dim() < 1 or bits.shape[-1] != W:
+        raise ValueError(f"unpack_obs: expected an int32 tensor [..., {W}]")
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError("unpack_obs: dtype must be float32 or float16")
+    lead = tuple(bits.shape[:-1])
+    n = bits.numel() // W
+    if out is None:
+        out = torch.empty(lead + (C, F, F), dtype=dtype, device=bits.device)
+    _check(out, dtype, n * CFF, bits.device, "out")
+    if bits.device.type == "cpu":
+        sh = torch.arange(32, dtype=torch.int32)
+        b = ((bits.reshape(n, W, 1) >> sh) & 1).reshape(n, W * 32)[:, :CFF]
+        out.view(-1)[:] = b.reshape(-1).to(dtype)
+        return out
+    b = _check(bits, torch.int32, n * W, bits.device, "bits")
+    if out.data_ptr() % 4:
+        raise ValueError("unpack_obs: out must be 4-byte aligned")
+    _lib.check(_lib.lib().mapf_unpack_obs(_ptr(b), _ptr(out), n, C, F, int(dtype == torch.float16), _stream(bits.device)))
+    return out
+
+
+def unpack_obs_host(bits, C, F):
+    """Host form (mapf_obs_unpack_host): int32 [..., WPA] on the CPU -> float32 [..., C, F, F]."""
+    b = torch.as_tensor(bits, dtype=torch.int32, device="cpu").contiguous()
+    C, F = int(C), int(F)
+    if b.dim() < 1 or b.shape[-1] != obs_words(C, F):
+        raise ValueError(f"unpack_obs_host: expected int32 [..., {obs_words(C, F)}]")
+    out = torch.empty(tuple(b.shape[:-1]) + (C, F, F), dtype=torch.float32)
+    _lib.check(_lib.lib().mapf_obs_unpack_host(_ptr(b), b.numel() // b.shape[-1], C, F, _ptr(out)))
+    return out
 
 
 def gae(rewards, values, last_values, gamma=0.95, lam=0.95):

@@ -222,6 +222,9 @@ class Model:
         dev = self.device
         t = lambda x: (torch.from_numpy(x) if isinstance(x, np.ndarray) else x).to(dev)
         observation, vector = t(observation), t(vector)
+        if observation.dtype == torch.int32:       # packed (one bit per cell): the update reads floats
+            from .env import unpack_obs
+            observation = unpack_obs(observation.contiguous(), self.network.num_channel, self.network.fov)
         returns, old_v, cost_returns, old_cv = t(returns).float(), t(old_v).float(), t(cost_returns).float(), t(old_cv).float()
         action = t(action).long().unsqueeze(-1)
         old_ps, train_valid = t(old_ps).float(), t(train_valid).float()
@@ -355,17 +358,20 @@ class Model:
         if isinstance(rows, np.ndarray):
             rows = torch.from_numpy(rows)
         rows = rows.to(dev, non_blocking=True).contiguous()
-        buffers = (runner.obs[:T], runner.vec[:T], runner.returns, runner.cost_returns, runner.values,
+        packed = getattr(runner, "packed", False)      # DeviceRunner(obs_bits=True): packed rows, unpacked below
+        buffers = (runner.obs_bits[:T] if packed else runner.obs[:T], runner.vec[:T], runner.returns, runner.cost_returns, runner.values,
                    runner.cost_values, runner.actions, runner.ps, runner.train_valid)
         M = rows.numel()
         meta = lambda x, *tail: torch.empty((M,) + tuple(x.shape[2:]) + tail, device="meta")   # noqa: E731
         obs, vec, ret, _, _, _, act, ps, tv = buffers
-        upd = self._device_update(meta(obs), meta(vec), meta(ret), meta(ps), meta(tv), meta(act, 1))
+        C_, F_ = runner.env.C, runner.env.F
+        obs_meta = torch.empty((M, obs.shape[2], C_, F_, F_), device="meta") if packed else meta(obs)
+        upd = self._device_update(obs_meta, meta(vec), meta(ret), meta(ps), meta(tv), meta(act, 1))
         lam = self.lagrange.get_lagrangian_param()
         distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         if self.distributed_update is not None:
             distributed = bool(self.distributed_update) and dist.is_available() and dist.is_initialized()
-        upd.load_rows(buffers, T, B, rows, coef=self._loss_coef(lam), lam=lam)
+        upd.load_rows(buffers, T, B, rows, coef=self._loss_coef(lam), lam=lam, packed=(C_, F_) if packed else None)
         return self._run_device_update(upd, episode_cost, distributed)
 
     def _finish_update(self, all_loss, policy_loss, entropy, critic_loss, valid_loss, cost_critic_loss, cost_loss,
@@ -470,15 +476,25 @@ class _DeviceUpdate:
         h = torch.tensor(list(coef) + [lam, lam + 1.0], dtype=torch.float64).float()
         self.dyn.copy_(h.pin_memory() if torch.cuda.is_available() else h, non_blocking=True)
 
-    def load_rows(self, buffers, T, B, rows, coef, lam):
+    def load_rows(self, buffers, T, B, rows, coef, lam, packed=None):
         """load() straight from a rollout's t-major [T, B, ...] device buffers: buffers = (obs, vec,
         returns, cost returns, values, cost values, actions int64, ps, train_valid), rows = int64
         device tensor of env-major row ids in [0, B * T), one per minibatch row.  One gather launch
         (env.gather_rows) fills the nine static inputs; with the coefficients' copy that is two
-        launches per minibatch."""
-        from .env import gather_rows
-        gather_rows(buffers, T, B, rows, (self.obs, self.vec, self.ret, self.cret, self.v, self.cv, self.action,
+        launches per minibatch.  packed = (C, F): buffers[0] is the packed observation buffer (int32
+        [T, B, N, WPA]); its rows (N * WPA * 4 bytes each) are gathered into a staging tensor by the same
+        launch and unpacked into the static float input (env.unpack_obs: one more launch)."""
+        from .env import gather_rows, unpack_obs
+        obs_dst = self.obs
+        if packed is not None:
+            shape = (rows.numel(),) + tuple(buffers[0].shape[2:])
+            if getattr(self, "obs_stage", None) is None or tuple(self.obs_stage.shape) != shape:
+                self.obs_stage = torch.zeros(shape, dtype=torch.int32, device=self.obs.device)
+            obs_dst = self.obs_stage
+        gather_rows(buffers, T, B, rows, (obs_dst, self.vec, self.ret, self.cret, self.v, self.cv, self.action,
                                           self.old_ps, self.tv))
+        if packed is not None:
+            unpack_obs(self.obs_stage, packed[0], packed[1], out=self.obs)
         self._load_dyn(coef, lam)
 
     def _front(self, allreduce):

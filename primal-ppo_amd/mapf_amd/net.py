@@ -394,9 +394,18 @@ class SCRIMPNet(nn.Module):
     def forward(self, obs, vector, input_state=None):
         """Returns (policy, value, blocking, policy_sig, x, policy_logits, cost_value) like net.py:101-155.
         obs: [..., N, C, F, F] (any leading shape); the agent axis is num_agents (EnvParameters.N_AGENTS
-        when not given at construction).  Acting on the GPU (no grad): acting.forward_fused."""
+        when not given at construction).  Acting on the GPU (no grad): acting.forward_fused.
+        obs may be the packed observation (env.unpack_obs's input: int32 [..., N, WPA], one bit per
+        cell; the net must know its fov): the fused acting forward reads it directly
+        (mapf_conv_first_bits), every other path unpacks it into a scratch tensor first."""
+        packed = obs.dtype == torch.int32
+        if packed and not self.fov:
+            raise ValueError("a packed observation needs the network's fov (SCRIMPNet(fov=...))")
         if self.fused_acting and obs.is_cuda and not torch.is_grad_enabled() and self.cT == 512:
             return acting.forward_fused(self, obs, vector)
+        if packed:
+            from .env import unpack_obs
+            obs = unpack_obs(obs, self.num_channel, self.fov)
         if self.hip_train and obs.is_cuda and torch.is_grad_enabled() and not self._in_cast:
             # the same forward on fp16 copies of the conv / linear weights, made in one launch
             # (autocast would cast each weight on use and its ToCopyBackward each gradient)

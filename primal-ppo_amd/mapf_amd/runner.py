@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from .config import EnvParameters, NetParameters, TrainingParameters
-from .env import BatchedMapfGym, episode_sum, gae
+from .env import BatchedMapfGym, episode_sum, gae, unpack_obs
 
 
 class DeviceMaps:
@@ -186,6 +186,25 @@ class EnvMajorRows(_DeviceRows):
         return self.buf.transpose(0, 1).reshape(self.shape)
 
 
+class PackedObsRows(EnvMajorRows):
+    """EnvMajorRows over a PACKED observation buffer (int32 [T, B, N, WPA], one bit per cell): rows
+    look like the float observations ([B*T, N, C, F, F] float32); indexing gathers the packed rows
+    asked for and unpacks just those (env.unpack_obs), so a minibatch of floats exists only while
+    it is used."""
+
+    def __init__(self, buf, T, B, C, F):
+        super().__init__(buf, T, B)
+        self.C, self.F = C, F
+        self.shape = torch.Size((B * T, buf.shape[2], C, F, F))
+        self.dtype = torch.float32
+
+    def _gather(self, rows):
+        return unpack_obs(super()._gather(rows).contiguous(), self.C, self.F)
+
+    def materialize(self):
+        return unpack_obs(self.buf.transpose(0, 1).contiguous(), self.C, self.F).reshape(self.shape)
+
+
 class ZeroRows(_DeviceRows):
     """hiddenState rows: all zeros in the reference (runner.py:47-48, never read by the
     net), handed out as expanded zero views, never materialised."""
@@ -288,9 +307,14 @@ class DeviceRunner:
     host maps for env.reset_seeded, at the start of every run(), i.e. Runner.run's
     `env = MapfGym()` (runner.py:30: a NEW random-size warehouse and new agents/human
     every rollout) -- e.g. reference_maps(env).  None: the envs continue from where the
-    previous rollout left them (lifelong)."""
+    previous rollout left them (lifelong).
+    obs_bits: keep the rollout's observations packed, one bit per cell -- `obs_bits` int32
+    [T + 1, B, N, WPA] instead of the float `obs` [T + 1, B, N, C, F, F] (32 times smaller); the env
+    writes them (observe_bits / step_observe_bits), the policy reads them (Model.step / value accept
+    packed input), batch().observations unpacks the rows it is indexed with, and Model.train_rows
+    gathers packed rows and unpacks them into the update's static input."""
 
-    def __init__(self, env: BatchedMapfGym, model, n_steps=None, seed=0, new_maps=None):
+    def __init__(self, env: BatchedMapfGym, model, n_steps=None, seed=0, new_maps=None, obs_bits=False):
         self.env = env
         self.model = model
         self.T = TrainingParameters.N_STEPS if n_steps is None else n_steps
@@ -301,7 +325,11 @@ class DeviceRunner:
         dev = env.device
         T = self.T
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)
-        self.obs = z(T + 1, B, N, C, F, F)          # obs[T] = bootstrap observation
+        self.packed = bool(obs_bits)
+        if self.packed:                             # obs_bits[T] = bootstrap observation
+            self.obs, self.obs_bits = None, z(T + 1, B, N, env.obs_words, dt=torch.int32)
+        else:
+            self.obs, self.obs_bits = z(T + 1, B, N, C, F, F), None          # obs[T] = bootstrap observation
         self.vec = z(T + 1, B, N, NetParameters.VECTOR_LEN)
         self.rewards = z(T, B, N)
         self.values = z(T, B, N)
@@ -328,19 +356,21 @@ class DeviceRunner:
             self.new_maps.reset(env, self.rollouts, (self.seed << 20) + self.rollouts + 1)
         elif self.new_maps is not None:
             env.reset_seeded(self.new_maps(self.rollouts), seed=(self.seed << 20) + self.rollouts + 1)
-        env.observe(self.obs[0], self.vec[0])
+        ob = self.obs_bits if self.packed else self.obs
+        (env.observe_bits if self.packed else env.observe)(ob[0], self.vec[0])
+        step_observe = env.step_observe_bits if self.packed else env.step_observe
         for t in range(T):
-            a, ps, v, _, _, cv = self.model.step(self.obs[t], self.vec[t], None, seed=self.seed,
+            a, ps, v, _, _, cv = self.model.step(ob[t], self.vec[t], None, seed=self.seed,
                                                  step=self.rollouts * T + t, actions_out=self.actions[t],
                                                  actions32_out=self.actions32)
             self.ps[t].copy_(ps.reshape(self.ps[t].shape))
             self.values[t].copy_(v.reshape(self.values[t].shape))
             self.cost_values[t].copy_(cv.reshape(self.cost_values[t].shape))
-            env.step_observe(self.actions32, self.obs[t + 1], self.vec[t + 1], out={
+            step_observe(self.actions32, ob[t + 1], self.vec[t + 1], out={
                 "reward_total": self.rewards[t],            # reward + GOAL_REWARD (runner.py:89-91)
                 "cost": self.cost_rewards[t], "train_valid": self.train_valid[t], "status": self.status[t],
                 "goals_reached": self.goals[t], "constraints": self.constraints[t], "shadow_goals": self.shadow[t]})
-        last_v, last_cv = self.model.value(self.obs[T], self.vec[T], None)
+        last_v, last_cv = self.model.value(ob[T], self.vec[T], None)
         self.last_v = last_v.reshape(self.values[0].shape).contiguous()
         self.last_cv = last_cv.reshape(self.values[0].shape).contiguous()
         self.adv, self.returns = gae(self.rewards, self.values, self.last_v,
@@ -354,8 +384,10 @@ class DeviceRunner:
         """BatchValues over this rollout's buffers, rows env-major (EnvMajorRows)."""
         T, B, N = self.T, self.env.B, self.env.N
         rows = lambda x: EnvMajorRows(x, T, B)   # noqa: E731
+        obs_rows = (PackedObsRows(self.obs_bits[:T], T, B, self.env.C, self.env.F) if self.packed
+                    else rows(self.obs[:T]))
         return BatchValues(
-            observations=rows(self.obs[:T]), vectors=rows(self.vec[:T]), rewards=rows(self.rewards),
+            observations=obs_rows, vectors=rows(self.vec[:T]), rewards=rows(self.rewards),
             values=rows(self.values), ps=rows(self.ps), actions=rows(self.actions),
             hiddenState=ZeroRows(T * B, (2, N, NetParameters.NET_SIZE), self.env.device),
             returns=rows(self.returns), trainValid=rows(self.train_valid), costRewards=rows(self.cost_rewards),
