@@ -240,6 +240,13 @@ int mapf_rollout_random_fused(const mapf_env *env);
  * address: pass the address of the very slot and env asked about, obs + ((t * B + b) * N*C*F*F) * 4.
  * Returns the float4s per env, or a negative error. */
 int mapf_obs_band_skip(const mapf_config *cfg, int32_t unit, uint64_t byte_offset, uint8_t *skip, int32_t n);
+/* The pacing gate of the grouped pair-lane kernel (roll_group with roll_slack >= 0), computed on the
+ * host (no device call) by the function the kernel runs.  The `live` waves of a workgroup (1..64, those
+ * that own an env) share a ring of 16 counters; a wave that has finished step t adds 1 to counter
+ * t % 16.  A wave may start step t (>= 0) once *word has reached *target.  Returns 1 with the two set,
+ * 0 if step t needs no wait at all (t <= slack), or a negative error.  slack >= 0; more than 14 is
+ * paced as 14. */
+int mapf_pace_gate(int32_t t, int32_t slack, int32_t live, int32_t *word, uint32_t *target);
 
 /* Launch tuning of one handle: which form of a kernel the launches take (the measured choices
  * of DESIGN.md §4 / §9).  The reference has no counterpart (its env is Python); these fields
@@ -252,7 +259,8 @@ typedef struct mapf_tuning {
     int32_t roll_occ;        /* workgroups per CU the LDS request admits: 0 = ceil(grid / CUs), 1..16      */
     int32_t roll_group;      /* the 16 waves of a CU in one workgroup: -1 auto (slots, or roll_fair > 0), 0, 1 */
     int32_t roll_fair;       /* grouped, issue priority by progress: -1 auto (4 in place, 0 slots), 0 off, n */
-    int32_t roll_slack;      /* grouped, roll_fair 0: waves paced within n steps of the slowest (< 0 off)  */
+    int32_t roll_slack;      /* grouped, roll_fair 0: waves paced within n steps of the slowest (< 0 off;
+                                more than 14 paces as 14: mapf_pace_gate)                                 */
     /* one-wave-per-env rollout (mapf_rollout_random_fused == 2: up to 64 agents, per-env maps, C = 7) */
     int32_t wide_nt;         /* nontemporal observation stores: -1 auto (slots, or a [B] buffer > 128 MB), 0, 1 */
     int32_t wide_pipe;       /* 1 auto: a stepping and observing waves per env where they fit; 0 one wave   */

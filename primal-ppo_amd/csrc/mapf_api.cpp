@@ -20,7 +20,8 @@
 
 #include "mapf.h"
 #include "mapf_kernels.h"
-#include "mapf_observe.h"   // obs_band_skip, evaluated on the host by mapf_obs_band_skip
+#include "mapf_group.h"     // pace_gate, evaluated on the host by mapf_pace_gate
+#include "mapf_observe.h"  // obs_band_skip, evaluated on the host by mapf_obs_band_skip
 
 using namespace mapf;
 
@@ -367,6 +368,17 @@ int mapf_obs_band_skip(const mapf_config *cfg, int32_t unit, uint64_t byte_offse
     const int nq = env_floats >> 2;
     for (int q = 0; q < nq && q < n; ++q) skip[q] = obs_band_skip(d, unit, (size_t)byte_offset, q) ? 1 : 0;
     return nq;
+}
+
+int mapf_pace_gate(int32_t t, int32_t slack, int32_t live, int32_t *word, uint32_t *target) {
+    if (!word || !target) return fail(MAPF_EINVAL, "null argument");
+    if (t < 0 || slack < 0 || live < 1 || live > 64) return fail(MAPF_EINVAL, "t, slack or live out of range");
+    int w = 0;
+    uint32_t v = 0;
+    if (!pace_gate(t, slack, live, w, v)) return 0;
+    *word = w;
+    *target = v;
+    return 1;
 }
 
 // s waits for the deferred aux-stream searches: every one (all), or those due before the

@@ -217,13 +217,16 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
     const int nenv = min(E, e.B - b0);
     const int le = qt >> 6;
     char *qsm = smem + (SUBS > 1 ? (size_t)sub * ro.sub_lds : 0);
-    uint32_t *prog = reinterpret_cast<uint32_t *>(smem + (size_t)SUBS * ro.sub_lds);   // [4 * SUBS] steps done
+    // [4 * SUBS] words: fair, each wave's steps done; paced, the ring of arrival counters (mapf_group.h)
+    uint32_t *prog = reinterpret_cast<uint32_t *>(smem + (size_t)SUBS * ro.sub_lds);
+    static_assert(SUBS == 1 || 4 * SUBS == PACE_RING, "the pacing ring takes the place of the per-wave counters");
     const int gw = sub * E + le;                       // the wave's index in the workgroup
     ObsLds L = obs_layout(e, E, qsm, true);
     float4 *lut = reinterpret_cast<float4 *>(qsm + rollout_obs_lds(e) - 256);
     if (qt < 16) lut[qt] = make_float4((float)(qt & 1), (float)((qt >> 1) & 1), (float)((qt >> 2) & 1), (float)(qt >> 3));
-    // envs past B never count: they start at the top
-    if (SUBS > 1 && (int)threadIdx.x < 4 * SUBS) prog[threadIdx.x] = wg * SUBS * E + (int)threadIdx.x < e.B ? 0u : 0xFFFFFFFFu;
+    // envs past B never count: fair, they start at the top; paced, they are not among the live waves
+    if (SUBS > 1 && (int)threadIdx.x < 4 * SUBS)
+        prog[threadIdx.x] = ro.fair <= 0 || wg * SUBS * E + (int)threadIdx.x < e.B ? 0u : 0xFFFFFFFFu;
     __syncthreads();
     L.lut = lut;
     const size_t swl = srch::wave_lds<uint32_t, 1>(e.H, e.W);
@@ -253,12 +256,18 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
                                            (int)(threadIdx.x & 63));
     }
     RSTAMP_BEGIN();
-    const bool pacing = SUBS > 1 && ro.slack >= 0 && le < nenv;
+    // (a scalar condition: pace_wait's s_sleep ignores EXEC)
+    const bool pacing = SUBS > 1 && ro.slack >= 0 && __builtin_amdgcn_readfirstlane(le) < nenv;
     const bool fair = SUBS > 1 && ro.fair > 0 && le < nenv;
+    const int live = min(max(e.B - wg * SUBS * E, 0), 4 * SUBS);     // the workgroup's waves that own an env
     for (int t = 0; t < T; ++t) {
         const DevEnv &E = e;
         const RolloutOut &R = ro;
-        if (pacing && t > R.slack) wait_group_min(prog, 4 * SUBS, (uint32_t)(t - R.slack));
+        if (pacing) {
+            RSTAMP_WAIT0();
+            pace_wait(prog, t, R.slack, live);
+            RSTAMP_WAIT1();
+        }
         if (fair) {
             if ((uint32_t)t > group_min(prog, 4 * SUBS) + (uint32_t)R.fair) __builtin_amdgcn_s_setprio(0);
             else __builtin_amdgcn_s_setprio(2);
@@ -333,7 +342,8 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
             else ob = R.obs + s * BN * E.C * E.F * E.F;
             obs_emit<false, ST, BAND>(E, L, ob, R.vec + s * BN * 4, g, b0, false, band_mask);
             step_pairs_search_inline(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs);
-            if (pacing || fair) publish_count(prog + gw, (uint32_t)(t + 1));
+            if (pacing) pace_arrive(prog, t);
+            else if (fair) publish_count(prog + gw, (uint32_t)(t + 1));
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();

@@ -118,7 +118,7 @@ __device__ inline uint32_t group_min(const uint32_t *p, int n) {
     for (int o = 1; o < n; o <<= 1) x = min(x, (uint32_t)__shfl_xor((int)x, o));
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
 }
-// pacing: wait until each of the n (<= 64) counters p[0..n) has reached v
+// pacing, the one-wave-per-env kernels' form: wait until each of the n (<= 64) counters p[0..n) has reached v
 __device__ inline void wait_group_min(const uint32_t *p, int n, uint32_t v) {
     const int l = lane_id();
     for (;;) {
@@ -129,6 +129,46 @@ __device__ inline void wait_group_min(const uint32_t *p, int n, uint32_t v) {
         if ((uint32_t)__builtin_amdgcn_readfirstlane((int)x) >= v) return;
         __builtin_amdgcn_s_sleep(1);
     }
+}
+
+// Pacing of the pair-lane rollout's CU group by arrival counters: a ring of PACE_RING monotonic
+// LDS words, never reset within a launch.  A wave that has finished step t adds 1 to word
+// t % PACE_RING, so after lap k of the ring (steps < (k + 1) * PACE_RING) a word holds
+// live * (k + 1), `live` the waves of the workgroup that own an env.  "Every live wave has finished
+// step u" is then ONE word reaching ONE value: the waiting wave polls with a uniform ds_read and
+// a scalar compare, no cross-lane reduction.  A wave may start step t once every live wave has
+// finished step t - slack - 1.  No arrival of step u + PACE_RING can reach u's word before u's
+// target is met -- starting that step needs everyone past u + PACE_RING - slack - 1 >= u + 1 --
+// which is why slack is capped at PACE_RING - 2 (a tighter pace than asked for, same results).
+constexpr int PACE_RING = 16;
+__host__ __device__ inline int pace_word(int t) { return t & (PACE_RING - 1); }
+// The gate of step t: false when the step needs no wait at all (t <= slack), else the ring word to
+// read and the value it must have reached.  The one predicate of the protocol, host and device
+// (mapf_pace_gate, tests/test_pace_protocol.py).
+__host__ __device__ inline bool pace_gate(int t, int slack, int live, int &word, uint32_t &target) {
+    const int u = t - (slack < PACE_RING - 2 ? slack : PACE_RING - 2) - 1;
+    if (u < 0) return false;
+    word = pace_word(u);
+    target = (uint32_t)live * (uint32_t)(u / PACE_RING + 1);
+    return true;
+}
+// arrive: every earlier LDS write of the wave lands before the word moves
+__device__ inline void pace_arrive(uint32_t *ring, int t) {
+    __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
+    if (lane_id() == 0)
+        __hip_atomic_fetch_add(as_lds(ring + pace_word(t)), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// The first check is in line: a wave that need not wait pays one read.  A wave that must wait sleeps
+// 256 cycles between polls (a step is ~36,000): the waiting waves are the older ones of their SIMD,
+// whose instructions issue ahead of the trailing wave's that the group is waiting for.  Sleeps of
+// 256 and 1,024 cycles measured the same, 64 cycles 0.5 % slower; running the paced waves at
+// priority 1 or 2 and the waiting ones at 0 changed nothing and is not done.
+// Call it wave-uniformly: s_sleep ignores EXEC (lds_count's result is scalar, so are the branches).
+__device__ inline void pace_wait(const uint32_t *ring, int t, int slack, int live) {
+    int w;
+    uint32_t target;
+    if (!pace_gate(t, slack, live, w, target)) return;
+    while (lds_count(ring + w) < target) __builtin_amdgcn_s_sleep(4);
 }
 
 }  // namespace mapf

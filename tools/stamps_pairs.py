@@ -2,7 +2,11 @@
 wave's start / end and its CU, SIMD and wave slot -- does the launch wait for some waves?
 
     make -C primal-ppo_amd/csrc stamps
-    MAPF_LIB=primal-ppo_amd/lib/libmapf_stamps.so python tools/stamps_pairs.py"""
+    MAPF_LIB=primal-ppo_amd/lib/libmapf_stamps.so python tools/stamps_pairs.py
+
+SLOTS=1: into [T]-slot buffers; BAND=1 with it: the timed launch declares the zero band clean, as a
+launcher's later calls do.  The grouped, paced form also reports the time each wave spent in its
+pacing waits, by wave slot of the SIMD."""
 import os
 import sys
 
@@ -34,6 +38,8 @@ if slots:
               obs=torch.empty(T, B, N, C, F, F, device=dev), vec=torch.empty(T, B, N, 4, device=dev),
               out={k: torch.empty((T,) + tuple(v.shape), dtype=v.dtype, device=dev) for k, v in env.out.items()})
 env.rollout_random(T, **kw)
+if slots and int(os.environ.get("BAND", "0")):      # the timed launch declares the zero band clean (the launcher's later calls)
+    kw["band_clean"] = True
 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 a.record()
 env.rollout_random(T, **kw)
@@ -57,7 +63,17 @@ print(" per XCD wall us/step: " + "  ".join(
     f"{x}:{(en[xcc == x].max() - st[xcc == x].min()) / 100.0 / T:.2f}" for x in xs))
 print(" per wave slot: " + "  ".join(f"{k}:{dur[slot == k].mean():.2f}({(slot == k).sum()})" for k in range(16)
                                     if (slot == k).any()))
-print(" per SIMD: " + "  ".join(f"{k}:{dur[simd == k].mean():.2f}" for k in range(4)))
+# pacing waits (RSTAMP_WAIT0 / RSTAMP_WAIT1 around the grouped kernel's wait): each wave's share of its own
+# loop spent waiting, and what is left -- the wave's step phase -- by wave slot (the youngest slot is the highest)
+wait = r[:, 3].astype(np.float64) / 100.0 / T
+ks = [k for k in range(16) if (slot == k).any()]
+print(" wait us/step per wave slot: " + "  ".join(f"{k}:{wait[slot == k].mean():.2f}" for k in ks))
+print(" wait share of the step per wave slot: " + "  ".join(
+    f"{k}:{100 * wait[slot == k].sum() / dur[slot == k].sum():.1f}%" for k in ks))
+print(" step phase (loop - wait) us/step per wave slot: " + "  ".join(f"{k}:{(dur - wait)[slot == k].mean():.2f}" for k in ks))
+print(f" all waves: wait {100 * wait.sum() / dur.sum():.1f}% of the step; youngest slot {ks[-1]}: step phase "
+      f"{(dur - wait)[slot == ks[-1]].mean():.2f} us, wait {wait[slot == ks[-1]].mean():.2f} us")
+print(" per SIMD: " +"  ".join(f"{k}:{dur[simd == k].mean():.2f}" for k in range(4)))
 u, inv, cnt = np.unique(cukey, return_inverse=True, return_counts=True)
 cu_mean = np.bincount(inv, dur) / cnt
 cu_max = np.array([dur[inv == k].max() for k in range(len(u))])

@@ -17,6 +17,9 @@
 // agent block) with the skipped lanes predicated off; "compact 16": the 1,216 float4s that remain
 // at the 16-B unit as 19 full instructions.  Each form with plain and with `sc1 nt` stores; the
 // full pattern is measured in the same run (min / median / max of the repeats).
+// "aligned": odd envs (slice base % 128 = 64) use lane l -> float4 l - 4 + 64k instead, lanes whose
+// index falls outside [0, 1452) off, so that every instruction of every env starts on a 128-B line
+// (same bytes, same 64-B pieces, same 23 instructions; fewer lines touched per instruction).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,15 +60,16 @@ __device__ inline void store4(v4f *p, v4f v) {
 
 // masks: [2][64] per-lane skip bits (bit k = float4 lane + 64k) by env parity, or null (full);
 // cidx: [COMPACT_ITERS][64] float4 indices of the compacted form, or null
+// aligned: odd envs shift their lane mapping down by 4 float4s (the masks are then built for that mapping)
 template <bool NT>
 __global__ __launch_bounds__(1024) void slice_stores(float *buf, int steps, size_t step_floats, const uint32_t *masks,
-                                                     const int *cidx) {
-    const int lane = threadIdx.x & 63;
+                                                     const int *cidx, int aligned) {
     const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint32_t mask = masks ? masks[(w & 1) * 64 + lane] : 0u;      // env offset % 128 = 64 * (w & 1)
+    const int lane = (int)(threadIdx.x & 63) - (aligned ? 4 * (w & 1) : 0);
+    const uint32_t mask = masks ? masks[(w & 1) * 64 + (threadIdx.x & 63)] : 0u;      // env offset % 128 = 64 * (w & 1)
     int idx[COMPACT_ITERS];
 #pragma unroll
-    for (int k = 0; k < COMPACT_ITERS; ++k) idx[k] = cidx ? cidx[k * 64 + lane] : 0;
+    for (int k = 0; k < COMPACT_ITERS; ++k) idx[k] = cidx ? cidx[k * 64 + (threadIdx.x & 63)] : 0;
     for (int s = 0; s < steps; ++s) {
         v4f *base = reinterpret_cast<v4f *>(buf + (size_t)s * step_floats + (size_t)w * (ENV_BYTES / 4));
         const v4f v = {(float)s, 1.f, 0.f, 1.f};
@@ -77,7 +81,7 @@ __global__ __launch_bounds__(1024) void slice_stores(float *buf, int steps, size
 #pragma unroll
             for (int k = 0; k < ITERS; ++k) {
                 const int q = lane + 64 * k;
-                if (q < ENV_Q && !(m & 1u)) store4<NT>(base + q, v);
+                if (q >= 0 && q < ENV_Q && !(m & 1u)) store4<NT>(base + q, v);      // never outside the env's slice
                 m >>= 1;
             }
         }
@@ -102,10 +106,10 @@ static int slice_mode(int steps, int reps) {
     if (hipMalloc(&buf, step_floats * 4 * steps) != hipSuccess) return 1;
     uint32_t *dmask = nullptr;
     int *dcidx = nullptr;
-    if (hipMalloc(&dmask, 3 * 2 * 64 * 4) != hipSuccess || hipMalloc(&dcidx, COMPACT_ITERS * 64 * 4) != hipSuccess) return 1;
+    if (hipMalloc(&dmask, 4 * 2 * 64 * 4) != hipSuccess || hipMalloc(&dcidx, COMPACT_ITERS * 64 * 4) != hipSuccess) return 1;
     const int units[3] = {16, 64, 128};
     double skipped[3] = {0, 0, 0};
-    std::vector<uint32_t> hm(3 * 2 * 64, 0u);
+    std::vector<uint32_t> hm(4 * 2 * 64, 0u);      // [3]: the 64-B unit in the aligned lane mapping
     for (int u = 0; u < 3; ++u)
         for (int par = 0; par < 2; ++par)
             for (int q = 0; q < ENV_Q; ++q)
@@ -113,6 +117,12 @@ static int slice_mode(int steps, int reps) {
                     hm[(u * 2 + par) * 64 + (q & 63)] |= 1u << (q >> 6);
                     skipped[u] += 16.0 / 2;
                 }
+    for (int par = 0; par < 2; ++par)
+        for (int q = 0; q < ENV_Q; ++q)
+            if (skip_q(64, 64 * par, q)) {
+                const int j = q + 4 * par;              // lane (j & 63) holds float4 q at iteration j >> 6
+                hm[(3 * 2 + par) * 64 + (j & 63)] |= 1u << (j >> 6);
+            }
     std::vector<int> hc;
     for (int q = 0; q < ENV_Q; ++q)
         if (!skip_q(16, 0, q)) hc.push_back(q);
@@ -122,12 +132,12 @@ static int slice_mode(int steps, int reps) {
     hipEvent_t a, b;
     hipEventCreate(&a);
     hipEventCreate(&b);
-    auto run = [&](const char *name, bool nt, const uint32_t *masks, const int *cidx, double bytes_env) {
+    auto run = [&](const char *name, bool nt, const uint32_t *masks, const int *cidx, double bytes_env, int aligned = 0) {
         std::vector<float> us;
         for (int r = 0; r <= reps; ++r) {
             hipEventRecord(a);
-            if (nt) hipLaunchKernelGGL(slice_stores<true>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx);
-            else hipLaunchKernelGGL(slice_stores<false>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx);
+            if (nt) hipLaunchKernelGGL(slice_stores<true>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx, aligned);
+            else hipLaunchKernelGGL(slice_stores<false>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx, aligned);
             hipEventRecord(b);
             hipEventSynchronize(b);
             float ms;
@@ -147,6 +157,9 @@ static int slice_mode(int steps, int reps) {
             run(name, nt, dmask + u * 2 * 64, nullptr, ENV_BYTES - skipped[u]);
         }
         run("compact 16 (19 instr)", nt, nullptr, dcidx, ENV_BYTES - skipped[0]);
+        run("full, aligned", nt, nullptr, nullptr, ENV_BYTES, 1);
+        run("skip 64-B, aligned", nt, dmask + 3 * 2 * 64, nullptr, ENV_BYTES - skipped[1], 1);
+        run("skip 64-B units (again)", nt, dmask + 1 * 2 * 64, nullptr, ENV_BYTES - skipped[1]);
         run("full (again)", nt, nullptr, nullptr, ENV_BYTES);
     }
     hipFree(buf);
