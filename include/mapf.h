@@ -368,6 +368,65 @@ int mapf_descent_actions(mapf_env *env, int32_t *actions, void *stream);
  * forever -- or 0 if S is empty.  Bits other than 1..4 are ignored. */
 int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent);
 
+/* The PIBT policy (priority inheritance with backtracking, Okumura et al.): a one-step planner over
+ * the agents' BFS maps that never produces a vertex or a swap conflict -- the collision-free
+ * baseline a learned policy is compared with.  Per env at clock t (steps since reset), agents
+ * i = 0..N-1 at cells p_i with goals g_i, D_i = agent.bfsMap, the human at h with next cell hn:
+ *   1. Age (policy-owned state of the handle, never touched by a step): per agent a packed goal
+ *      `seen` and a clock `since`.  At a pick, if since_i > t or seen_i != g_i then seen_i = g_i,
+ *      since_i = t; age_i = t - since_i.  Every reset, and mapf_set_state, sets since to 0xFFFFFFFF
+ *      (mapf_get_state does not export the ages: a restored state starts them anew).  Picking
+ *      twice at the same clock changes nothing the second time.
+ *   2. Candidates: action a in 0..4 with target q = p_i + d(a) is admitted iff the step would give
+ *      it neither status -1 nor -2: q inside the map and free, q != hn, and not (p_i == hn and
+ *      q == h).  C_i = the admitted actions in ascending mapf_pibt_key(D_i[q], a, t, i).
+ *   3. Solve: next_i undecided for all agents; in the order (age descending, index ascending)
+ *      every still undecided agent calls PIBT(i, none):
+ *        PIBT(i, parent): for (a, q) in C_i:
+ *            skip if some k has next_k == q (vertex), or parent != none and q == p_parent (swap);
+ *            next_i = q, act_i = a;
+ *            if an undecided agent k != i stands on q and PIBT(k, i) fails: continue (backtrack);
+ *            return true
+ *          next_i = p_i, act_i = 0, return false      (a failed pick: stay, whatever the human does)
+ *      Every agent is entered at most once and at most 5 N candidates are examined; the loops stop
+ *      after 6 N examinations (never reached), every agent without a final pick then stays.
+ * Under these actions no agent gets status -1 or -3, status -2 only goes to an agent whose pick
+ * failed while it stands on hn, and in an env-step without a -2 actions_fixed equals the actions.
+ *
+ * mapf_pibt_actions: the policy's actions for the current state, DEVICE int32 [B][N] (requires
+ * keep_bfs, MAPF_ESTATE otherwise; flushes pending search work first, as mapf_observe does);
+ * updates the age arrays. */
+int mapf_pibt_actions(mapf_env *env, int32_t *actions, void *stream);
+/* The candidate key, on the host (the function the kernels run): cost * 8 + rank, cost = dist if
+ * dist >= 0 else 0x7FFF, rank = 0 for action 0 and 1 + ((action - 1 - k0) & 3) for the moves,
+ * k0 = (clock + agent) & 3 (the descent policy's rotation).  The five keys of one agent are
+ * distinct. */
+int mapf_pibt_key(int32_t dist, int32_t action, uint32_t clock, int32_t agent);
+/* Step 3 on the host, plain sequential code with no device call: pos [n][2] (row, col), key [n][5]
+ * (negative = not admitted), age [n] -> actions [n]; bit i of *failed = agent i's pick failed.
+ * MAPF_EINVAL on n outside 1..64, a null pointer or two agents on one cell. */
+int mapf_pibt_host(int32_t n, const int32_t *pos, const int32_t *key, const uint32_t *age, int32_t *actions,
+                   uint64_t *failed);
+/* The PIBT policy, T steps: T x (mapf_pibt_actions, mapf_step_observe) -- identical results -- as
+ * ONE launch where mapf_rollout_random_fused says so: the rollout kernels' PIBT forms pick in the
+ * stepping wave from the tiled maps (pair-lane kernel: the solve over the agents' head lanes, the
+ * picks handed over through the descent policy's LDS row), the age pair in registers across the
+ * steps and written back at the end, so the handle's arrays are exactly as T per-step picks
+ * leave them.  actions_out receives the chosen actions; slots (MAPF_SLOTS, MAPF_SLOTS_BAND_CLEAN,
+ * MAPF_SLOTS_OBS_BITS) / actions_out / out / obs / vec, the capture rules and T = 0: as
+ * mapf_rollout_descent.  Requires keep_bfs (MAPF_ESTATE otherwise). */
+int mapf_rollout_pibt(mapf_env *env, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
+                      float *obs, float *vec, void *stream);
+/* mapf_rollout_plan for mapf_rollout_pibt: the same text with ",pibt" inside the angle brackets,
+ * e.g. "rollout_random_kernel<true,4,pibt>", "rollout_wide3_kernel<u64,1,true,pibt>" (the pair-lane
+ * text ends as descent's, the wide three-wave form says bfsobs=0).  The text names the FORM: the
+ * PIBT kernels take the age arrays as well, so the symbols a profiler shows are
+ * rollout_random_pibt_kernel<ST,SUBS,BAND>, rollout_wide_pibt_kernel<T,RW,ST> and
+ * rollout_wide3_pibt_kernel<T,RW,ST> with the same leading template arguments (ST: 0 plain stores,
+ * 1 nontemporal -- printed "false" / "true" --, 2 packed bits).  Kind 0:
+ * "pibt_actions+step_observe", the per-step launches. */
+int mapf_rollout_pibt_plan(const mapf_env *env, int32_t slots, char *buf, int32_t n);
+
 /* Copy agent.bfsMap for every agent: DEVICE int16 [B][N][H][W] (requires keep_bfs). */
 int mapf_bfs(mapf_env *env, int16_t *dist, void *stream);
 

@@ -71,6 +71,9 @@ struct mapf_env {
     int def_next = 0;
     mapf_tuning tune;                      // launch forms (mapf_set_tuning); never the process environment
     ArgRing args;                          // device-resident argument blocks of the persistent kernels
+    // the PIBT policy's age arrays [B][N] (mapf.h: mapf_pibt_actions): the packed goal last seen and
+    // the clock it was first seen at; policy-owned, no step kernel touches them
+    uint32_t *pibt_seen = nullptr, *pibt_since = nullptr;
     template <class T>
     int alloc(T *&p, size_t n) {
         void *q = nullptr;
@@ -240,6 +243,7 @@ int mapf_create(const mapf_config *cfg, int device, mapf_env **out) {
     rc |= e->alloc(e->maps8, nmaps * (size_t)d.H * d.W);
     rc |= e->alloc(cl, cost_lut.size());
     rc |= e->alloc(e->args.base, (ARG_SLOTS + ARG_CAPTURE_SLOTS) * ARG_SLOT_BYTES);
+    rc |= e->alloc(e->pibt_seen, BN); rc |= e->alloc(e->pibt_since, BN);
     if (rc) {
         std::string m = g_err;
         mapf_destroy(e);
@@ -250,7 +254,9 @@ int mapf_create(const mapf_config *cfg, int device, mapf_env **out) {
     d.cost_lut = cl;
     if (hipMemcpy(cl, cost_lut.data(), cost_lut.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(d.counters, 0, C_NUM * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(d.prof, 0, PROF_WORDS * sizeof(unsigned long long)) != hipSuccess) {
+        hipMemset(d.prof, 0, PROF_WORDS * sizeof(unsigned long long)) != hipSuccess ||
+        hipMemset(e->pibt_seen, 0, BN * sizeof(uint32_t)) != hipSuccess ||
+        hipMemset(e->pibt_since, 0xFF, BN * sizeof(uint32_t)) != hipSuccess) {
         mapf_destroy(e);
         return fail(MAPF_EDEVICE, "initial upload failed");
     }
@@ -298,7 +304,9 @@ static int rollout_plan_impl(const mapf_env *e, int policy, int32_t slots, char 
         describe_rollout_wide(e->d, slots & (MAPF_SLOTS | MAPF_SLOTS_OBS_BITS), e->tune, buf, (size_t)n, policy);
         return 2;
     }
-    std::snprintf(buf, (size_t)n, "%s%s", policy == ROLLOUT_DESCENT ? "descent_actions+step_observe" : "step_observe",
+    std::snprintf(buf, (size_t)n, "%s%s",
+                  policy == ROLLOUT_PIBT ? "pibt_actions+step_observe"
+                                         : (policy == ROLLOUT_DESCENT ? "descent_actions+step_observe" : "step_observe"),
                   (slots & MAPF_SLOTS_OBS_BITS) ? "_bits" : "");
     return 0;
 }
@@ -312,8 +320,78 @@ int mapf_rollout_descent_plan(const mapf_env *e, int32_t slots, char *buf, int32
     return rollout_plan_impl(e, ROLLOUT_DESCENT, slots, buf, n);
 }
 
+int mapf_rollout_pibt_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
+    return rollout_plan_impl(e, ROLLOUT_PIBT, slots, buf, n);
+}
+
 int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent) {
     return descent_pick(descent_mask, clock, (int)agent);
+}
+
+int mapf_pibt_key(int32_t dist, int32_t action, uint32_t clock, int32_t agent) {
+    return pibt_key((int)dist, (int)action, clock, (int)agent);
+}
+
+// Step 3 of the policy (mapf.h: mapf_pibt_actions), sequentially: the recursion as the chain of
+// parent indices the wave form keeps one per lane (mapf_pibt.h: pibt_solve_wave).
+int mapf_pibt_host(int32_t n, const int32_t *pos, const int32_t *key, const uint32_t *age, int32_t *actions,
+                   uint64_t *failed) {
+    if (!pos || !key || !age || !actions || !failed) return fail(MAPF_EINVAL, "null argument");
+    if (n < 1 || n > 64) return fail(MAPF_EINVAL, "n must be in 1..64");
+    constexpr long NONE = -(1L << 40);
+    long cell[64], nxt[64];
+    int cand[64][NA], ncand[64], cur[64], par[64], order[64];
+    for (int i = 0; i < n; ++i) {
+        cell[i] = (long)pos[2 * i] * (1L << 20) + pos[2 * i + 1];
+        for (int j = 0; j < i; ++j)
+            if (cell[j] == cell[i]) return fail(MAPF_EINVAL, "two agents on one cell");
+        ncand[i] = 0;
+        for (int a = 0; a < NA; ++a)
+            if (key[i * NA + a] >= 0) cand[i][ncand[i]++] = a;
+        std::stable_sort(cand[i], cand[i] + ncand[i], [&](int a, int b) { return key[i * NA + a] < key[i * NA + b]; });
+        nxt[i] = NONE; cur[i] = 0; par[i] = -1; order[i] = i; actions[i] = 0;
+    }
+    std::stable_sort(order, order + n, [&](int a, int b) { return age[a] > age[b]; });
+    auto target = [&](int i, int a) { return cell[i] + (long)dr(a) * (1L << 20) + dc(a); };
+    uint64_t fl = 0;
+    int iters = 0;
+    bool bail = false;
+    for (int k = 0; k < n && !bail; ++k) {
+        int i = order[k];
+        if (nxt[i] != NONE) continue;
+        for (;;) {
+            bool pushed = false, ok = false;
+            const int pa = par[i];
+            while (cur[i] < ncand[i]) {
+                const int a = cand[i][cur[i]++];
+                if (++iters > 6 * n) { bail = true; break; }
+                const long q = target(i, a);
+                bool taken = false;
+                for (int j = 0; j < n; ++j) taken |= nxt[j] == q;
+                if (taken) continue;                              // vertex
+                if (pa >= 0 && q == cell[pa]) continue;           // swap with the agent that pushed
+                nxt[i] = q; actions[i] = a;
+                int child = -1;
+                for (int j = 0; j < n; ++j)
+                    if (cell[j] == q && nxt[j] == NONE) child = j;
+                if (child >= 0) { par[child] = i; i = child; pushed = true; }
+                else ok = true;
+                break;
+            }
+            if (bail) {
+                for (; i >= 0; i = par[i]) { nxt[i] = cell[i]; actions[i] = 0; }
+                break;
+            }
+            if (pushed) continue;
+            if (ok) break;
+            nxt[i] = cell[i]; actions[i] = 0;                     // failed pick: stay
+            fl |= 1ull << i;
+            if (pa < 0) break;
+            i = pa;                                               // backtrack
+        }
+    }
+    *failed = fl;
+    return MAPF_OK;
 }
 
 int32_t mapf_obs_bits_words(const mapf_config *cfg) {
@@ -409,6 +487,8 @@ static int join_deferred(mapf_env *e, hipStream_t s, bool all) {
 static int reset_searches(mapf_env *e, hipStream_t s) {
     const DevEnv &d = e->d;
     e->nsteps = 0;
+    // the PIBT ages restart with the episode: no goal seen yet
+    HIPCHK(hipMemsetAsync(e->pibt_since, 0xFF, (size_t)d.B * d.N * sizeof(uint32_t), s));
     launch_search(d, 0, 1, s);     // first human paths (buffer 0) + every agent's BFS map
     launch_plan(d, 1, s);          // promote them, plan each human's next path
     launch_search(d, 0, 2, s);     // ... and search it (buffer 1)
@@ -736,14 +816,14 @@ static mapf_step_out step_out_slot(const mapf_step_out &out, size_t k, const Dev
     return ot;
 }
 
-// mapf_rollout_random / _actions / _descent (`name`, for the error text).  policy (ROLLOUT_*) says
+// mapf_rollout_random / _actions / _descent / _pibt (`name`, for the error text).  policy (ROLLOUT_*) says
 // where the actions come from; `actions` is the caller's tape with ROLLOUT_TAPE (read only), else out.
 static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, int32_t slots, int32_t *actions,
                         const mapf_step_out *out, float *obs, float *vec, void *stream) {
     if (!e || !actions || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
     if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
     if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN | MAPF_SLOTS_OBS_BITS)) return fail(MAPF_EINVAL, "slots: unknown bits");
-    if (policy == ROLLOUT_DESCENT && !e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
+    if ((policy == ROLLOUT_DESCENT || policy == ROLLOUT_PIBT) && !e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
     if (!e->ready) return fail(MAPF_ESTATE, std::string(name) + " before mapf_reset");
     // with MAPF_SLOTS_OBS_BITS `obs` is the packed buffer (uint32 behind the float pointer): a slot is
     // B * N * WPA words, and every launch below is told so
@@ -763,10 +843,11 @@ static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, in
         // the wide kernels take what the pair-lane one does not (a tape or descent whose LDS rows pass its
         // LDS included); they store everything (MAPF_SLOTS_BAND_CLEAN ignored)
         const StepOut o = step_out_of(out);
-        int rc = launch_rollout_random(e->d, T, actions, o, obs, vec, slots, e->tune, e->args, s, policy);
+        int rc = launch_rollout_random(e->d, T, actions, o, obs, vec, slots, e->tune, e->args, s, policy, e->pibt_seen,
+                                       e->pibt_since);
         if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
             rc = launch_rollout_wide(e->d, T, actions, o, obs, vec, slots & (MAPF_SLOTS | MAPF_SLOTS_OBS_BITS), e->tune,
-                                     e->args, s, policy);
+                                     e->args, s, policy, e->pibt_seen, e->pibt_since);
         if (rc == MAPF_ESTATE)
             return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
                                      "(16 per handle, ArgRing; mapf_release_captures frees them)");
@@ -787,6 +868,8 @@ static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, in
         int32_t *act = actions + (policy == ROLLOUT_TAPE ? (size_t)t : k) * BN;
         if (policy == ROLLOUT_DESCENT) {
             if (int rc = mapf_descent_actions(e, act, stream)) return rc;
+        } else if (policy == ROLLOUT_PIBT) {
+            if (int rc = mapf_pibt_actions(e, act, stream)) return rc;
         }
         if (int rc = step_observe_impl(e, act, out ? &ot : nullptr, policy == ROLLOUT_RANDOM ? 2u : 0u, obs + k * obs_t,
                                        vec + k * BN * 4, stream, bits))
@@ -821,6 +904,22 @@ int mapf_descent_actions(mapf_env *e, int32_t *actions, void *stream) {
 int mapf_rollout_descent(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
                          float *obs, float *vec, void *stream) {
     return rollout_impl(e, ROLLOUT_DESCENT, "mapf_rollout_descent", T, slots, actions_out, out, obs, vec, stream);
+}
+
+int mapf_pibt_actions(mapf_env *e, int32_t *actions, void *stream) {
+    if (!e || !actions) return fail(MAPF_EINVAL, "null argument");
+    if (!e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
+    if (!e->ready) return fail(MAPF_ESTATE, "mapf_pibt_actions before mapf_reset");
+    HIPCHK(hipSetDevice(e->device));
+    if (int rc = flush_search(e, (hipStream_t)stream)) return rc;      // the maps of the last step's new goals
+    launch_pibt_actions(e->d, actions, e->pibt_seen, e->pibt_since, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+int mapf_rollout_pibt(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
+                      float *obs, float *vec, void *stream) {
+    return rollout_impl(e, ROLLOUT_PIBT, "mapf_rollout_pibt", T, slots, actions_out, out, obs, vec, stream);
 }
 
 int mapf_release_captures(mapf_env *e) {
@@ -1005,6 +1104,8 @@ int mapf_set_state(mapf_env *e, const mapf_state *h, void *stream) {
     const size_t BN = (size_t)d.B * d.N;
     if (int rc = flush_search(e, s)) return rc;
     HIPCHK(hipStreamSynchronize(s));
+    // a restored state is another point of another episode: the PIBT ages restart (mapf.h)
+    HIPCHK(hipMemsetAsync(e->pibt_since, 0xFF, BN * sizeof(uint32_t), s));
     if (h->pos) {
         std::vector<uint32_t> v(BN);
         for (size_t k = 0; k < BN; ++k) {

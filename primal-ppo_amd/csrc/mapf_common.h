@@ -222,6 +222,18 @@ __device__ inline int descent_action(const DevEnv &e, const int16_t *D, uint32_t
     return descent_pick(mask, clock, agent);
 }
 
+// The PIBT policy's candidate key (mapf_pibt_actions, mapf_rollout_pibt; include/mapf.h: mapf_pibt_key
+// has the specification): cost * 8 + rank, cost = the agent's BFS distance at the target cell
+// (0x7FFF where it is negative: unreachable), rank 0 for staying and descent's rotation
+// 1 + ((a - 1 - k0) & 3), k0 = (clock + agent) & 3, among the moves.  The keys of one agent's five
+// actions are distinct.  The one function every kernel and the host export run.
+__host__ __device__ inline int pibt_key(int dist, int action, uint32_t clock, int agent) {
+    const uint32_t k0 = (clock + (uint32_t)agent) & 3u;
+    const int cost = dist >= 0 ? dist : 0x7FFF;
+    const int rank = action == 0 ? 0 : 1 + (int)(((uint32_t)(action - 1) - k0) & 3u);
+    return cost * 8 + rank;
+}
+
 __device__ inline uint32_t *human_path(const DevEnv &e, int b, int buf) {
     return e.hpath + ((size_t)b * 2 + buf) * e.Lmax;
 }

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "mapf_step_pairs.h"
+#include "mapf_pibt.h"
 #include "mapf_search.h"
 
 namespace mapf {
@@ -154,6 +155,16 @@ struct RolloutArgs {
     DevEnv e;
     RolloutOut ro;
 };
+// PIBT launches: the same with the handle's age arrays [B][N].  Types and a kernel of their own
+// (rollout_random_pibt_kernel), so that the other policies' kernels keep their names, their
+// argument layout and with it their register allocation (as mapf_rollout_wide.hip's).
+struct RolloutOutPibt : RolloutOut {
+    uint32_t *pibt_seen, *pibt_since;
+};
+struct RolloutArgsPibt {
+    DevEnv e;
+    RolloutOutPibt ro;
+};
 
 __host__ __device__ inline bool rollout_fusable(const DevEnv &e) {
     return e.G == 8 && e.human_mode != 2 && e.goal_mode == 1 && e.C < 7 && !e.force_agent_lanes && fused_per_wave(e) &&
@@ -163,11 +174,12 @@ __host__ __device__ inline bool rollout_fusable(const DevEnv &e) {
 // LDS of a rollout workgroup: observation layout | nibble table | 4 search scratch | 4 path copies
 __host__ __device__ inline size_t rollout_obs_lds(const DevEnv &e) { return ((obs_lds_bytes(e, 4, true) + 15) & ~(size_t)15) + 256; }
 // TAPE: + 4 waves x TAPE_K staged rows (8 slots each, N <= 8) of the action tape (below)
-// DESCENT: + 4 waves x one row of 8 picked actions (the hand-over to the step's pair lanes)
+// DESCENT, PIBT: + 4 waves x one row of 8 picked actions (the hand-over to the step's pair lanes)
 constexpr int TAPE_K = 32;
 __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy) {
     return rollout_obs_lds(e) + 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W) + 4 * (size_t)e.Lmax * 4 +
-           (policy == ROLLOUT_TAPE ? 4 * (size_t)TAPE_K * 8 * 4 : (policy == ROLLOUT_DESCENT ? 4 * (size_t)8 * 4 : 0));
+           (policy == ROLLOUT_TAPE ? 4 * (size_t)TAPE_K * 8 * 4
+                                   : (policy == ROLLOUT_DESCENT || policy == ROLLOUT_PIBT ? 4 * (size_t)8 * 4 : 0));
 }
 
 // ST (OBS_*, mapf_observe.h): OBS_NT, nontemporal observation stores -- for slot buffers (fresh HBM lines every step,
@@ -191,6 +203,12 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy)
 // rs.pi, picks (descent_action) and hands the action to the pair lanes through the wave's LDS row,
 // as the tape does (LDSACT); ro.actions receives the picks like the random draw's.  The five loads
 // are a plain per-step vector load: waited for behind the wave's observation stores.
+// PIBT: the PIBT policy (mapf_rollout_pibt).  Agent i's cell, goal and age pair sit on its head lane
+// 8 i; the head lanes read descent's five map cells and their cell's static mask, the wave solves
+// over them (pibt_solve_wave<8>, mapf_pibt.h) and the picks go through descent's LDS row.  The age
+// pair stays in registers across the steps and is written back after the last (RO = RolloutOutPibt).
+// The loop is one text, mapf_fused_rollout.inc, included into both kernels below: as a device function
+// called from them the other policies' kernels compiled to other code (the band form with scratch).
 template <int ST, int SUBS, bool BAND, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_kernel(
 #if MAPF_ARGS_PTR      // experiment build: arguments through a device pointer (mapf_rollout_wide.hip)
@@ -200,156 +218,28 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
 #else
     DevEnv e, int T, RolloutOut ro) {
 #endif
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int E = 4;                     // envs per workgroup, one per wave
-    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT;
-    // XCD-aware env order: workgroups are dealt round-robin over the 8 XCDs, so workgroup w
-    // takes env block (w % 8) * (grid / 8) + w / 8 -- each XCD owns one contiguous range of
-    // envs, and the output lines that several envs share (status: 16 envs per 128-B line)
-    // are completed in one XCD's L2 instead of leaving it as partial lines from several.
-    const int nb = (int)gridDim.x;
-    const int wg = (ro.xcd_remap && (nb & 7) == 0) ? ((int)blockIdx.x & 7) * (nb >> 3) + ((int)blockIdx.x >> 3)
-                                                   : (int)blockIdx.x;
-    const int sub = SUBS > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8)) : 0;   // this wave's quarter
-    const int qt = (int)(threadIdx.x & 255);           // thread index within the quarter
-    const int blk = wg * SUBS + sub;                   // the quarter's 4-env block
-    const int b0 = blk * E;
-    const int nenv = min(E, e.B - b0);
-    const int le = qt >> 6;
-    char *qsm = smem + (SUBS > 1 ? (size_t)sub * ro.sub_lds : 0);
-    // [4 * SUBS] words: fair, each wave's steps done; paced, the ring of arrival counters (mapf_group.h)
-    uint32_t *prog = reinterpret_cast<uint32_t *>(smem + (size_t)SUBS * ro.sub_lds);
-    static_assert(SUBS == 1 || 4 * SUBS == PACE_RING, "the pacing ring takes the place of the per-wave counters");
-    const int gw = sub * E + le;                       // the wave's index in the workgroup
-    ObsLds L = obs_layout(e, E, qsm, true);
-    float4 *lut = reinterpret_cast<float4 *>(qsm + rollout_obs_lds(e) - 256);
-    if (qt < 16) lut[qt] = make_float4((float)(qt & 1), (float)((qt >> 1) & 1), (float)((qt >> 2) & 1), (float)(qt >> 3));
-    // envs past B never count: fair, they start at the top; paced, they are not among the live waves
-    if (SUBS > 1 && (int)threadIdx.x < 4 * SUBS)
-        prog[threadIdx.x] = ro.fair <= 0 || wg * SUBS * E + (int)threadIdx.x < e.B ? 0u : 0xFFFFFFFFu;
-    __syncthreads();
-    L.lut = lut;
-    const size_t swl = srch::wave_lds<uint32_t, 1>(e.H, e.W);
-    char *slds = qsm + rollout_obs_lds(e) + (size_t)le * swl;
-    uint32_t *lpath = reinterpret_cast<uint32_t *>(qsm + rollout_obs_lds(e) + 4 * swl) + (size_t)le * e.Lmax;
-    // TAPE: this wave's TAPE_K staged rows, after the quarter's path copies; DESCENT: its one row of picks
-    int32_t *trow = nullptr;
-    if constexpr (TAPE) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e, ROLLOUT_RANDOM)) + (size_t)le * TAPE_K * 8;
-    if constexpr (DESCENT) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e, ROLLOUT_RANDOM)) + (size_t)le * 8;
-    const uint32_t mreg = obs_map_word(e, b0, nenv, (int)(threadIdx.x & 63));
-    EnvRegs rs{};
-    if (le < nenv) env_regs_load<8>(e, b0 + le, rs, lpath);
-    // every prologue load has landed before the loop: otherwise the compiler keeps a
-    // register's load "pending" at the loop header and waits vmcnt(0) -- i.e. behind
-    // all of the previous step's stores -- where the loop uses it
-    __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0), expcnt/lgkmcnt untouched
-    // the lane's skip set, one bit per store of its env's slice, from the slice's address.  It is
-    // the same at every step where the unit divides the slot stride (every slot of the env keeps
-    // slot 0's alignment: c2); where it does not (B * env bytes not a multiple of the unit, e.g.
-    // B = 37) the set moves with t and the loop computes it again for each slot.
-    uint32_t band_mask = 0;
-    bool band_moves = false;
-    if constexpr (BAND) {
-        band_moves = ((size_t)e.B * e.N * e.C * e.F * e.F * 4) % MAPF_BAND_UNIT != 0;
-        if (le < nenv && !band_moves)
-            band_mask = obs_band_skip_mask(e, MAPF_BAND_UNIT, (size_t)(ro.obs + (size_t)(b0 + le) * e.N * e.C * e.F * e.F),
-                                           (int)(threadIdx.x & 63));
-    }
-    RSTAMP_BEGIN();
-    // (a scalar condition: pace_wait's s_sleep ignores EXEC)
-    const bool pacing = SUBS > 1 && ro.slack >= 0 && __builtin_amdgcn_readfirstlane(le) < nenv;
-    const bool fair = SUBS > 1 && ro.fair > 0 && le < nenv;
-    const int live = min(max(e.B - wg * SUBS * E, 0), 4 * SUBS);     // the workgroup's waves that own an env
-    for (int t = 0; t < T; ++t) {
-        const DevEnv &E = e;
-        const RolloutOut &R = ro;
-        if (pacing) {
-            RSTAMP_WAIT0();
-            pace_wait(prog, t, R.slack, live);
-            RSTAMP_WAIT1();
-        }
-        if (fair) {
-            if ((uint32_t)t > group_min(prog, 4 * SUBS) + (uint32_t)R.fair) __builtin_amdgcn_s_setprio(0);
-            else __builtin_amdgcn_s_setprio(2);
-        }
-        const size_t BN = (size_t)E.B * E.N;
-        const size_t s = R.slots ? (size_t)t : 0;
-        if constexpr (TAPE) {
-            if ((t & (TAPE_K - 1)) == 0) {
-                if (le < nenv) {        // rows [t, t + TAPE_K) of this env, inside [T][B][N]
-                    // lane -> agent lane & 7 of rows (lane >> 3) + 8k; the opaque copy keeps the
-                    // addresses out of the loop's invariants (hoisted, they held 20 VGPRs through
-                    // the whole loop: 128 VGPRs and scratch in the band form)
-                    int lane = (int)(threadIdx.x & 63);
-                    asm volatile("" : "+v"(lane));
-                    const int i = lane & 7, r0 = lane >> 3, nrow = min(TAPE_K, T - t);
-                    const int32_t *src = R.actions + ((size_t)(t + r0) * E.B + (size_t)(b0 + le)) * E.N + i;
-                    int32_t v[TAPE_K / 8];
-#pragma unroll
-                    for (int k = 0; k < TAPE_K / 8; ++k)
-                        v[k] = (i < E.N && r0 + 8 * k < nrow) ? src[(size_t)(8 * k) * BN] : 0;
-#pragma unroll
-                    for (int k = 0; k < TAPE_K / 8; ++k) as_lds(trow)[lane + 64 * k] = v[k];
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-        if constexpr (DESCENT) {
-            // The maps read here were written before the launch (visible by the launch boundary)
-            // or by this very wave, in step_pairs_search_inline of an earlier step: one wave's
-            // vector stores and loads, same CU, performed in program order -- wavefront scope, so
-            // the fence emits nothing and only keeps the compiler from moving these int16 loads
-            // over the search's uint4 stores; the loads' own vmcnt wait is the only wait.
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (le < nenv) {
-                int lane = (int)(threadIdx.x & 63);
-                asm volatile("" : "+v"(lane));          // addresses stay out of the loop's invariants (as the tape's)
-                const int i = lane >> 3;
-                if ((lane & 7) == 0 && i < E.N) {
-                    const size_t ai = (size_t)(b0 + le) * E.N + i;
-                    const int a = descent_action(E, E.bfs + ai * bfs_cells(E.H, E.W), rs.pi, rs.clock, i);
-                    as_lds(trow)[i] = a;
-                    R.actions[s * BN + ai] = a;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-        StepOut o = R.out;
-        if (o.status) o.status += s * BN;
-        if (o.reward) o.reward += s * BN;
-        if (o.shadow_goals) o.shadow_goals += s * E.B;
-        if (o.cost) o.cost += s * BN;
-        if (o.train_valid) o.train_valid += s * BN * NA;
-        if (o.actions_fixed) o.actions_fixed += s * BN;
-        if (o.goals_reached) o.goals_reached += s * BN;
-        if (o.constraints) o.constraints += s * BN;
-        if (o.reward_total) o.reward_total += s * BN;
-        PairsDeferred dfr;
-        step_pairs_env<8, true, true, true, TAPE || DESCENT>(
-            E, TAPE ? trow + (size_t)(t & (TAPE_K - 1)) * 8 : (DESCENT ? trow : R.actions + s * BN), o, TAPE || DESCENT ? 1u : 3u, 0,
-            blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
-        if (le < nenv) {
-            const ObsGroup g = obs_wave_init(E, L, le, mreg);
-            if (BAND && band_moves)
-                band_mask = obs_band_skip_mask(E, MAPF_BAND_UNIT,
-                                               (size_t)(R.obs + (s * BN + (size_t)(b0 + le) * E.N) * E.C * E.F * E.F),
-                                               (int)(threadIdx.x & 63));
-            // a slot of the packed buffer is B * N * WPA words, not B * N * CFF floats
-            float *ob;
-            if constexpr (ST == OBS_BITS) ob = R.obs + s * BN * (size_t)obs_bits_words(E.C, E.F);
-            else ob = R.obs + s * BN * E.C * E.F * E.F;
-            obs_emit<false, ST, BAND>(E, L, ob, R.vec + s * BN * 4, g, b0, false, band_mask);
-            step_pairs_search_inline(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs);
-            if (pacing) pace_arrive(prog, t);
-            else if (fair) publish_count(prog + gw, (uint32_t)(t + 1));
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (le < nenv) env_regs_store<8>(e, b0 + le, rs);
-    if (le < nenv) RSTAMP_END(b0 + le);
+    using RO = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibt, RolloutOut>;     // RolloutOut: never PIBT here
+#include "mapf_fused_rollout.inc"
+}
+// the PIBT form: the same loop, a kernel of its own because its arguments differ (RolloutOutPibt);
+// the plan text names it by the form it shares, rollout_random_kernel<..,pibt>
+template <int ST, int SUBS, bool BAND>
+__global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_pibt_kernel(
+#if MAPF_ARGS_PTR
+    const RolloutArgsPibt *__restrict__ args, int T) {
+    const DevEnv &e = args->e;
+    const RolloutOutPibt &ro = args->ro;
+#else
+    DevEnv e, int T, RolloutOutPibt ro) {
+#endif
+    constexpr int POL = ROLLOUT_PIBT;
+    using RO = RolloutOutPibt;
+#include "mapf_fused_rollout.inc"
+}
+template <int ST, int SUBS, bool BAND, int POL>
+constexpr auto rollout_kernel_fn() {
+    if constexpr (POL == ROLLOUT_PIBT) return &rollout_random_pibt_kernel<ST, SUBS, BAND>;
+    else return &rollout_random_kernel<ST, SUBS, BAND, POL>;
 }
 
 bool rollout_random_fusable(const DevEnv &e) { return rollout_fusable(e) && rollout_lds_bytes(e, ROLLOUT_RANDOM) <= 64 * 1024; }
@@ -363,7 +253,7 @@ struct RolloutPlan {
     bool tape_ungrouped = false;   // tape / descent: their LDS rows did not fit the grouped form's LDS
 };
 
-// policy ROLLOUT_TAPE / ROLLOUT_DESCENT: the caller's-actions and descent forms (their LDS rows; past
+// policy ROLLOUT_TAPE / ROLLOUT_DESCENT / ROLLOUT_PIBT: the caller's-actions, descent and PIBT forms (their LDS rows; past
 // 64 KiB the wide kernel takes over)
 static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p, int policy) {
     if (!rollout_random_fusable(e) || rollout_lds_bytes(e, policy) > 64 * 1024) return false;
@@ -427,42 +317,52 @@ bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, 
     if (k > 0 && (size_t)k < n) {
         if (policy == ROLLOUT_TAPE)
             std::snprintf(buf + k, n - (size_t)k, " tape_k=%d%s", TAPE_K, p.tape_ungrouped ? " ungrouped=tape_lds" : "");
-        if (policy == ROLLOUT_DESCENT)
-            std::snprintf(buf + k, n - (size_t)k, " fetch=load%s", p.tape_ungrouped ? " ungrouped=descent_lds" : "");
+        if (policy == ROLLOUT_DESCENT || policy == ROLLOUT_PIBT)
+            std::snprintf(buf + k, n - (size_t)k, " fetch=load%s",
+                          p.tape_ungrouped ? (policy == ROLLOUT_PIBT ? " ungrouped=pibt_lds" : " ungrouped=descent_lds") : "");
     }
     return true;
 }
 
 // slots: the MAPF_SLOTS_* bits of mapf_rollout_random
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                          int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy) {
+                          int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy,
+                          uint32_t *pibt_seen, uint32_t *pibt_since) {
     const bool bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
     const bool band = !bits && rollout_band_form(e, slots) && ((uintptr_t)obs & 15) == 0;     // whole float4s
     slots &= 1;
     RolloutPlan p;
     if (!plan_rollout_random(e, slots, tu, p, policy)) return ROLLOUT_NOT_COVERED;
-    const RolloutOut ro{actions, out, obs, vec, slots, p.remap, p.sub_lds, p.slack, p.fair};
-    auto launch = [&](auto kern) -> int {
-        const dim3 gd(p.grid), bd(256 * p.subs);
-#if MAPF_ARGS_PTR
-        const RolloutArgs *args = push_args(ring, RolloutArgs{e, ro}, s);
-        if (!args) return MAPF_ESTATE;      // a capture found no free argument slot: nothing launched
-        hipLaunchKernelGGL(kern, gd, bd, p.lds, s, args, T);
-#else
-        hipLaunchKernelGGL(kern, gd, bd, p.lds, s, e, T, ro);
-#endif
-        return MAPF_OK;
-    };
+    const RolloutOut ro0{actions, out, obs, vec, slots, p.remap, p.sub_lds, p.slack, p.fair};
     (void)ring;
     return with_policy(policy, [&](auto pol) -> int {
         constexpr int POL = decltype(pol)::value;
+        using RO = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibt, RolloutOut>;
+        RO ro{};
+        static_cast<RolloutOut &>(ro) = ro0;
+        if constexpr (POL == ROLLOUT_PIBT) {
+            ro.pibt_seen = pibt_seen;
+            ro.pibt_since = pibt_since;
+        }
+        auto launch = [&](auto kern) -> int {
+            const dim3 gd(p.grid), bd(256 * p.subs);
+#if MAPF_ARGS_PTR
+            using RA = std::conditional_t<POL == ROLLOUT_PIBT, RolloutArgsPibt, RolloutArgs>;
+            const RA *args = push_args(ring, RA{e, ro}, s);
+            if (!args) return MAPF_ESTATE;      // a capture found no free argument slot: nothing launched
+            hipLaunchKernelGGL(kern, gd, bd, p.lds, s, args, T);
+#else
+            hipLaunchKernelGGL(kern, gd, bd, p.lds, s, e, T, ro);
+#endif
+            return MAPF_OK;
+        };
         if (bits)      // one instantiation for slots and in place (ro.slots is a run-time field)
-            return p.subs == 4 ? launch(rollout_random_kernel<OBS_BITS, 4, false, POL>) : launch(rollout_random_kernel<OBS_BITS, 1, false, POL>);
+            return p.subs == 4 ? launch(rollout_kernel_fn<OBS_BITS, 4, false, POL>()) : launch(rollout_kernel_fn<OBS_BITS, 1, false, POL>());
         if (band)
-            return p.subs == 4 ? launch(rollout_random_kernel<true, 4, true, POL>) : launch(rollout_random_kernel<true, 1, true, POL>);
+            return p.subs == 4 ? launch(rollout_kernel_fn<true, 4, true, POL>()) : launch(rollout_kernel_fn<true, 1, true, POL>());
         if (p.subs == 4)
-            return slots ? launch(rollout_random_kernel<true, 4, false, POL>) : launch(rollout_random_kernel<false, 4, false, POL>);
-        return slots ? launch(rollout_random_kernel<true, 1, false, POL>) : launch(rollout_random_kernel<false, 1, false, POL>);
+            return slots ? launch(rollout_kernel_fn<true, 4, false, POL>()) : launch(rollout_kernel_fn<false, 4, false, POL>());
+        return slots ? launch(rollout_kernel_fn<true, 1, false, POL>()) : launch(rollout_kernel_fn<false, 1, false, POL>());
     });
 }
 

@@ -68,6 +68,9 @@ bool launch_step_pairs(const DevEnv &e, int32_t *actions, const StepOut &out, ui
 void launch_random_actions(const DevEnv &e, int32_t *actions, hipStream_t s);
 // the descent policy's actions from the state and the tiled BFS maps (keep_bfs; mapf_descent_actions)
 void launch_descent_actions(const DevEnv &e, int32_t *actions, hipStream_t s);
+// the PIBT policy's actions from the state, the tiled BFS maps and the handle's age arrays seen /
+// since [B][N], which it updates (keep_bfs; mapf_pibt_actions, mapf_pibt.hip): one wave per env
+void launch_pibt_actions(const DevEnv &e, int32_t *actions, uint32_t *seen, uint32_t *since, hipStream_t s);
 // humans' next paths (replan_list[parity]) + agent BFS maps (bfs_list[parity]);
 // all = 1: every env's next path and every agent's map, 2: every env's next path,
 // 3 / 4: the step's human paths / BFS maps only
@@ -102,31 +105,42 @@ void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, 
 //   ROLLOUT_DESCENT (mapf_rollout_descent): every action is picked from the agents' tiled BFS maps
 //     (keep_bfs) and written to `actions` like the draw; the plan's text carries ",descent" (and
 //     bfsobs=0 in the wide three-wave form).
+//   ROLLOUT_PIBT (mapf_rollout_pibt): the stepping wave picks every action with the PIBT solve
+//     (mapf_pibt.h) from the tiled BFS maps and the handle's age arrays, written to `actions` like
+//     the draw; the plan's text carries ",pibt" (and bfsobs=0 in the wide three-wave form).  Its
+//     kernels take the age arrays in argument types of their own and are therefore symbols of their
+//     own over the shared bodies: rollout_random_pibt_kernel, rollout_wide_pibt_kernel,
+//     rollout_wide3_pibt_kernel.
 // describe_rollout_random returns false (text "none") where the pair-lane kernel does not take the
 // launch -- with a tape or descent that includes a fusable configuration whose LDS rows do not fit.
 constexpr int ROLLOUT_NOT_COVERED = 1;
-constexpr int ROLLOUT_RANDOM = 0, ROLLOUT_TAPE = 1, ROLLOUT_DESCENT = 2;
+constexpr int ROLLOUT_RANDOM = 0, ROLLOUT_TAPE = 1, ROLLOUT_DESCENT = 2, ROLLOUT_PIBT = 3;
 // f(std::integral_constant<int, policy>{}): the runtime policy as a template argument
 template <class F>
 inline auto with_policy(int policy, F f) {
+    if (policy == ROLLOUT_PIBT) return f(std::integral_constant<int, ROLLOUT_PIBT>{});
     if (policy == ROLLOUT_DESCENT) return f(std::integral_constant<int, ROLLOUT_DESCENT>{});
     if (policy == ROLLOUT_TAPE) return f(std::integral_constant<int, ROLLOUT_TAPE>{});
     return f(std::integral_constant<int, ROLLOUT_RANDOM>{});
 }
 // the policy's mark inside the angle brackets of the plan text
 inline const char *rollout_policy_tag(int policy) {
-    return policy == ROLLOUT_DESCENT ? ",descent" : (policy == ROLLOUT_TAPE ? ",tape" : "");
+    return policy == ROLLOUT_PIBT ? ",pibt" : (policy == ROLLOUT_DESCENT ? ",descent" : (policy == ROLLOUT_TAPE ? ",tape" : ""));
 }
+// pibt_seen / pibt_since (here and in launch_rollout_wide): the handle's age arrays [B][N], read and
+// written back by ROLLOUT_PIBT launches only
 bool rollout_random_fusable(const DevEnv &e);
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                           int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy);
+                           int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy,
+                           uint32_t *pibt_seen, uint32_t *pibt_since);
 bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy);
 // the same for up to 64 agents / per-env maps / the BFS channel: one wave per env
 // (mapf_rollout_wide.hip); used where the pair-lane rollout does not apply.  Returns MAPF_OK or
 // MAPF_ESTATE (a captured launch found no free argument slot, ArgRing).
 bool rollout_wide_fusable(const DevEnv &e);
 int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                        int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy);
+                        int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy,
+                        uint32_t *pibt_seen, uint32_t *pibt_since);
 void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy);
 
 // Device-resident kernel argument blocks.  A persistent kernel whose arguments (DevEnv + its

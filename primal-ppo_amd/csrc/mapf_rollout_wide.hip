@@ -59,6 +59,19 @@ struct WideArgs {
     WideOut ro;
 };
 
+// PIBT launches: the same with the handle's age arrays [B][N].  Types and kernels of their own
+// (rollout_wide_pibt_kernel, rollout_wide3_pibt_kernel), so that the other policies' kernels keep
+// their names, their argument layout and with it their register allocation.
+struct WideOutPibt : WideOut {
+    uint32_t *pibt_seen, *pibt_since;
+};
+struct WideArgsPibt {
+    DevEnv e;
+    WideOutPibt ro;
+};
+template <int POL> using wide_out_t = std::conditional_t<POL == ROLLOUT_PIBT, WideOutPibt, WideOut>;
+template <int POL> using wide_args_t = std::conditional_t<POL == ROLLOUT_PIBT, WideArgsPibt, WideArgs>;
+
 __host__ __device__ inline size_t wide_a16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // observation part of the scratch area: stream | occ | spos | sgoal | shn | shp | shpn | idg
@@ -175,9 +188,11 @@ __device__ inline void wide_plain_barrier() {
 // stepper measured slower
 #if MAPF_ARGS_PTR
 #define WIDE_PARAMS const WideArgs *__restrict__ args, int T_steps
-#define WIDE_BIND const DevEnv &e = args->e; const WideOut &ro = args->ro;
+#define WIDE_PIBT_PARAMS const WideArgsPibt *__restrict__ args, int T_steps
+#define WIDE_BIND const DevEnv &e = args->e; const auto &ro = args->ro;
 #else
 #define WIDE_PARAMS DevEnv e, int T_steps, WideOut ro
+#define WIDE_PIBT_PARAMS DevEnv e, int T_steps, WideOutPibt ro
 #define WIDE_BIND
 #endif
 
@@ -190,12 +205,18 @@ __device__ inline void wide_plain_barrier() {
 // the picks like the random draw's.  The maps the step rebuilds are always searched by the stepping
 // wave itself, never by the observers (bfsobs is ignored: they run up to WIDE_SNAPS steps behind),
 // so every map the step reads was written by the reading wave or before the launch.
+// PIBT: the PIBT policy (mapf_rollout_pibt): the stepping wave picks for the whole env where descent's
+// loads sit (step_group<.., ROLLOUT_PIBT>: lane = agent, the solve by readlanes and ballots, no LDS),
+// under descent's ordering rule (the stepper searches the maps it reads: bfsobs is ignored).  Every
+// stepping lane keeps its agent's age pair in registers across the steps, loaded from and written
+// back to ro.pibt_seen / ro.pibt_since, so the arrays end as T per-step picks leave them.
 // ST (OBS_*, mapf_observe.h): plain or nontemporal float stores, or OBS_BITS: ro.obs is the packed
 // uint32 [T or 1][B][N][WPA] buffer (MAPF_SLOTS_OBS_BITS) and every observation written by the loop
 // -- the three-wave in-place form's last-step re-store included -- is the packed one.
-template <class T, int RW, int ST, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
-__device__ __attribute__((always_inline)) inline void rollout_wide_body(const DevEnv &e, int T_steps, const WideOut &ro) {
-    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT;
+template <class T, int RW, int ST, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT / ROLLOUT_PIBT
+__device__ __attribute__((always_inline)) inline void rollout_wide_body(const DevEnv &e, int T_steps, const wide_out_t<POL> &ro) {
+    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT, PIBT = POL == ROLLOUT_PIBT;
+    constexpr bool PICKS = DESCENT || PIBT;          // the stepping wave picks from the BFS maps
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // XCD-aware env order (as the pair-lane rollout): workgroups are dealt round-robin
     // over the 8 XCDs, so each XCD owns one contiguous range of envs
@@ -263,6 +284,11 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
     __syncthreads();
     StepRegs rs;                           // the stepping wave keeps the env's state in registers
     step_regs_load(e, b, lane, rs);
+    if constexpr (PIBT) {
+        const size_t ag = (size_t)b * e.N + (size_t)min(lane, e.N - 1);
+        rs.pseen = ro.pibt_seen[ag];
+        rs.psince = ro.pibt_since[ag];
+    }
     // the registers' loads done before the loop: with one still counted at the loop header,
     // the top of every step waited vmcnt(0), i.e. for the previous step's output stores too
     __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0), expcnt/lgkmcnt untouched
@@ -328,7 +354,7 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
     // observation, instead of on the stepper's chain (c4: 0.59 of its 4.63 us per step).  Step
     // t's maps are written after step t - 1's (ctr[3]: steps whose maps are done), so an agent's
     // later map wins; an observer that searched drains its stores before it counts.
-    const bool bfs_obs = !DESCENT && ovl && nobs >= 2 && observing && ro.bfsobs;
+    const bool bfs_obs = !PICKS && ovl && nobs >= 2 && observing && ro.bfsobs;
     // several observers writing the same in-place buffers, in alternation
     const bool inplace_multi = ovl && nobs >= 2 && observing && !ro.slots;
     WSTAMP_BEGIN();
@@ -341,8 +367,8 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
         }
         StepInline inl;
         if (stepper)
-            step_group<WaveGroup, true, true, DESCENT>(e, lact + (TAPE ? (size_t)t : s) * BN, step_out(s),
-                                                       TAPE || DESCENT ? 1u : 3u, 0, b, g, &inl, src, rs, have);
+            step_group<WaveGroup, true, true, PICKS ? POL : ROLLOUT_RANDOM>(e, lact + (TAPE ? (size_t)t : s) * BN, step_out(s),
+                                                                            TAPE || PICKS ? 1u : 3u, 0, b, g, &inl, src, rs, have);
         WSTAMP(0);
         // A: observation t-1 done.  Nothing the observer reads from HBM was written by the step
         // (its outputs and state are not read back), so the stepper does not wait for them.
@@ -440,6 +466,12 @@ __device__ __attribute__((always_inline)) inline void rollout_wide_body(const De
         obs_emit<true, ST>(e, Lt, ro.obs, ro.vec, G, b, false);     // (packed in a packed launch)
     }
     if (stepper) step_regs_store(e, b, lane, rs);
+    if constexpr (PIBT) {
+        if (stepper && lane < e.N) {
+            ro.pibt_seen[(size_t)b * e.N + lane] = rs.pseen;
+            ro.pibt_since[(size_t)b * e.N + lane] = rs.psince;
+        }
+    }
     WSTAMP_END(b, role);
 }
 
@@ -458,6 +490,31 @@ template <class T, int RW, int ST, int POL>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void rollout_wide3_kernel(
     const WideArgs *__restrict__ args, int T_steps) {
     rollout_wide_body<T, RW, ST, POL>(args->e, T_steps, args->ro);
+}
+
+// The PIBT forms of the two kernels: the same body with ROLLOUT_PIBT, kernels of their own because
+// their arguments differ (WideOutPibt).  The plan text names them by the form they share,
+// rollout_wide_kernel<..,pibt> / rollout_wide3_kernel<..,pibt>.
+template <class T, int RW, int ST>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void rollout_wide_pibt_kernel(WIDE_PIBT_PARAMS) {
+    WIDE_BIND
+    rollout_wide_body<T, RW, ST, ROLLOUT_PIBT>(e, T_steps, ro);
+}
+template <class T, int RW, int ST>
+__global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void rollout_wide3_pibt_kernel(
+    const WideArgsPibt *__restrict__ args, int T_steps) {
+    rollout_wide_body<T, RW, ST, ROLLOUT_PIBT>(args->e, T_steps, args->ro);
+}
+// the kernel of a policy and store form
+template <class T, int RW, int ST, int POL>
+constexpr auto wide_kernel_fn() {
+    if constexpr (POL == ROLLOUT_PIBT) return &rollout_wide_pibt_kernel<T, RW, ST>;
+    else return &rollout_wide_kernel<T, RW, ST, POL>;
+}
+template <class T, int RW, int ST, int POL>
+constexpr auto wide3_kernel_fn() {
+    if constexpr (POL == ROLLOUT_PIBT) return &rollout_wide3_pibt_kernel<T, RW, ST>;
+    else return &rollout_wide3_kernel<T, RW, ST, POL>;
 }
 
 // The three-wave form is not built for 128-bit rows spread over two lanes (maps wider than 64 cells):
@@ -498,12 +555,12 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     p.nt = tu.wide_nt >= 0 ? tu.wide_nt != 0 : (slots || (size_t)e.B * e.N * e.C * e.F * e.F * 4 > ((size_t)128 << 20));
     if (p.bits) p.nt = false;
     // (the packed kernels' own register counts decide their form, as each policy's do)
-    const void *kern = p.bits ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, OBS_BITS, POL>) : p.nt ? reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, true, POL>)
-                            : reinterpret_cast<const void *>(rollout_wide_kernel<T, RW, false, POL>);
+    const void *kern = p.bits ? reinterpret_cast<const void *>(wide_kernel_fn<T, RW, OBS_BITS, POL>()) : p.nt ? reinterpret_cast<const void *>(wide_kernel_fn<T, RW, true, POL>())
+                            : reinterpret_cast<const void *>(wide_kernel_fn<T, RW, false, POL>());
     const void *kern3 = nullptr;
     if constexpr (wide3_form<T, RW>())
-        kern3 = p.bits ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, OBS_BITS, POL>) : p.nt ? reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, true, POL>)
-                     : reinterpret_cast<const void *>(rollout_wide3_kernel<T, RW, false, POL>);
+        kern3 = p.bits ? reinterpret_cast<const void *>(wide3_kernel_fn<T, RW, OBS_BITS, POL>()) : p.nt ? reinterpret_cast<const void *>(wide3_kernel_fn<T, RW, true, POL>())
+                     : reinterpret_cast<const void *>(wide3_kernel_fn<T, RW, false, POL>());
     // two waves per env where every env's pair fits at once: the VGPR budget of a SIMD
     // (512 per lane) over the waves it must hold, 4 SIMDs per CU
     const int fit = 512 / ((kernel_vgprs(kern) + 7) & ~7);
@@ -514,7 +571,7 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     r.slots = slots;
     r.xcd_remap = tu.xcd_remap != 0;
     r.prio = tu.wide_prio;
-    r.bfsobs = POL == ROLLOUT_DESCENT ? 0 : tu.wide_bfsobs;      // descent: the stepping wave reads the maps it rebuilt
+    r.bfsobs = POL == ROLLOUT_DESCENT || POL == ROLLOUT_PIBT ? 0 : tu.wide_bfsobs;   // descent, PIBT: the stepping wave reads the maps it rebuilt
     r.grid = 0;
     if (!pipe && wide_grid_bytes(e) <= wide_scratch_bytes<T, RW>(e)) r.grid = 2;
     else if (wide_lds_bytes<T, RW>(e, 1) <= (occ > 1 ? cap : (size_t)64 * 1024)) r.grid = 1;
@@ -570,28 +627,33 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
 }
 
 template <class T, int RW, int POL>
-static int launch_wide_t(const DevEnv &e, int steps, const WideOut &ro, const mapf_tuning &tu, ArgRing &ring,
+static int launch_wide_t(const DevEnv &e, int steps, const WideOutPibt &ro, const mapf_tuning &tu, ArgRing &ring,
                          hipStream_t s) {
     const WidePlan p = plan_wide_t<T, RW, POL>(e, ro.slots, tu);     // ro.slots: MAPF_SLOTS | MAPF_SLOTS_OBS_BITS
-    WideOut r = p.r;
+    wide_out_t<POL> r{};
+    static_cast<WideOut &>(r) = p.r;
+    if constexpr (POL == ROLLOUT_PIBT) {
+        r.pibt_seen = ro.pibt_seen;
+        r.pibt_since = ro.pibt_since;
+    }
     r.actions = ro.actions;
     r.out = ro.out;
     r.obs = ro.obs;
     r.vec = ro.vec;
     if constexpr (wide3_form<T, RW>()) {
         if (r.wpe == 3) {
-            const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
+            const wide_args_t<POL> *args = push_args(ring, wide_args_t<POL>{e, r}, s);
             if (!args) return MAPF_ESTATE;
-            auto kern3 = p.bits ? rollout_wide3_kernel<T, RW, OBS_BITS, POL>
-                                : (p.nt ? rollout_wide3_kernel<T, RW, true, POL> : rollout_wide3_kernel<T, RW, false, POL>);
+            auto kern3 = p.bits ? wide3_kernel_fn<T, RW, OBS_BITS, POL>()
+                                : (p.nt ? wide3_kernel_fn<T, RW, true, POL>() : wide3_kernel_fn<T, RW, false, POL>());
             hipLaunchKernelGGL(kern3, dim3(p.grid), dim3(p.block), p.lds, s, args, steps);
             return MAPF_OK;
         }
     }
-    auto kern = p.bits ? rollout_wide_kernel<T, RW, OBS_BITS, POL>
-                       : (p.nt ? rollout_wide_kernel<T, RW, true, POL> : rollout_wide_kernel<T, RW, false, POL>);
+    auto kern = p.bits ? wide_kernel_fn<T, RW, OBS_BITS, POL>()
+                       : (p.nt ? wide_kernel_fn<T, RW, true, POL>() : wide_kernel_fn<T, RW, false, POL>());
 #if MAPF_ARGS_PTR
-    const WideArgs *args = push_args(ring, WideArgs{e, r}, s);
+    const wide_args_t<POL> *args = push_args(ring, wide_args_t<POL>{e, r}, s);
     if (!args) return MAPF_ESTATE;
     hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, s, args, steps);
 #else
@@ -621,8 +683,11 @@ bool rollout_wide_fusable(const DevEnv &e) {
 }
 
 int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                        int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy) {
-    WideOut ro{};
+                        int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy,
+                        uint32_t *pibt_seen, uint32_t *pibt_since) {
+    WideOutPibt ro{};
+    ro.pibt_seen = pibt_seen;
+    ro.pibt_since = pibt_since;
     ro.actions = actions;
     ro.out = out;
     ro.obs = obs;

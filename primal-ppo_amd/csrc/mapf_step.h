@@ -24,6 +24,7 @@
 #pragma once
 #include "mapf_group.h"
 #include "mapf_kernels.h"
+#include "mapf_pibt.h"
 #include "mapf_pyset.h"
 
 namespace mapf {
@@ -50,6 +51,7 @@ struct StepRegs {
     uint32_t clock, hp, hn;
     int hs, hcur, hl0, hl1;
     uint32_t hq;         // per lane q in 1..k_predict: human.path[q] after the step (NO_CELL past its end)
+    uint32_t pseen, psince;   // per lane, PIBT launches only: the agent's age pair (loaded and stored by the caller)
 };
 
 __device__ inline void step_regs_load(const DevEnv &e, int b, int i, StepRegs &r) {
@@ -133,14 +135,19 @@ struct StepSrc {
 // lane's element (shadow_goals this env's), held in VGPRs by the caller, and `have` says which
 // outputs exist (bit k = the k-th StepOut field) -- the output bases then take no SGPRs in the
 // step loop, where they were spilled to VGPR lanes and read back at every store.
-// DESCENT (the wide rollout's descent launches, with REGS): the lane picks its agent's action
-// itself (descent_action() over its tiled BFS map) and stores it to `actions`; `flags` bit 1 is
-// then not looked at.
-template <class Grp, bool REGS = false, bool LANEPTR = false, bool DESCENT = false>
+// POL = ROLLOUT_DESCENT (the wide rollout's descent launches, with REGS): the lane picks its agent's
+// action itself (descent_action() over its tiled BFS map) and stores it to `actions`; `flags` bit 1
+// is then not looked at.  POL = ROLLOUT_PIBT (its PIBT launches, REGS and the env the whole wave):
+// the wave picks with the PIBT solve (mapf_pibt.h) from the same five cells per lane, the env's
+// human cells and the age pair in rg, and stores the picks likewise.  Any other POL: the actions
+// come from `flags` bit 1 or the caller.
+template <class Grp, bool REGS = false, bool LANEPTR = false, int POL = ROLLOUT_RANDOM>
 __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e, int32_t *__restrict__ actions,
                                                                 const StepOut &out, uint32_t flags, int parity, int b,
                                                                 const Grp &g, StepInline *inl, StepSrc src,
                                                                 StepRegs &rg, uint32_t have = 0) {
+    constexpr bool DESCENT = POL == ROLLOUT_DESCENT, PIBT = POL == ROLLOUT_PIBT;
+    static_assert(!PIBT || (REGS && std::is_same<Grp, WaveGroup>::value), "the PIBT solve runs on a whole wave");
     const int N = e.N;
     STAMP_BEGIN();
     const int i = g.i;
@@ -219,6 +226,26 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
             a = descent_action(e, e.bfs + ai * bfs_cells(e.H, e.W), pp, clock, i);
             actions[oi] = a;
         }
+    } else if constexpr (PIBT) {
+        // The map cells load where descent's do, under the same visibility rule (the caller
+        // searches the maps it reads: bfsobs = 0).  The static mask comes from the LDS rows, as
+        // getInvalidActions' below; the human's cells and the age pair from the registers.
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        uint32_t cand[NA] = {PIBT_NONE, PIBT_NONE, PIBT_NONE, PIBT_NONE, PIBT_NONE};
+        uint32_t age = 0;
+        if (act) {
+            age = pibt_age(rg.pseen, rg.psince, gg, clock);
+            const auto rows = as_lds(src.map);
+            unsigned sm = 0;
+            uint32_t w[NA];
+#pragma unroll
+            for (int k = 0; k < NA; ++k) w[k] = rows[(pr + dr(k) + e.P) * e.WW + ((pc + dc(k) + e.P) >> 5)];
+#pragma unroll
+            for (int k = 0; k < NA; ++k) sm |= ((w[k] >> ((pc + dc(k) + e.P) & 31)) & 1u) << k;
+            pibt_candidates(e, e.bfs + ai * bfs_cells(e.H, e.W), pp, sm, rg.hp, rg.hn, clock, i, cand);
+        }
+        a = pibt_solve_wave(N, i, pp, cand, age);     // every lane: pp is NO_CELL past N
+        if (act) actions[oi] = a;
     } else
     if (flags & 2u) {          // random policy fused in: same stream as random_actions_kernel
         if (act) {

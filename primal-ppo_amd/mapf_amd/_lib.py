@@ -100,6 +100,11 @@ SIGNATURES = {
     "mapf_rollout_descent_plan": (ctypes.c_int, [P, I32, ctypes.c_char_p, I32]),
     "mapf_descent_actions": (ctypes.c_int, [P, P, P]),
     "mapf_descent_pick": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, I32]),
+    "mapf_rollout_pibt": (ctypes.c_int, [P, I32, I32, P, ctypes.POINTER(StepOut), P, P, P]),
+    "mapf_rollout_pibt_plan": (ctypes.c_int, [P, I32, ctypes.c_char_p, I32]),
+    "mapf_pibt_actions": (ctypes.c_int, [P, P, P]),
+    "mapf_pibt_key": (ctypes.c_int, [I32, I32, ctypes.c_uint32, I32]),
+    "mapf_pibt_host": (ctypes.c_int, [I32, P, P, P, P, P]),
     "mapf_flush": (ctypes.c_int, [P, P]),
     "mapf_release_captures": (ctypes.c_int, [P]),
     "mapf_random_actions": (ctypes.c_int, [P, P, P]),

@@ -167,6 +167,16 @@ class BatchedMapfGym:
         """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,descent>'."""
         return self.rollout_descent_plan(slots, band_clean, obs_bits).split(" ")[0]
 
+    def rollout_pibt_plan(self, slots=False, band_clean=False, obs_bits=False):
+        """rollout_plan for rollout_pibt (mapf_rollout_pibt_plan): the same text with ",pibt" inside the
+        angle brackets (the wide three-wave form with bfsobs=0), or "pibt_actions+step_observe" where
+        the call runs per-step launches.  The text names the form; mapf.h lists the kernels' symbols."""
+        return self._plan(_lib.lib().mapf_rollout_pibt_plan, slots, band_clean, obs_bits)
+
+    def rollout_pibt_kernel_name(self, slots=False, band_clean=False, obs_bits=False):
+        """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,pibt>'."""
+        return self.rollout_pibt_plan(slots, band_clean, obs_bits).split(" ")[0]
+
     @staticmethod
     def _make_stepout(out):
         so = _lib.StepOut()
@@ -457,6 +467,24 @@ class BatchedMapfGym:
                                                    ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
 
+    def rollout_pibt(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False,
+                     obs_bits=False):
+        """T x (pibt_actions, step_observe) -- the PIBT planner, the collision-free baseline
+        (mapf_rollout_pibt; needs keep_bfs) -- as ONE launch where rollout_fused (the rollout kernels'
+        PIBT forms, rollout_pibt_plan), else T pairs of per-step launches; identical
+        results, the policy's ages included.  `actions` receives the chosen actions; slots, actions,
+        obs, vec, out, band_clean, obs_bits: as rollout_random.  Returns (out, obs, vec)."""
+        T = int(T)
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
+                                                           obs_bits=obs_bits)
+        if T == 0:          # nothing to play (an empty tensor has no address to hand over)
+            return out, obs, vec
+        _lib.check(_lib.lib().mapf_rollout_pibt(self.h, T, self._slot_bits(slots, band_clean, obs_bits), _ptr(actions),
+                                                ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
+        return out, obs, vec
+
     def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None, actions_in=None,
                          policy="random", obs_bits=False):
         """rollout_random(T, slots, ...) prepared once: the buffers are checked and the C call's
@@ -475,14 +503,14 @@ class BatchedMapfGym:
         slots, ...) instead (`actions` is not used), under the same band rule.  The tape's contents
         are read at launch time: refill the same tensor between calls to play other actions.
 
-        policy: "random" (the default) or "descent" -- the launcher then issues rollout_descent(T,
-        slots, actions, ...) under the same band rule.  A policy other than "random" and
-        actions_in exclude each other.
+        policy: "random" (the default), "descent" or "pibt" -- the launcher then issues
+        rollout_descent / rollout_pibt(T, slots, actions, ...) under the same band rule.  A policy
+        other than "random" and actions_in exclude each other.
 
         obs_bits: `obs` is the packed int32 buffer (as rollout_random); every call stores every word
         (the band rule does not apply)."""
-        if policy not in ("random", "descent"):
-            raise ValueError(f"policy: expected 'random' or 'descent', got {policy!r}")
+        if policy not in ("random", "descent", "pibt"):
+            raise ValueError(f"policy: expected 'random', 'descent' or 'pibt', got {policy!r}")
         if policy != "random" and actions_in is not None:
             raise ValueError("policy and actions_in are mutually exclusive")
         if actions_in is not None:
@@ -493,7 +521,8 @@ class BatchedMapfGym:
                 _ptr(vec), _stream(self.device))
         clean = args[:2] + (self._slot_bits(slots, not obs_bits, obs_bits),) + args[3:]
         fn = (_lib.lib().mapf_rollout_actions if actions_in is not None else
-              _lib.lib().mapf_rollout_descent if policy == "descent" else _lib.lib().mapf_rollout_random)
+              _lib.lib().mapf_rollout_descent if policy == "descent" else
+              _lib.lib().mapf_rollout_pibt if policy == "pibt" else _lib.lib().mapf_rollout_random)
         keep = (so, actions, obs, vec, out)
         state = [args]                  # the next call's arguments: `clean` once a call has stored the band
 
@@ -528,6 +557,14 @@ class BatchedMapfGym:
         out = self.actions if out is None else out
         _check(out, torch.int32, self.B * self.N, self.device, "actions")
         _lib.check(_lib.lib().mapf_descent_actions(self.h, _ptr(out), _stream(self.device)))
+        return out
+
+    def pibt_actions(self, out=None):
+        """The PIBT policy's actions for the current state (mapf_pibt_actions; needs keep_bfs): int32
+        [B, N], no two agents to one cell and no swap; updates the policy's ages."""
+        out = self.actions if out is None else out
+        _check(out, torch.int32, self.B * self.N, self.device, "actions")
+        _lib.check(_lib.lib().mapf_pibt_actions(self.h, _ptr(out), _stream(self.device)))
         return out
 
     def random_actions(self, out=None):

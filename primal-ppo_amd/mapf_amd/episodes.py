@@ -188,6 +188,17 @@ def descent_policy():
     return policy
 
 
+def pibt_policy():
+    """The PIBT planner as a policy(obs, vec, env, t) for evaluate_fixed_episodes: one collision-free
+    step for all agents from their BFS maps (env.pibt_actions, mapf_pibt_actions).  The env must keep
+    the agents' BFS maps: evaluate_fixed_episodes(..., keep_bfs=True)."""
+    def policy(obs, vec, env, t):
+        if not env.cfg.keep_bfs:
+            raise RuntimeError("pibt_policy needs the agents' BFS maps: evaluate_fixed_episodes(..., keep_bfs=True)")
+        return env.pibt_actions()
+    return policy
+
+
 def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, use_da=False, use_hp=False,
                             human_movement_type=0, max_steps=256, k_predict=5, fix_choice=1, record_actions=False,
                             keep_bfs=False):
@@ -202,7 +213,7 @@ def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, us
     record_actions: return (metrics, tapes) instead -- tapes[(H, W)] = the policy's actions of that
     map-shape group (not the executed actions_fixed), int32 [max_steps, len(group), N] on the
     device: what replay_fixed_episodes plays back.
-    keep_bfs: the envs keep every agent's BFS map current (descent_policy reads them)."""
+    keep_bfs: the envs keep every agent's BFS map current (descent_policy and pibt_policy read them)."""
     device = torch.device("cuda") if device is None else torch.device(device)
     E = infos["numEpisodes"]
     res = {k: np.zeros(E, np.float64) for k in METRIC_KEYS}

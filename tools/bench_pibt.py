@@ -1,0 +1,157 @@
+"""PIBT rollouts (mapf_rollout_pibt) beside random- and descent-policy rollouts, beside the same policy
+through per-step launches, and against a baseline build of the library, in one alternated series on
+one GPU.
+
+  python tools/bench_pibt.py --config c2                       # this build: random / descent / pibt / per-step
+  python tools/bench_pibt.py --config c2 --baseline-lib primal-ppo_amd/lib/libmapf_parent.so --rounds 3
+
+Each measurement process builds the preset's env (bench.py's presets and maps), prepares one launcher
+per policy over the same [T]-slot buffers (T = 256, c5: 87), every policy on a handle of its own (so
+each plays its own episode from the same reset), runs one untimed round, then `--pairs` alternated
+rounds random / descent / pibt, each launch between two HIP events, and then `--pairs` per-step
+series: PIBT as T x (pibt_actions, step_observe) calls in place, between two HIP events over the whole
+series.  From the last timed launch of descent and of PIBT, per env-step: goals reached, agents with
+status -3, and actions fixActions rewrote (actions_fixed != actions).  With --baseline-lib the driver
+(which never opens the GPU) starts fresh child processes in turn, baseline / this build, `--rounds`
+times: the baseline library (the parent commit's build, which has no PIBT entry points) runs its
+random and descent policies only.  The verdicts printed at the end:
+  (i)   this build's random and descent medians lie inside the baseline's own min..max spreads;
+  (ii)  the one-launch PIBT median is below the per-step median by more than the per-step series' own
+        min..max spread.
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "primal-ppo_amd")]
+PIBT_FNS = ("mapf_rollout_pibt", "mapf_rollout_pibt_plan", "mapf_pibt_actions", "mapf_pibt_key", "mapf_pibt_host")
+
+
+def measure(args):
+    """One process: per-launch times in us per step, {"random": [...], "descent": [...], "pibt": [...],
+    "per-step": [...]}."""
+    if args.lib:
+        os.environ["MAPF_LIB"] = os.path.abspath(args.lib)
+    import torch
+    import bench
+    from mapf_amd import _lib
+    has = all(hasattr(ctypes.CDLL(_lib.LIB_PATH), n) for n in PIBT_FNS)
+    if not has:                           # a build from before the PIBT entry points: random and descent only
+        for n in PIBT_FNS:
+            _lib.SIGNATURES.pop(n)
+    from mapf_amd.config import make_config
+    from mapf_amd.env import BatchedMapfGym
+    p = bench.PRESETS[args.config]
+    B, N, S, F, C = args.envs or p["envs"], p["agents"], p["size"], p["fov"], p["channels"]
+    T = args.T or (87 if args.config == "c5" else 256)
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    maps, shared = bench.make_maps(p["maps"], B, S, S, 0)
+
+    def make_env():
+        e = BatchedMapfGym(make_config(B, S, S, num_agents=N, fov=F, num_channel=C, human_mode="random",
+                                       goal_mode="random", fix_choice=1, seed=1234, shared_map=shared), device=dev)
+        e.reset_seeded(maps)
+        return e
+    slots = not args.inplace
+    K = T if slots else 1                 # in place: every step re-writes the [B]-leading buffers
+    acts = torch.empty(K, B, N, dtype=torch.int32, device=dev)
+    obs = torch.empty(K, B, N, C, F, F, dtype=torch.float32, device=dev)
+    vec = torch.empty(K, B, N, 4, dtype=torch.float32, device=dev)
+    envs = {"random": make_env(), "descent": make_env()}
+    out = {k: torch.empty((K,) + tuple(v.shape), dtype=v.dtype, device=dev) for k, v in envs["random"].out.items()}
+    kw = dict(slots=slots, actions=acts, obs=obs, vec=vec, out=out)
+    launch = {"random": envs["random"].rollout_launcher(T, **kw),
+              "descent": envs["descent"].rollout_launcher(T, policy="descent", **kw)}
+    plan = {"random": envs["random"].rollout_plan(slots, slots), "descent": envs["descent"].rollout_descent_plan(slots, slots)}
+    if has:
+        envs["pibt"] = penv = make_env()
+        launch["pibt"] = penv.rollout_launcher(T, policy="pibt", **kw)
+        plan["pibt"] = penv.rollout_pibt_plan(slots, slots)
+        out0 = {k: v[0] for k, v in out.items()}
+
+        def per_step():
+            for _ in range(T):
+                penv.step_observe(penv.pibt_actions(acts[0]), obs[0], vec[0], out=out0)
+        launch["per-step"] = per_step
+    times = {k: [] for k in launch}
+    quality = {}
+    # the persistent launches first, the per-step series after them: its launches leave the GPU mostly
+    # idle (the host paces them), and a persistent launch right behind it measured slow
+    order = [("random", "descent", "pibt")] * (args.pairs + 1) + [("per-step",)] * (args.pairs + 1)
+    for rep, keys in enumerate(order):    # round 0 of each phase is untimed: first touch of the buffers, code load
+        rep %= args.pairs + 1
+        for k in keys:
+            if k not in launch:
+                continue
+            fn = launch[k]
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if rep:
+                times[k].append(round(a.elapsed_time(b) * 1e3 / T, 4))
+            if k in ("descent", "pibt") and slots:
+                steps = float(T * B)
+                quality[k] = {"goals": round(float(out["goals_reached"].sum()) / steps, 5),
+                              "status_-3": round(float((out["status"] == -3).sum()) / steps, 5),
+                              "status_-2": round(float((out["status"] == -2).sum()) / steps, 5),
+                              "rewritten": round(float((out["actions_fixed"] != acts).sum()) / steps, 5)}
+    c = sum(e.counters() for e in envs.values())
+    print(json.dumps({"config": args.config, "envs": B, "buffers": "slots" if slots else "in place",
+                      "lib": os.path.basename(_lib.LIB_PATH), "T": T, "us_per_step": times, "plan": plan,
+                      "per_env_step": quality, "counters": [int(x) for x in c[:8]]}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="c2", choices=["c2", "c4", "c5"])
+    ap.add_argument("--envs", type=int, default=0, help="envs instead of the preset's (a partly filled chip)")
+    ap.add_argument("--T", type=int, default=0, help="steps per launch (default 256, c5: 87)")
+    ap.add_argument("--pairs", type=int, default=6, help="timed rounds per process")
+    ap.add_argument("--rounds", type=int, default=3, help="with --baseline-lib: baseline / this build alternations")
+    ap.add_argument("--lib", default=None, help="library to measure (default: the package's)")
+    ap.add_argument("--baseline-lib", default=None, help="a baseline build to alternate with (random and descent only)")
+    ap.add_argument("--inplace", action="store_true", help="the [B]-leading buffers instead of [T]-slot buffers")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child or not args.baseline_lib:
+        measure(args)
+        return
+    series = {"baseline random": [], "baseline descent": [], "random": [], "descent": [], "pibt": [], "per-step": []}
+    for r in range(args.rounds):
+        for which, lib in (("baseline", args.baseline_lib), ("new", args.lib)):
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", "--config", args.config, "--T", str(args.T),
+                   "--pairs", str(args.pairs)] + (["--lib", lib] if lib else []) + (["--inplace"] if args.inplace else []) + ["--envs", str(args.envs)]
+            res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            if res.returncode != 0:
+                sys.stderr.write(res.stderr[-3000:])
+                raise SystemExit(f"round {r} {which}: exit {res.returncode}")
+            d = json.loads(res.stdout.strip().splitlines()[-1])
+            print(r, which, json.dumps(d), flush=True)
+            for k, v in d["us_per_step"].items():
+                series[("baseline " if which == "baseline" else "") + k] += v
+    print(f"\n{args.config} ({d['envs']} envs): us per step, per launch of T = {d['T']} steps " +
+          ("in place" if args.inplace else "into slots (launcher, band-clean after its first call)"))
+    stat = {}
+    for k, v in series.items():
+        stat[k] = (statistics.median(v), min(v), max(v))
+        print(f"  {k:16s} n={len(v):3d} median {stat[k][0]:9.3f} min {stat[k][1]:9.3f} max {stat[k][2]:9.3f}")
+    print(f"  per env-step, last launch: {d['per_env_step']}")
+    for k in ("random", "descent"):
+        bm, lo, hi = stat["baseline " + k]
+        print(f"  (i)  {k} median {stat[k][0]:.3f} inside the baseline's [{lo:.3f}, {hi:.3f}]: "
+              f"{'PASS' if lo <= stat[k][0] <= hi else 'FAIL'}")
+    pm, plo, phi = stat["per-step"]
+    print(f"  (ii) pibt median {stat['pibt'][0]:.3f} < per-step {pm:.3f} - spread {phi - plo:.3f} = {pm - (phi - plo):.3f}: "
+          f"{'PASS' if stat['pibt'][0] < pm - (phi - plo) else 'FAIL'}")
+
+
+if __name__ == "__main__":
+    main()
