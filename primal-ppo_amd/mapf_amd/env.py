@@ -48,6 +48,19 @@ def parse_tuning(text):
     return out
 
 
+# rollout policy (its name in the plan texts: ",tape", ",descent", ",pibt") -> the library's (rollout, plan) calls
+ROLLOUT_POLICIES = {"random": ("mapf_rollout_random", "mapf_rollout_plan"),
+                    "tape": ("mapf_rollout_actions", "mapf_rollout_actions_plan"),
+                    "descent": ("mapf_rollout_descent", "mapf_rollout_descent_plan"),
+                    "pibt": ("mapf_rollout_pibt", "mapf_rollout_pibt_plan")}
+
+
+def _policy_symbols(policy):
+    if policy not in ROLLOUT_POLICIES:
+        raise ValueError(f"policy: expected one of {sorted(ROLLOUT_POLICIES)}, got {policy!r}")
+    return ROLLOUT_POLICIES[policy]
+
+
 class BatchedMapfGym:
     """B environments x N agents on one GPU (one handle per process/GPU)."""
 
@@ -130,52 +143,47 @@ class BatchedMapfGym:
         return ((_lib.SLOTS | (_lib.SLOTS_BAND_CLEAN if band_clean else 0)) if slots else 0) | \
             (_lib.SLOTS_OBS_BITS if obs_bits else 0)
 
-    def _plan(self, fn, slots, band_clean, obs_bits=False):
-        """The text of one of the mapf_rollout_*plan calls."""
+    def rollout_plan(self, slots=False, band_clean=False, obs_bits=False, *, policy="random"):
+        """The kernel (template instantiation + form) a rollout under `policy` launches now, as text
+        (the policy's mapf_rollout_*plan call).  band_clean: for a slots launch with MAPF_SLOTS_BAND_CLEAN;
+        obs_bits: for a packed launch, MAPF_SLOTS_OBS_BITS -- ",bits" inside the angle brackets.  A policy
+        other than "random" comes last inside them (",tape", ",descent", ",pibt"; descent and pibt take the
+        wide three-wave form with bfsobs=0); where the call runs per-step launches the text is "step_observe",
+        "descent_actions+step_observe" or "pibt_actions+step_observe".  mapf.h lists the kernels' symbols."""
+        fn = getattr(_lib.lib(), _policy_symbols(policy)[1])
         buf = ctypes.create_string_buffer(512)
         kind = fn(self.h, self._slot_bits(slots, band_clean, obs_bits), buf, 512)
         if kind < 0:
             _lib.check(kind)
         return buf.value.decode()
 
-    def rollout_plan(self, slots=False, band_clean=False, obs_bits=False):
-        """The kernel (template instantiation + form) mapf_rollout_random launches now, as text
-        (band_clean: for a slots launch with MAPF_SLOTS_BAND_CLEAN; obs_bits: for a packed launch,
-        MAPF_SLOTS_OBS_BITS -- ",bits" inside the angle brackets; the same for the plans below)."""
-        return self._plan(_lib.lib().mapf_rollout_plan, slots, band_clean, obs_bits)
-
-    def rollout_kernel_name(self, slots=False, obs_bits=False):
-        """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,false>'."""
-        return self.rollout_plan(slots, obs_bits=obs_bits).split(" ")[0]
+    def rollout_kernel_name(self, slots=False, obs_bits=False, *, band_clean=False, policy="random"):
+        """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,tape>' under "tape"."""
+        return self.rollout_plan(slots, band_clean, obs_bits, policy=policy).split(" ")[0]
 
     def rollout_actions_plan(self, slots=False, band_clean=False, obs_bits=False):
-        """rollout_plan for rollout_actions (mapf_rollout_actions_plan): the same text with ",tape"
-        inside the angle brackets, or "step_observe" where the call runs per-step launches."""
-        return self._plan(_lib.lib().mapf_rollout_actions_plan, slots, band_clean, obs_bits)
+        """rollout_plan(policy="tape")."""
+        return self.rollout_plan(slots, band_clean, obs_bits, policy="tape")
 
     def rollout_actions_kernel_name(self, slots=False, band_clean=False, obs_bits=False):
-        """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,tape>'."""
-        return self.rollout_actions_plan(slots, band_clean, obs_bits).split(" ")[0]
+        """rollout_kernel_name(policy="tape")."""
+        return self.rollout_kernel_name(slots, obs_bits, band_clean=band_clean, policy="tape")
 
     def rollout_descent_plan(self, slots=False, band_clean=False, obs_bits=False):
-        """rollout_plan for rollout_descent (mapf_rollout_descent_plan): the same text with ",descent"
-        inside the angle brackets (the wide three-wave form with bfsobs=0), or
-        "descent_actions+step_observe" where the call runs per-step launches."""
-        return self._plan(_lib.lib().mapf_rollout_descent_plan, slots, band_clean, obs_bits)
+        """rollout_plan(policy="descent")."""
+        return self.rollout_plan(slots, band_clean, obs_bits, policy="descent")
 
     def rollout_descent_kernel_name(self, slots=False, band_clean=False, obs_bits=False):
-        """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,descent>'."""
-        return self.rollout_descent_plan(slots, band_clean, obs_bits).split(" ")[0]
+        """rollout_kernel_name(policy="descent")."""
+        return self.rollout_kernel_name(slots, obs_bits, band_clean=band_clean, policy="descent")
 
     def rollout_pibt_plan(self, slots=False, band_clean=False, obs_bits=False):
-        """rollout_plan for rollout_pibt (mapf_rollout_pibt_plan): the same text with ",pibt" inside the
-        angle brackets (the wide three-wave form with bfsobs=0), or "pibt_actions+step_observe" where
-        the call runs per-step launches.  The text names the form; mapf.h lists the kernels' symbols."""
-        return self._plan(_lib.lib().mapf_rollout_pibt_plan, slots, band_clean, obs_bits)
+        """rollout_plan(policy="pibt")."""
+        return self.rollout_plan(slots, band_clean, obs_bits, policy="pibt")
 
     def rollout_pibt_kernel_name(self, slots=False, band_clean=False, obs_bits=False):
-        """The template instantiation alone, e.g. 'rollout_wide3_kernel<u64,1,true,pibt>'."""
-        return self.rollout_pibt_plan(slots, band_clean, obs_bits).split(" ")[0]
+        """rollout_kernel_name(policy="pibt")."""
+        return self.rollout_kernel_name(slots, obs_bits, band_clean=band_clean, policy="pibt")
 
     @staticmethod
     def _make_stepout(out):
@@ -366,12 +374,20 @@ class BatchedMapfGym:
         _lib.check(fn(self.h, _ptr(actions), ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return (self.out if out is None else out), obs, vec
 
-    def rollout_random(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False,
-                       obs_bits=False):
-        """T x step_observe(random_policy=True) -- runner.py:64-100 with the uniform random
-        policy, T times -- as ONE launch where mapf_rollout_random_fused (each wave owns an
-        env and loops step -> observe -> its search work).  slots: step t writes slot t of
-        [T]-leading buffers (actions [T, B, N], obs [T, B, N, C, F, F], vec [T, B, N, 4],
+    def rollout(self, T=None, policy="random", *, slots=False, actions=None, tape=None, obs=None, vec=None, out=None,
+                band_clean=False, obs_bits=False):
+        """T x (the policy's actions, step_observe) -- runner.py:64-100, T times -- as ONE launch where
+        rollout_fused (each wave owns an env and loops step -> observe -> its search work; the kernel
+        is rollout_plan(policy=...)), else per-step launches; identical results.  policy:
+          "random"   uniform random, drawn in the kernel (mapf_rollout_random);
+          "tape"     the caller's policy (mapf_rollout_actions): tape int32 [T, B, N] on the device,
+                     read by the launch (not by this call), always [T]-leading, T = tape.shape[0];
+                     values outside 0..4 are counted as bad actions and played as 0;
+                     out["actions_fixed"] is what was executed and must not overlap the tape;
+          "descent"  the heuristic baseline, every agent one step down its own BFS map (needs keep_bfs);
+          "pibt"     the collision-free baseline, the PIBT planner (needs keep_bfs), its ages included.
+        `actions` receives the drawn or chosen actions (not used under "tape").  slots: step t writes
+        slot t of [T]-leading buffers (actions [T, B, N], obs [T, B, N, C, F, F], vec [T, B, N, 4],
         out[k] [T, ...]); otherwise every step overwrites the [B]-leading buffers.
         band_clean (with slots): the caller's promise that the zero band of every slot of `obs`
         (channel 5 while use_hp is off) already holds zeros, e.g. from an earlier call on the same
@@ -379,6 +395,29 @@ class BatchedMapfGym:
         obs_bits: `obs` is the packed observation buffer, int32 [T, B, N, WPA] (slots) or [B, N, WPA]
         (default: this env's own), one bit per cell (MAPF_SLOTS_OBS_BITS; band_clean is then ignored).
         Returns (out, obs, vec)."""
+        symbol = _policy_symbols(policy)[0]
+        if policy == "tape":
+            n = self._check_tape(tape)
+            if T is not None and int(T) != n:
+                raise ValueError(f"T = {T} but the tape holds {n} steps")
+            T = n
+        elif tape is not None:
+            raise ValueError(f"tape= goes with policy='tape', not {policy!r}")
+        elif policy != "random":
+            T = int(T)
+            if T < 0:
+                raise ValueError("T must be >= 0")
+        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
+                                                           tape=tape, obs_bits=obs_bits)
+        if T == 0 and policy != "random":   # nothing to play (an empty tensor has no address to hand over)
+            return out, obs, vec
+        _lib.check(getattr(_lib.lib(), symbol)(self.h, int(T), self._slot_bits(slots, band_clean, obs_bits), _ptr(actions),
+                                               ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
+        return out, obs, vec
+
+    def rollout_random(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False,
+                       obs_bits=False):
+        """rollout(T, "random", ...); the default in-place call takes the cached-argument path below."""
         if not obs_bits and not slots and actions is None and obs is None and vec is None and out is None:
             # the default [B]-leading buffers (checked at construction): the call's arguments are
             # built once -- a 20-step rollout takes ~300 us on the GPU, so the host's ~8 us of
@@ -391,11 +430,8 @@ class BatchedMapfGym:
             _, fn, h, so, pa, po, pv = fast
             _lib.check(fn(h, int(T), 0, pa, so, po, pv, _stream(self.device)))
             return self.out, self.obs, self.vec
-        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
-                                                           obs_bits=obs_bits)
-        _lib.check(_lib.lib().mapf_rollout_random(self.h, int(T), self._slot_bits(slots, band_clean, obs_bits), _ptr(actions),
-                                                  ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
-        return out, obs, vec
+        return self.rollout(T, "random", slots=slots, actions=actions, obs=obs, vec=vec, out=out, band_clean=band_clean,
+                            obs_bits=obs_bits)
 
     def _check_tape(self, tape, T=None):
         """An action tape: int32 [T, B, N], contiguous, on the handle's GPU (the kernels read it
@@ -433,61 +469,25 @@ class BatchedMapfGym:
         return actions, self._make_stepout(out), out, obs, vec
 
     def rollout_actions(self, tape, slots=False, obs=None, vec=None, out=None, band_clean=False, obs_bits=False):
-        """T x step_observe(tape[t]) -- the caller's policy, T = tape.shape[0] steps -- as ONE launch
-        where rollout_fused (the rollout kernels' tape instantiations, rollout_actions_plan), else
-        T per-step launches; identical results.  tape: int32 [T, B, N] on the device, read by the
-        launch (not by this call), always [T]-leading; values outside 0..4 are counted as bad
-        actions and played as 0.  slots, obs, vec, out, band_clean, obs_bits: as rollout_random;
-        out["actions_fixed"] is what was executed and must not overlap the tape.
-        Returns (out, obs, vec)."""
-        T = self._check_tape(tape)
-        tape, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, tape=tape,
-                                                        obs_bits=obs_bits)
-        if T == 0:          # nothing to play (an empty tensor has no address to hand over)
-            return out, obs, vec
-        _lib.check(_lib.lib().mapf_rollout_actions(self.h, T, self._slot_bits(slots, band_clean, obs_bits), _ptr(tape),
-                                                   ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
-        return out, obs, vec
+        """rollout(policy="tape", tape=tape, ...)."""
+        return self.rollout(None, "tape", slots=slots, tape=tape, obs=obs, vec=vec, out=out, band_clean=band_clean,
+                            obs_bits=obs_bits)
 
     def rollout_descent(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False,
                         obs_bits=False):
-        """T x (descent_actions, step_observe) -- every agent one step down its own BFS map, the
-        heuristic baseline (mapf_rollout_descent; needs keep_bfs) -- as ONE launch where
-        rollout_fused (the rollout kernels' descent instantiations, rollout_descent_plan), else T
-        pairs of per-step launches; identical results.  `actions` receives the chosen actions;
-        slots, actions, obs, vec, out, band_clean, obs_bits: as rollout_random.  Returns (out, obs, vec)."""
-        T = int(T)
-        if T < 0:
-            raise ValueError("T must be >= 0")
-        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
-                                                           obs_bits=obs_bits)
-        if T == 0:          # nothing to play (an empty tensor has no address to hand over)
-            return out, obs, vec
-        _lib.check(_lib.lib().mapf_rollout_descent(self.h, T, self._slot_bits(slots, band_clean, obs_bits), _ptr(actions),
-                                                   ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
-        return out, obs, vec
+        """rollout(T, "descent", ...)."""
+        return self.rollout(T, "descent", slots=slots, actions=actions, obs=obs, vec=vec, out=out, band_clean=band_clean,
+                            obs_bits=obs_bits)
 
     def rollout_pibt(self, T, slots=False, actions=None, obs=None, vec=None, out=None, band_clean=False,
                      obs_bits=False):
-        """T x (pibt_actions, step_observe) -- the PIBT planner, the collision-free baseline
-        (mapf_rollout_pibt; needs keep_bfs) -- as ONE launch where rollout_fused (the rollout kernels'
-        PIBT forms, rollout_pibt_plan), else T pairs of per-step launches; identical
-        results, the policy's ages included.  `actions` receives the chosen actions; slots, actions,
-        obs, vec, out, band_clean, obs_bits: as rollout_random.  Returns (out, obs, vec)."""
-        T = int(T)
-        if T < 0:
-            raise ValueError("T must be >= 0")
-        actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
-                                                           obs_bits=obs_bits)
-        if T == 0:          # nothing to play (an empty tensor has no address to hand over)
-            return out, obs, vec
-        _lib.check(_lib.lib().mapf_rollout_pibt(self.h, T, self._slot_bits(slots, band_clean, obs_bits), _ptr(actions),
-                                                ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
-        return out, obs, vec
+        """rollout(T, "pibt", ...)."""
+        return self.rollout(T, "pibt", slots=slots, actions=actions, obs=obs, vec=vec, out=out, band_clean=band_clean,
+                            obs_bits=obs_bits)
 
     def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None, actions_in=None,
                          policy="random", obs_bits=False):
-        """rollout_random(T, slots, ...) prepared once: the buffers are checked and the C call's
+        """rollout(T, policy, slots=slots, ...) prepared once: the buffers are checked and the C call's
         arguments built now, on the current stream; the returned callable issues the launch with
         no per-call host work beyond one ctypes call (a 20-step rollout is ~350 us on the GPU, the
         checks and wrapping ~60 us of host time).  The launcher keeps its buffers alive.
@@ -499,30 +499,27 @@ class BatchedMapfGym:
         non-zeros into that band of `obs`.  Whoever does (or hands the memory to something that
         may) calls launch.invalidate(): the next call stores everything again.
 
-        actions_in: an int32 [T, B, N] tape -- the launcher then issues rollout_actions(actions_in,
-        slots, ...) instead (`actions` is not used), under the same band rule.  The tape's contents
-        are read at launch time: refill the same tensor between calls to play other actions.
+        actions_in: an int32 [T, B, N] tape -- the launcher then issues the "tape" policy over it (`actions`
+        is not used); its contents are read at launch time: refill the tensor to play other actions.
+        policy: "random" (the default), "descent" or "pibt", as rollout(); these and actions_in exclude
+        each other.  The band rule holds for every policy.
 
-        policy: "random" (the default), "descent" or "pibt" -- the launcher then issues
-        rollout_descent / rollout_pibt(T, slots, actions, ...) under the same band rule.  A policy
-        other than "random" and actions_in exclude each other.
-
-        obs_bits: `obs` is the packed int32 buffer (as rollout_random); every call stores every word
+        obs_bits: `obs` is the packed int32 buffer (as rollout()); every call stores every word
         (the band rule does not apply)."""
-        if policy not in ("random", "descent", "pibt"):
-            raise ValueError(f"policy: expected 'random', 'descent' or 'pibt', got {policy!r}")
-        if policy != "random" and actions_in is not None:
-            raise ValueError("policy and actions_in are mutually exclusive")
+        _policy_symbols(policy)
         if actions_in is not None:
+            if policy not in ("random", "tape"):
+                raise ValueError("policy and actions_in are mutually exclusive")
+            policy = "tape"
             self._check_tape(actions_in, int(T))
+        elif policy == "tape":
+            raise ValueError("policy='tape' needs its tape: actions_in=...")
         actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
                                                            tape=actions_in, obs_bits=obs_bits)
         args = (self.h, int(T), self._slot_bits(slots, False, obs_bits), _ptr(actions), ctypes.byref(so), _ptr(obs),
                 _ptr(vec), _stream(self.device))
         clean = args[:2] + (self._slot_bits(slots, not obs_bits, obs_bits),) + args[3:]
-        fn = (_lib.lib().mapf_rollout_actions if actions_in is not None else
-              _lib.lib().mapf_rollout_descent if policy == "descent" else
-              _lib.lib().mapf_rollout_pibt if policy == "pibt" else _lib.lib().mapf_rollout_random)
+        fn = getattr(_lib.lib(), _policy_symbols(policy)[0])
         keep = (so, actions, obs, vec, out)
         state = [args]                  # the next call's arguments: `clean` once a call has stored the band
 

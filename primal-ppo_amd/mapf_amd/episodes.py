@@ -176,27 +176,26 @@ def _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human
     return env
 
 
-def descent_policy():
-    """The heuristic baseline as a policy(obs, vec, env, t) for evaluate_fixed_episodes: every agent
-    one step down its own BFS map (env.descent_actions, mapf_descent_actions), ignoring the other
-    agents and the human.  The env must keep the agents' BFS maps:
-    evaluate_fixed_episodes(..., keep_bfs=True)."""
+def _bfs_policy(method, name):
+    """A policy(obs, vec, env, t) for evaluate_fixed_episodes that calls env.<method>(); the env must
+    keep the agents' BFS maps: evaluate_fixed_episodes(..., keep_bfs=True)."""
     def policy(obs, vec, env, t):
         if not env.cfg.keep_bfs:
-            raise RuntimeError("descent_policy needs the agents' BFS maps: evaluate_fixed_episodes(..., keep_bfs=True)")
-        return env.descent_actions()
+            raise RuntimeError(f"{name} needs the agents' BFS maps: evaluate_fixed_episodes(..., keep_bfs=True)")
+        return getattr(env, method)()
     return policy
+
+
+def descent_policy():
+    """The heuristic baseline: every agent one step down its own BFS map (env.descent_actions,
+    mapf_descent_actions), ignoring the other agents and the human."""
+    return _bfs_policy("descent_actions", "descent_policy")
 
 
 def pibt_policy():
-    """The PIBT planner as a policy(obs, vec, env, t) for evaluate_fixed_episodes: one collision-free
-    step for all agents from their BFS maps (env.pibt_actions, mapf_pibt_actions).  The env must keep
-    the agents' BFS maps: evaluate_fixed_episodes(..., keep_bfs=True)."""
-    def policy(obs, vec, env, t):
-        if not env.cfg.keep_bfs:
-            raise RuntimeError("pibt_policy needs the agents' BFS maps: evaluate_fixed_episodes(..., keep_bfs=True)")
-        return env.pibt_actions()
-    return policy
+    """The PIBT planner: one collision-free step for all agents from their BFS maps
+    (env.pibt_actions, mapf_pibt_actions)."""
+    return _bfs_policy("pibt_actions", "pibt_policy")
 
 
 def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, use_da=False, use_hp=False,

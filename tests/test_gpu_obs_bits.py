@@ -17,9 +17,9 @@ import torch
 
 import test_gpu_rollout_tape as tape_tests
 from kernel_registry import record_rollout_kernel
+from rollout_harness import OUT_KEYS, check_state, preset_envs, slot_buffers
 from test_gpu_parity import FUSED_CASES, assert_no_errors, host
-from test_gpu_rollout_tape import (LAUNCHES, OUT_KEYS, PAIR_CASES, case_env, case_setup, check_state, make_tape, oracle_run,
-                                   preset_envs, slot_buffers)
+from test_gpu_rollout_tape import LAUNCHES, PAIR_CASES, case_env, case_setup, make_tape, oracle_run
 from test_obs_bits_cpu import pack_np
 
 pytestmark = pytest.mark.gpu

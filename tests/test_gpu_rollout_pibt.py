@@ -16,23 +16,18 @@ obstacles).
 The file ends with a guard: the PIBT kernel every BASELINE preset launches by default, into slots and
 in place, has been run by an oracle-compared case above (tests/kernel_registry.py).
 """
-import ctypes
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import pibt_ref
+import rollout_harness as H
 from descent_ref import descent_actions
-from kernel_registry import COVERED, record_rollout_kernel
 from oracle import oracle as O
-from test_gpu_parity import (FUSED_CASES, GROUP_CASES, RANDOM_CASES, ROLLOUT_CASES, WIDE_SHAPES, assert_no_errors,
-                             build_maps, host, mk_env)
-from test_gpu_rollout_band import host_skip, set_sentinels
-from test_gpu_rollout_descent import check_actions
-from test_gpu_rollout_tape import OUT_KEYS, check_slots, check_state, slot_buffers
+from rollout_harness import check_actions, check_slots, check_state, slot_buffers
+from test_gpu_parity import FUSED_CASES, GROUP_CASES, RANDOM_CASES, ROLLOUT_CASES, WIDE_SHAPES, host
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +36,8 @@ PIBT_COVERED = set()                         # kernel names this file compared a
 DENSE = "p_n8_8x8_f5_dense"                  # this file's own shape: 8 agents, shared 8 x 8 map, few obstacles
 CASES = {**FUSED_CASES, **GROUP_CASES, **ROLLOUT_CASES, **RANDOM_CASES, **WIDE_SHAPES,
          DENSE: dict(B=24, H=8, W=8, n=8, fov=5, nch=6, map="sparse_shared", map_seed=2)}
+SEED = 0x91B70000
+covered = functools.partial(H.covered, "pibt", PIBT_COVERED)
 SMALL = ["r_n6_16x16_f9_dahp", "g_n8_20x20_f11_ragged61", "g_n8_20x20_f11", "r_n6_12x12_f7_dense", DENSE]
 WIDE = ["c4_40x40_n16_f9_looping", "dense_12x12_n16_f9_dahp", "c1_10x10_n4_f11", "c5_80x80_n64_f11_bfsch",
         "w_n20_48x90_f11_bfsch"]
@@ -52,30 +49,12 @@ def need_gpu():
         pytest.fail("GPU tests need an MI355X")
 
 
-def covered(kname, what):
-    assert kname.endswith(",pibt>"), kname
-    PIBT_COVERED.add(kname)
-    record_rollout_kernel(kname, what)
-
-
 def case_setup(name):
-    case = CASES[name]
-    if case["map"] == "sparse_shared":
-        from mapf_amd.maps import keep_largest_component, random_map
-        m = random_map(np.random.default_rng(case["map_seed"]), case["H"], case["W"], 0.1)
-        maps, shared = keep_largest_component(m), True
-    else:
-        maps, shared = build_maps(case, case["B"], np.random.default_rng(5))
-    return case, maps, shared, 0x91B70000 + len(name)
+    return H.case_setup(CASES, name, SEED)
 
 
 def case_env(name, tuning=None, **kw):
-    case, maps, shared, seed = case_setup(name)
-    env = mk_env(B=case["B"], H=case["H"], W=case["W"], num_agents=case["n"], fov=case["fov"], num_channel=case["nch"],
-                 use_da=case.get("da", 0), use_hp=case.get("hp", 0), human_mode=case.get("human", "random"),
-                 goal_mode="random", fix_choice=1, shared_map=shared, seed=seed, env_offset=7, tuning=tuning, **kw)
-    env.reset_seeded(maps)
-    return env, case, maps, shared, seed
+    return H.case_env(CASES, name, SEED, tuning, **kw)
 
 
 @functools.lru_cache(maxsize=None)
@@ -85,67 +64,30 @@ def oracle_run(name, steps=int(np.sum(LAUNCHES))):
     the oracle's error count) after every launch of every path, and what the policy did: per step and
     env the failed picks standing on the human's next cell, and the run's inheritance calls,
     backtracks and failed picks."""
-    case, maps, shared, seed = case_setup(name)
-    B, n = case["B"], case["n"]
-    cfg = O.make_config(case["H"], case["W"], n, case["fov"], case["nch"], use_da=case.get("da", 0),
-                        use_hp=case.get("hp", 0), human_mode={"random": 1, "looping": 0}[case.get("human", "random")],
-                        goal_mode=1, fix_choice=1, seed=seed, env_offset=7)
-    bounds = set(np.cumsum(LAUNCHES).tolist()) | set(np.cumsum(LAUNCHES[1:]).tolist()) | set(range(1, 41)) | {steps}
-    ref = {k: [] for k, _ in OUT_KEYS}
-    ref.update(obs=[], vec=[], actions=[], may_hit=[])
-    state = {}
+    n = CASES[name]["n"]
+    ages = [pibt_ref.Ages(n) for _ in range(CASES[name]["B"])]
     stats = dict(inherit=0, backtracks=0, failed=0)
-    oracles, ages = [], []
-    for b in range(B):
-        oe = O.OracleEnv(cfg, env_id=7 + b)
-        oe.reset_random(maps if shared else maps[b])
-        oracles.append(oe)
-        ages.append(pibt_ref.Ages(n))
-    for t in range(steps):
-        row = {k: [] for k in ref}
-        for b, oe in enumerate(oracles):
-            pos, goal = oe.agents()
-            hum = oe.human()
-            world = np.asarray(maps if shared else maps[b], np.int8)
-            a, failed, st = pibt_ref.pibt_actions(world, oe.bfs(), pos, goal, hum["pos"], hum["next"], t, ages[b])
-            stats["inherit"] += st["inherit"]
-            stats["backtracks"] += st["backtracks"]
-            stats["failed"] += len(failed)
-            hit = np.zeros(n, bool)
-            for i in failed:
-                hit[i] = tuple(pos[i]) == tuple(hum["next"])
-            o = oe.step(a)
-            oo, ov = oe.observe()
-            for k, key in OUT_KEYS:
-                row[k].append(np.array(o[key]))
-            row["obs"].append(oo)
-            row["vec"].append(ov)
-            row["actions"].append(a)
-            row["may_hit"].append(hit)
-        for k in ref:
-            ref[k].append(np.stack(row[k]))
-        if t + 1 in bounds:
-            state[t + 1] = dict(pos=np.stack([oe.agents()[0] for oe in oracles]),
-                                goal=np.stack([oe.agents()[1] for oe in oracles]),
-                                hpos=np.stack([oe.human()["pos"] for oe in oracles]),
-                                hgoal=np.stack([oe.human()["goal"] for oe in oracles]),
-                                bfs=np.stack([oe.bfs() for oe in oracles]),
-                                errors=sum(oe.errors() for oe in oracles))
-    ref = {k: np.stack(v) for k, v in ref.items()}
-    for v in ref.values():
-        v.setflags(write=False)
-    return ref, state, stats
+
+    def pick(oe, b, t, world):
+        pos, goal = oe.agents()
+        hum = oe.human()
+        a, failed, st = pibt_ref.pibt_actions(np.asarray(world, np.int8), oe.bfs(), pos, goal, hum["pos"], hum["next"], t, ages[b])
+        stats["inherit"] += st["inherit"]
+        stats["backtracks"] += st["backtracks"]
+        stats["failed"] += len(failed)
+        hit = np.zeros(n, bool)
+        for i in failed:
+            hit[i] = tuple(pos[i]) == tuple(hum["next"])
+        return a, dict(may_hit=hit)
+    bounds = set(np.cumsum(LAUNCHES).tolist()) | set(np.cumsum(LAUNCHES[1:]).tolist()) | set(range(1, 41)) | {steps}
+    return H.oracle_rollout(CASES, name, SEED, steps, bounds, pick) + (stats,)
 
 
 def assert_inputs(name, launches=LAUNCHES):
     """The per-case conditions: goal changes (a stale map or age can only show there) and inheritance."""
     ref, _, stats = oracle_run(name)
-    per_step = ref["goals_reached"].reshape(len(ref["goals_reached"]), -1).sum(1)
-    total = int(np.sum(launches))
-    last = set((np.cumsum(launches) - 1).tolist())
-    inner = sum(int(per_step[t]) for t in range(total) if t not in last)
-    print(f"{name}: {int(per_step[:total].sum())} goal changes in {total} steps, {inner} before a launch's last step; {stats}")
-    assert int(per_step[:total].sum()) >= 20 and inner >= 10, (name, int(per_step[:total].sum()), inner)
+    H.assert_goals_change(name, ref, launches)
+    print(f"{name}: {stats}")
     assert stats["inherit"] >= 50, (name, stats)
     return ref
 
@@ -175,46 +117,10 @@ def test_inputs_exercise_backtracking_and_failed_picks(family, names):
 
 
 def run_pibt_case(name, path, tuning=None, launches=LAUNCHES, expect=None):
-    """path "rollout": [T]-slot buffers, every slot compared; "inplace": the [B]-leading buffers, each
-    launch's last step compared; "inplace1": one-step launches in place, every step compared."""
-    total = int(np.sum(launches))
     ref = assert_inputs(name, launches)
-    state = oracle_run(name)[1]
-    if path == "inplace1":
-        launches = (1,) * 24
-    elif path == "inplace":
-        launches = launches[1:]
-    env, case, _, _, _ = case_env(name, tuning)
-    try:
-        slots = path == "rollout"
-        kname = env.rollout_pibt_kernel_name(slots=slots)
-        plan = env.rollout_pibt_plan(slots=slots)
-        assert kname.endswith(",pibt>"), plan
-        assert kname.replace(",pibt>", ">") == env.rollout_kernel_name(slots=slots), (plan, env.rollout_plan(slots))
-        if kname.startswith("rollout_wide3"):
-            assert " bfsobs=0 " in plan, plan       # the stepping wave searches the maps it reads
-        if expect is not None:
-            assert kname == expect, plan
-        t0 = 0
-        for T in launches:
-            k = T if slots else 1
-            buf = slot_buffers(env, k)
-            acts = torch.full((k, case["B"], case["n"]), -9, dtype=torch.int32, device=env.device)
-            env.rollout_pibt(T, slots=slots, actions=acts, **buf)
-            got = host(buf["out"])
-            what = f"{name} {path} launch [{t0}, {t0 + T})"
-            which = [(q, q) for q in range(T)] if slots else [(0, T - 1)]
-            check_actions(what, ref, t0, acts, which)
-            check_slots(what, ref, t0, got, buf["obs"], buf["vec"], which)
-            assert_consequences(what, ref, t0, got, acts, which)
-            t0 += T
-            check_state(env, state[t0], what)
-        assert_no_errors(env)                      # PIBT leaves fixActions nothing it cannot place
-        assert state[t0]["errors"] == 0
-        covered(kname, f"{name} {path} pibt vs oracle")
-    finally:
-        env.close()
-    assert total >= t0
+    t0 = H.run_policy_case("pibt", case_env, PIBT_COVERED, name, path, ref, oracle_run(name)[1], launches, tuning, expect,
+                           allow=(), hook=assert_consequences)       # PIBT leaves fixActions nothing it cannot place
+    assert int(np.sum(launches)) >= t0
 
 
 # ------------------------------------------------------------------ 1. the pair-lane kernel
@@ -427,128 +333,27 @@ def test_packed_observations_equal_the_floats(name):
 # ------------------------------------------------------------------ 5. the launcher
 @pytest.mark.parametrize("form,subs", [(dict(roll_occ=4, roll_group=1), 4), (None, 1)])
 def test_pibt_launcher_declares_the_band_clean_after_its_first_call(form, subs):
-    """rollout_launcher(policy="pibt") on NaN-prefilled slot buffers: call 1 stores everything;
-    calls 2 and 3 carry MAPF_SLOTS_BAND_CLEAN and leave exactly mapf_obs_band_skip's floats alone
-    (sentinels survive there, every other float and output equals an unflagged twin's)."""
-    name, T = "g_n8_20x20_f11", 23
-    env, case, _, _, seed = case_env(name, form)
-    twin = case_env(name, form)[0]
-    try:
-        kname = env.rollout_pibt_kernel_name(slots=True, band_clean=True)
-        assert kname == "rollout_random_kernel<true,%d,band64,pibt>" % subs
-        acts = torch.full((T, case["B"], case["n"]), -9, dtype=torch.int32, device=env.device)
-        roll = dict(actions=acts, **slot_buffers(env, T))
-        launch = env.rollout_launcher(T, slots=True, actions=acts, obs=roll["obs"], vec=roll["vec"], out=roll["out"],
-                                      policy="pibt")
-        for call in range(3):
-            if call:
-                set_sentinels(roll)
-            launch()
-            ref = slot_buffers(twin, T)
-            ref_acts = torch.full_like(acts, -9)
-            twin.rollout_pibt(T, slots=True, actions=ref_acts, **ref)
-            torch.cuda.synchronize()
-            want = ref["obs"].clone()
-            if call:
-                skip = torch.from_numpy(host_skip(env, case, roll, True)).to(env.device)
-                want.view(skip.shape)[skip] = 7.0
-            assert torch.equal(roll["obs"].view(torch.int32), want.view(torch.int32)), f"call {call}: obs"
-            assert torch.equal(roll["vec"].view(torch.int32), ref["vec"].view(torch.int32)), f"call {call}: vec"
-            assert torch.equal(acts, ref_acts), f"call {call}: actions"
-            for key in ref["out"]:
-                assert torch.equal(roll["out"][key], ref["out"][key]), f"call {call}: {key}"
-        assert_no_errors(env)
-        covered(kname, f"{name} band-clean pibt vs an oracle-compared twin")
-    finally:
-        env.close()
-        twin.close()
+    H.launcher_band_clean_case("pibt", case_env, form, subs, allow=(), mine=PIBT_COVERED)
 
 
 # ------------------------------------------------------------------ 6. capture
 def test_captured_pibt_rollout_continues_the_episode():
-    """One rollout_pibt launch of the c4 shape (the three-wave form) captured into a graph and replayed
-    twice: 2T steps of the episode, every slot of both replays against the oracle -- the ages too are
-    carried from replay to replay through the handle's arrays."""
-    name, T = "c4_40x40_n16_f9_looping", 12
-    ref, state, _ = oracle_run(name)
-    env, case, _, _, _ = case_env(name)
-    g = None
-    try:
-        assert env.rollout_pibt_kernel_name(slots=True) == "rollout_wide3_kernel<u64,1,true,pibt>"
-        buf = slot_buffers(env, T)
-        acts = torch.full((T, case["B"], case["n"]), -9, dtype=torch.int32, device=env.device)
-        torch.cuda.synchronize()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                env.rollout_pibt(T, slots=True, actions=acts, **buf)       # recorded, not run
-        torch.cuda.synchronize()
-        for call in range(2):
-            g.replay()
-            torch.cuda.synchronize()
-            which = [(q, q) for q in range(T)]
-            check_actions(f"replay {call}", ref, call * T, acts, which)
-            check_slots(f"replay {call}", ref, call * T, host(buf["out"]), buf["obs"], buf["vec"], which)
-        check_state(env, state[2 * T], "after two replays")
-        assert_no_errors(env)
-    finally:
-        del g
-        env.close()
+    """The ages too are carried from replay to replay through the handle's arrays."""
+    H.captured_rollout_case("pibt", case_env, *oracle_run("c4_40x40_n16_f9_looping")[:2], allow=())
 
 
 # ------------------------------------------------------------------ 7. errors
 def test_keep_bfs_off_is_a_state_error_and_T0_is_a_no_op():
-    from mapf_amd import _lib
-    from mapf_amd.env import _ptr, _stream
-    env, case, _, _, _ = case_env("r_n6_16x16_f9_dahp")
-    off = case_env("r_n6_16x16_f9_dahp", keep_bfs=False)[0]
-    try:
-        before = env.get_state()
-        env.rollout_pibt(0)
-        assert _lib.lib().mapf_rollout_pibt(env.h, 0, 0, _ptr(env.actions), ctypes.byref(env._stepout), _ptr(env.obs),
-                                            _ptr(env.vec), _stream(env.device)) == 0
-        torch.cuda.synchronize()
-        after = env.get_state()
-        for key in before:
-            np.testing.assert_array_equal(before[key], after[key])
-        L = _lib.lib()
-        assert L.mapf_pibt_actions(off.h, _ptr(off.actions), _stream(off.device)) == -4
-        assert L.mapf_rollout_pibt(off.h, 4, 0, _ptr(off.actions), ctypes.byref(off._stepout), _ptr(off.obs),
-                                   _ptr(off.vec), _stream(off.device)) == -4
-        with pytest.raises(RuntimeError, match="keep_bfs"):
-            off.pibt_actions()
-        with pytest.raises(RuntimeError, match="keep_bfs"):
-            off.rollout_pibt(4)
-    finally:
-        env.close()
-        off.close()
+    H.keep_bfs_off_case("pibt", case_env)
 
 
 # ------------------------------------------------------------------ 8. record and replay of fixed episodes
-G6 = os.path.join(os.path.dirname(__file__), "golden", "g6_episodes")
-
-
 @pytest.mark.parametrize("mtype,da_hp", [(0, False), (1, True)])
 def test_pibt_policy_on_fixed_episodes_replays(mtype, da_hp):
-    """evaluate_fixed_episodes under pibt_policy(), recording its actions, then replay_fixed_episodes
-    over the tapes: integer metrics equal, the float64 sums of float32 terms within 1e-9 relative
-    (summation order only).  The planner reaches goals and never collides with an agent or a wall."""
-    from mapf_amd.episodes import (METRIC_KEYS, evaluate_fixed_episodes, load_fixed_episode_infos, pibt_policy,
-                                   replay_fixed_episodes)
-    infos = load_fixed_episode_infos(G6)
-    steps = 48
-    kw = dict(num_channel=6, fov=9, use_da=da_hp, use_hp=da_hp, human_movement_type=mtype, fix_choice=1)
-    with pytest.raises(RuntimeError, match="keep_bfs=True"):
-        evaluate_fixed_episodes(infos, pibt_policy(), max_steps=1, **kw)
-    got, tapes = evaluate_fixed_episodes(infos, pibt_policy(), max_steps=steps, record_actions=True, keep_bfs=True, **kw)
-    rep = replay_fixed_episodes(infos, tapes, **kw)
-    for key in METRIC_KEYS:
-        if key in ("episodeReward", "episodeCostReward"):
-            np.testing.assert_allclose(rep[key], got[key], rtol=1e-9, atol=0, err_msg=key)
-        else:
-            np.testing.assert_array_equal(rep[key], got[key], err_msg=key)
+    """H.fixed_episodes_case under pibt_policy().  The planner reaches goals and never collides with an
+    agent or a wall."""
+    from mapf_amd.episodes import pibt_policy
+    got = H.fixed_episodes_case(pibt_policy, mtype, da_hp)
     assert got["totalGoals"].sum() > 0
     assert got["staticCollide"].sum() == 0 and got["agentCollide"].sum() == 0
 
@@ -556,16 +361,4 @@ def test_pibt_policy_on_fixed_episodes_replays(mtype, da_hp):
 # ------------------------------------------------------------------ 9. coverage guard (last)
 @pytest.mark.parametrize("cfg", ["c1", "c2", "c4", "c5"])
 def test_default_pibt_kernels_are_covered_by_this_file(cfg):
-    from test_gpu_ycoverage import preset_env
-    if not PIBT_COVERED:
-        pytest.fail("no oracle-compared PIBT case ran before the guard")
-    env = preset_env(cfg)
-    try:
-        assert env.rollout_fused, cfg
-        for slots in (False, True):
-            name = env.rollout_pibt_kernel_name(slots)
-            assert name in PIBT_COVERED and name in COVERED, (
-                f"{cfg} slots={slots}: {env.rollout_pibt_plan(slots)} is launched by default but no compared "
-                f"case of this file ran it; covered: {sorted(PIBT_COVERED)}")
-    finally:
-        env.close()
+    H.coverage_guard("pibt", PIBT_COVERED, cfg)

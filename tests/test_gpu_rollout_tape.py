@@ -12,39 +12,30 @@ and in place, has been run by an oracle- or fixture-compared case above (tests/k
 """
 import ctypes
 import functools
-import os
 
 import numpy as np
 import pytest
 import torch
 
+import rollout_harness as H
 from golden_io import G1_NAMES, load, unpack_obs
-from kernel_registry import COVERED, record_rollout_kernel
-from oracle import oracle as O
-from test_gpu_parity import (GROUP_CASES, RANDOM_CASES, ROLLOUT_CASES, WIDE_SHAPES, assert_no_errors, build_maps,
-                             c5_maps, host, mk_env)
-from test_gpu_rollout_band import host_skip, set_sentinels
+from rollout_harness import host_skip, preset_envs, set_sentinels, slot_buffers
+from test_gpu_parity import GROUP_CASES, RANDOM_CASES, ROLLOUT_CASES, WIDE_SHAPES, assert_no_errors, host, mk_env
 
 pytestmark = pytest.mark.gpu
 
 TAPE_K = 32                                  # csrc/mapf_fused.hip: steps of the tape staged in LDS at a time
 LAUNCHES = (1, 23, 67, TAPE_K, TAPE_K + 1)   # steps per launch, in this order
-OUT_KEYS = [("status", "status"), ("reward", "reward"), ("cost", "cost"), ("train_valid", "valid"),
-            ("actions_fixed", "fixed"), ("goals_reached", "goals"), ("constraints", "constr"), ("shadow_goals", "shadow")]
 TAPE_COVERED = set()                         # kernel names this file compared against the oracle or a fixture
 CASES = {**GROUP_CASES, **ROLLOUT_CASES, **RANDOM_CASES, **WIDE_SHAPES}
+SEED = 0x5EED0000
+covered = functools.partial(H.covered, "tape", TAPE_COVERED)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def need_gpu():
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need an MI355X")
-
-
-def covered(kname, what):
-    assert kname.endswith(",tape>"), kname
-    TAPE_COVERED.add(kname)
-    record_rollout_kernel(kname, what)
 
 
 def make_tape(T, B, n, seed, bad=False):
@@ -66,25 +57,11 @@ def make_tape(T, B, n, seed, bad=False):
 
 
 def case_setup(name):
-    case = CASES[name]
-    maps, shared = build_maps(case, case["B"], np.random.default_rng(5))
-    return case, maps, shared, 0x5EED0000 + len(name)
+    return H.case_setup(CASES, name, SEED)
 
 
 def case_env(name, tuning=None):
-    case, maps, shared, seed = case_setup(name)
-    env = mk_env(B=case["B"], H=case["H"], W=case["W"], num_agents=case["n"], fov=case["fov"], num_channel=case["nch"],
-                 use_da=case.get("da", 0), use_hp=case.get("hp", 0), human_mode=case.get("human", "random"),
-                 goal_mode="random", fix_choice=1, shared_map=shared, seed=seed, env_offset=7, tuning=tuning)
-    env.reset_seeded(maps)
-    return env, case, maps, shared, seed
-
-
-def slot_buffers(env, k, fill=float("nan")):
-    return dict(obs=torch.full((k,) + tuple(env.obs.shape), fill, device=env.device),
-                vec=torch.full((k,) + tuple(env.vec.shape), fill, device=env.device),
-                out={key: torch.full((k,) + tuple(v.shape), -7, dtype=v.dtype, device=env.device)
-                     for key, v in env.out.items()})
+    return H.case_env(CASES, name, SEED, tuning)
 
 
 @functools.lru_cache(maxsize=None)
@@ -92,104 +69,15 @@ def oracle_run(name, steps):
     """The oracle playing make_tape's first `steps` rows of the case, computed once and shared
     (read-only): the tape, per-step outputs / observations / vectors [steps, B, ...], and the state
     (cells, goals, human, BFS maps, the oracle's error count) after every launch of every path."""
-    case, maps, shared, seed = case_setup(name)
-    B, n = case["B"], case["n"]
-    tape = make_tape(steps, B, n, seed)
-    cfg = O.make_config(case["H"], case["W"], n, case["fov"], case["nch"], use_da=case.get("da", 0),
-                        use_hp=case.get("hp", 0), human_mode={"random": 1, "looping": 0}[case.get("human", "random")],
-                        goal_mode=1, fix_choice=1, seed=seed, env_offset=7)
+    case, _, _, seed = case_setup(name)
+    tape = make_tape(steps, case["B"], case["n"], seed)
     bounds = set(np.cumsum(LAUNCHES).tolist()) | set(np.cumsum(LAUNCHES[1:]).tolist()) | set(range(1, 25)) | {steps}
-    ref = {k: [] for k, _ in OUT_KEYS}
-    ref.update(obs=[], vec=[])
-    state = {}
-    oracles = []
-    for b in range(B):
-        oe = O.OracleEnv(cfg, env_id=7 + b)
-        oe.reset_random(maps if shared else maps[b])
-        oracles.append(oe)
-    for t in range(steps):
-        row = {k: [] for k in ref}
-        for b, oe in enumerate(oracles):
-            o = oe.step(tape[t, b])
-            oo, ov = oe.observe()
-            for k, key in OUT_KEYS:
-                row[k].append(np.array(o[key]))
-            row["obs"].append(oo)
-            row["vec"].append(ov)
-        for k in ref:
-            ref[k].append(np.stack(row[k]))
-        if t + 1 in bounds:
-            state[t + 1] = dict(pos=np.stack([oe.agents()[0] for oe in oracles]),
-                                goal=np.stack([oe.agents()[1] for oe in oracles]),
-                                hpos=np.stack([oe.human()["pos"] for oe in oracles]),
-                                hgoal=np.stack([oe.human()["goal"] for oe in oracles]),
-                                bfs=np.stack([oe.bfs() for oe in oracles]),
-                                errors=sum(oe.errors() for oe in oracles))
-    ref = {k: np.stack(v) for k, v in ref.items()}
-    for v in ref.values():
-        v.setflags(write=False)
-    return tape, ref, state
-
-
-def check_state(env, state, what):
-    st = env.get_state()
-    np.testing.assert_array_equal(st["pos"], state["pos"], err_msg=f"{what}: pos")
-    np.testing.assert_array_equal(st["goal"], state["goal"], err_msg=f"{what}: goal")
-    np.testing.assert_array_equal(st["human"][:, 0:2], state["hpos"], err_msg=f"{what}: human pos")
-    np.testing.assert_array_equal(st["human"][:, 4:6], state["hgoal"], err_msg=f"{what}: human goal")
-    np.testing.assert_array_equal(env.bfs().cpu().numpy(), state["bfs"], err_msg=f"{what}: bfs")
-
-
-def check_slots(what, ref, t0, got_out, obs, vec, slots):
-    """slots: [(slot index in the buffers, step index relative to t0)] to compare, every bit."""
-    obs, vec = obs.cpu().numpy(), vec.cpu().numpy()
-    for k, dt in slots:
-        t = t0 + dt
-        for key, _ in OUT_KEYS:
-            want = ref[key][t].astype(got_out[key].dtype).reshape(got_out[key][k].shape)
-            assert np.array_equal(got_out[key][k], want), f"{what} t={t}: {key}"
-        want = ref["vec"][t].astype(np.float32).reshape(vec[k].shape)
-        assert np.array_equal(vec[k].view(np.uint32), want.view(np.uint32)), f"{what} t={t}: vec"
-        want = ref["obs"][t].astype(np.float32).reshape(obs[k].shape)
-        bad = np.argwhere(obs[k].view(np.uint32) != want.view(np.uint32))
-        assert len(bad) == 0, f"{what} t={t}: {len(bad)} obs floats differ, first (b, agent, ch, y, x) = {bad[0]}"
+    return (tape,) + H.oracle_rollout(CASES, name, SEED, steps, bounds, lambda oe, b, t, world: (tape[t, b], None))
 
 
 def run_tape_case(name, path, tuning=None, launches=LAUNCHES, expect=None):
-    """path "rollout": [T]-slot buffers, every slot compared; "inplace": the [B]-leading buffers, each
-    launch's last step compared; "inplace1": one-step launches in place, every step compared."""
-    total = int(np.sum(launches))
-    if path == "inplace1":
-        launches = (1,) * 24
-    elif path == "inplace":
-        launches = launches[1:]
-    tape_h, ref, state = oracle_run(name, total)
-    env, case, _, _, _ = case_env(name, tuning)
-    try:
-        slots = path == "rollout"
-        kname = env.rollout_actions_kernel_name(slots=slots)
-        assert kname.endswith(",tape>"), env.rollout_actions_plan(slots=slots)
-        assert kname.replace(",tape>", ">") == env.rollout_kernel_name(slots=slots), (kname, env.rollout_plan(slots))
-        if expect is not None:
-            assert kname == expect, env.rollout_actions_plan(slots=slots)
-        tape = torch.from_numpy(tape_h).to(env.device)
-        t0 = 0
-        for T in launches:
-            buf = slot_buffers(env, T if slots else 1)
-            env.rollout_actions(tape[t0:t0 + T], slots=slots, **buf)
-            got = host(buf["out"])
-            what = f"{name} {path} launch [{t0}, {t0 + T})"
-            check_slots(what, ref, t0, got, buf["obs"], buf["vec"],
-                        [(k, k) for k in range(T)] if slots else [(0, T - 1)])
-            t0 += T
-            check_state(env, state[t0], what)
-        # a numpy tape may box an agent in where the random policy's did not (counters 1, 2): the
-        # oracle counts the same events, and nothing else is ever counted
-        assert_no_errors(env, allow=(1, 2))
-        assert int(env.counters()[:8].sum()) == state[t0]["errors"]
-        covered(kname, f"{name} {path} tape vs oracle")
-    finally:
-        env.close()
+    tape, ref, state = oracle_run(name, int(np.sum(launches)))
+    H.run_policy_case("tape", case_env, TAPE_COVERED, name, path, ref, state, launches, tuning, expect, tape=tape)
 
 
 # ------------------------------------------------------------------ 1. the pair-lane kernel
@@ -282,21 +170,6 @@ def test_reference_episode_through_the_persistent_kernel(name):
 
 
 # ------------------------------------------------------------------ 4. replay equals record, full size
-def preset_envs(cfg, count):
-    import bench
-    from mapf_amd.maps import generate_warehouse
-    p = bench.PRESETS[cfg]
-    maps = generate_warehouse(p["size"], p["size"]) if p["maps"] == "warehouse" else c5_maps(p["envs"])
-    envs = []
-    for _ in range(count):
-        e = mk_env(B=p["envs"], H=p["size"], W=p["size"], num_agents=p["agents"], fov=p["fov"],
-                   num_channel=p["channels"], human_mode="random", goal_mode="random", fix_choice=1, seed=1234,
-                   shared_map=p["maps"] == "warehouse")
-        e.reset_seeded(maps)
-        envs.append(e)
-    return envs
-
-
 @pytest.mark.parametrize("cfg,T,slots", [("c2", 8, True), ("c4", 8, True), ("c5", 4, True), ("c2", 8, False)])
 def test_replay_equals_record_at_full_size(cfg, T, slots):
     """rollout_random on one handle, rollout_actions over its recorded actions on a twin: every
@@ -492,9 +365,6 @@ def test_tape_may_not_overlap_actions_fixed_and_T0_is_a_no_op():
 
 
 # ------------------------------------------------------------------ 9. record and replay of fixed episodes
-G6 = os.path.join(os.path.dirname(__file__), "golden", "g6_episodes")
-
-
 @pytest.mark.parametrize("mtype,da_hp", [(0, False), (1, True)])
 def test_replay_fixed_episodes_equals_evaluate(mtype, da_hp):
     """evaluate_fixed_episodes under uniform random actions (sample_actions over a uniform ps),
@@ -502,7 +372,7 @@ def test_replay_fixed_episodes_equals_evaluate(mtype, da_hp):
     sums of float32 terms within 1e-9 relative (summation order only)."""
     from mapf_amd.env import sample_actions
     from mapf_amd.episodes import METRIC_KEYS, evaluate_fixed_episodes, load_fixed_episode_infos, replay_fixed_episodes
-    infos = load_fixed_episode_infos(G6)
+    infos = load_fixed_episode_infos(H.G6)
     steps = 48
 
     def policy(obs, vec, env, t):
@@ -530,16 +400,4 @@ def test_replay_fixed_episodes_equals_evaluate(mtype, da_hp):
 # ------------------------------------------------------------------ 8. coverage guard (last)
 @pytest.mark.parametrize("cfg", ["c1", "c2", "c4", "c5"])
 def test_default_tape_kernels_are_covered_by_this_file(cfg):
-    from test_gpu_ycoverage import preset_env
-    if not TAPE_COVERED:
-        pytest.fail("no oracle- or fixture-compared tape case ran before the guard")
-    env = preset_env(cfg)
-    try:
-        assert env.rollout_fused, cfg
-        for slots in (False, True):
-            name = env.rollout_actions_kernel_name(slots)
-            assert name in TAPE_COVERED and name in COVERED, (
-                f"{cfg} slots={slots}: {env.rollout_actions_plan(slots)} is launched by default but no compared "
-                f"case of this file ran it; covered: {sorted(TAPE_COVERED)}")
-    finally:
-        env.close()
+    H.coverage_guard("tape", TAPE_COVERED, cfg)
