@@ -18,6 +18,7 @@
  *   renderWorld / MapfGym._render   util.py:189-232, mapf_gym.py:639 -> mapf_render
  *   Runner.run GAE                  runner.py:117-149               -> mapf_gae
  *   Model.train normalisation       model.py:106-113                -> mapf_normalize_advantages
+ *   Model.imitation_train           model.py:205-231                -> mapf_imitation_loss
  *   Model.step sampling             model.py:38-40                  -> mapf_sample_actions
  *   minibatch shuffle + indexing    driver.py:123-134               -> mapf_minibatch_rows, mapf_gather_rows
  *
@@ -833,6 +834,25 @@ int mapf_ppo_loss_dcoef(const float *new_ps, const float *old_ps, const int64_t 
                         const float *policy_sig, int32_t sig_fp16, const float *train_valid, int64_t R, int32_t A,
                         const float *coef_dev, float *loss, float *terms, float *grad_ps, float *grad_v,
                         float *grad_cv, float *grad_sig, void *stream);
+
+/* ---- Imitation loss (model.py:205-231: behaviour cloning) ------------------------------------
+ * The cross-entropy of the policy logits against an expert's actions over R = rows x agents
+ * elements with A actions each, plus its gradient, in one launch (csrc/mapf_imitation.hip).
+ * Device pointers: logits [R][A] contiguous, fp32 (logits_f16 = 0) or fp16 bit patterns (1: the
+ * autocast policy layer's output); action [R], int32 (action_i64 = 0: the rollout buffers) or
+ * int64 (1: the reference's contract).
+ *   loss[1]   = mean_r(logsumexp(l_r) - l_r[a_r]), rows in fp32 with their maximum subtracted:
+ *               F.cross_entropy(logits.swapaxes(1, 2), optimal_action) of model.py:221-222.  With
+ *               fp16 logits every log-probability is rounded to fp16 once (-inf past -65504), where
+ *               torch's autocast cross_entropy rounds it, for the loss and for the gradient's softmax
+ *   terms[2]  = {mean [argmax(l_r) == a_r] (the smallest index among the maxima),
+ *                mean softmax(l_r)[a_r]}
+ *   grad_logits[R][A] fp32 = (softmax(l_r)[k] - [k == a_r]) / R
+ * An action outside 0..A-1 makes loss[0] NaN (no device assert).  Deterministic (fixed-order
+ * reduction), no allocation, no host synchronisation: capturable.  MAPF_EINVAL before any launch
+ * for a null pointer, R < 1, or A outside 2..16. */
+int mapf_imitation_loss(const void *logits, int32_t logits_f16, const void *action, int32_t action_i64, int64_t R,
+                        int32_t A, float *loss, float *terms, float *grad_logits, void *stream);
 
 #ifdef __cplusplus
 }

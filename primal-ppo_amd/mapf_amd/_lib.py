@@ -154,6 +154,7 @@ SIGNATURES = {
                                      P]),
     "mapf_ppo_loss_dcoef": (ctypes.c_int, [P, P, P, P, P, P, P, P, P, P, P, P, I32, P, I64, I32, P, P, P, P, P, P, P,
                                            P]),
+    "mapf_imitation_loss": (ctypes.c_int, [P, I32, P, I32, I64, I32, P, P, P, P]),
     "mapf_normalize_advantages_dlam": (ctypes.c_int, [P, P, P, P, P, P, I32, P, I32, P]),
     "mapf_linear512_gelu_dropout": (ctypes.c_int, [P, P, P, P, I64, ctypes.c_float, ctypes.c_uint64, P]),
     "mapf_linear512_select": (ctypes.c_int, [I32]),

@@ -11,7 +11,10 @@ Mirrors the reference's Model (model.py:13-231) and Lagrangian multipliers
     unscale the RCCL all-reduce of the flattened gradient bucket (SURVEY.md §3.4:
     the only exchange step of the path).  Every rank then holds the same gradient, so
     found-inf, clipping, Adam and the loss scale agree across ranks; the returned stats are
-    averaged over the ranks (the global minibatch's means when the shards are equal).
+    averaged over the ranks (the global minibatch's means when the shards are equal);
+  * imitation_train() / imitate_rows(): the behaviour-cloning update (model.py:205-231) -- the
+    cross-entropy of the policy logits against an expert's actions and its gradient in one HIP
+    launch (mapf_imitation_loss), then train()'s own AMP / clip / Adam tail (_DeviceImitation).
 """
 import ctypes
 
@@ -57,6 +60,42 @@ class _FusedPPOLoss(torch.autograd.Function):
     def backward(ctx, g_loss, g_terms):
         out = [(g * g_loss).reshape(shape).to(dtype) for g, (shape, dtype) in zip(ctx.saved_tensors, ctx.meta)]
         return (*out,) + (None,) * 10
+
+
+class _FusedImitationLoss(torch.autograd.Function):
+    """model.py:221-222's cross-entropy and its gradient in one HIP launch (csrc/mapf_imitation.hip,
+    mapf_imitation_loss).  logits [..., A] fp32 or fp16 (the autocast policy layer's output, read as
+    it is), action [...] int32 or int64 (read as it is).  Returns (imitation_loss, terms[2] =
+    agreement with the expert, the expert action's mean probability); only the loss carries a
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, action):
+        A = logits.shape[-1]
+        R = logits.numel() // A
+        lg = logits.detach()
+        if lg.dtype not in (torch.float32, torch.float16):
+            lg = lg.float()
+        lg = lg.reshape(R, A).contiguous()
+        act = action.detach()
+        if act.dtype not in (torch.int32, torch.int64):
+            act = act.long()
+        act = act.reshape(R).contiguous()
+        loss = torch.empty((), device=logits.device)
+        terms = torch.empty(2, device=logits.device)
+        grad = torch.empty(R, A, device=logits.device)
+        _lib.call("mapf_imitation_loss", lg, int(lg.dtype == torch.float16), act, int(act.dtype == torch.int64), R, A,
+                  loss, terms, grad)
+        ctx.save_for_backward(grad)
+        ctx.meta = (logits.shape, logits.dtype)
+        ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, g_loss, g_terms):
+        grad, = ctx.saved_tensors
+        shape, dtype = ctx.meta
+        return (grad * g_loss).reshape(shape).to(dtype), None
 
 
 class Lagrangian:
@@ -374,6 +413,113 @@ class Model:
         upd.load_rows(buffers, T, B, rows, coef=self._loss_coef(lam), lam=lam, packed=(C_, F_) if packed else None)
         return self._run_device_update(upd, episode_cost, distributed)
 
+    # ------------------------------------------------------------ imitation
+    @torch.no_grad()
+    def generate_state(self, obs, vector, input_state=None):
+        """model.py:71-76: the network's fifth output (the per-agent features handed on as the next
+        hidden state in imitation learning).  Inputs may be numpy arrays or device tensors."""
+        t = lambda x: (torch.from_numpy(x) if isinstance(x, np.ndarray) else x).to(self.device)   # noqa: E731
+        _, _, _, _, output_state, _, _ = self.network(t(obs), t(vector), input_state)
+        return output_state
+
+    @staticmethod
+    def _distributed():
+        return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+
+    def imitation_train(self, observation, vector, optimal_action, input_state=None):
+        """model.py:205-231: one behaviour-cloning update -- the cross-entropy of the policy logits
+        against the expert's optimal_action [rows, agents], under the same AMP, clip and Adam tail as
+        train().  Inputs may be numpy arrays (reference contract) or device tensors; the observation may
+        be the packed int32 form; the actions int32 or int64.  input_state is ignored, as the network
+        ignores it.  Returns [imitation_loss, grad_norm].
+        CPU: plain torch.  GPU with fused_loss off: F.cross_entropy under autocast, then net_scaler's
+        scale / unscale / clip / step / update.  GPU default: _DeviceImitation (the fused loss
+        mapf_imitation_loss; captured and replayed after two eager updates of a minibatch shape).
+        World size > 1: the gradients are all-reduced between backward and unscale and the returned
+        stats averaged over the ranks; the device update then runs eagerly (segmented captured graphs
+        exist for the PPO update only)."""
+        dev = self.device
+        t = lambda x: (torch.from_numpy(x) if isinstance(x, np.ndarray) else x).to(dev)   # noqa: E731
+        observation, vector, optimal_action = t(observation), t(vector).float(), t(optimal_action)
+        if observation.dtype == torch.int32:       # packed (one bit per cell): the update reads floats
+            from .env import unpack_obs
+            observation = unpack_obs(observation.contiguous(), self.network.num_channel, self.network.fov)
+        if dev.type == "cuda" and self.fused_loss:
+            upd = self._device_imitation(observation.shape, vector.shape, optimal_action.shape)
+            upd.load(observation, vector, optimal_action)
+            return self._run_device_imitation(upd)[:2]
+        optimal_action = optimal_action.long()
+        self.net_optimizer.zero_grad()
+        with torch.autocast(device_type=dev.type, enabled=dev.type == "cuda"):
+            _, _, _, _, _, logits, _ = self.network(observation, vector, input_state)
+            imitation_loss = F.cross_entropy(torch.swapaxes(logits, 1, 2), optimal_action)
+        self.net_scaler.scale(imitation_loss).backward()
+        self._allreduce_grads()
+        self.net_scaler.unscale_(self.net_optimizer)
+        grad_norm = torch.nn.utils.clip_grad_norm_(self.network.parameters(), TrainingParameters.MAX_GRAD_NORM)
+        self.net_scaler.step(self.net_optimizer)
+        self.net_scaler.update()
+        stats = torch.stack([imitation_loss.detach().float().reshape(()), grad_norm.detach().float().reshape(())])
+        if self._distributed():
+            dist.all_reduce(stats)
+            stats /= dist.get_world_size()
+        return [np.asarray(v) for v in stats.cpu().numpy()]
+
+    def _device_imitation(self, obs_shape, vec_shape, action_shape):
+        """The _DeviceImitation of this minibatch shape, keyed ("imitation", shapes) beside the PPO
+        updates in _updates; it shares their optimizer and their one GradScaler."""
+        key = ("imitation", tuple(obs_shape), tuple(vec_shape), tuple(action_shape))
+        sc = self.net_scaler
+        if sc._scale is None:
+            sc._lazy_init_scale_growth_tracker(self.device)
+        upd = self._updates.get(key)
+        if upd is not None and not upd.uses(sc):
+            upd = None                        # net_scaler replaced or reconfigured: re-capture
+        if upd is None:
+            upd = self._updates[key] = _DeviceImitation(self, obs_shape, vec_shape, action_shape)
+        return upd
+
+    def _run_device_imitation(self, upd):
+        """One update from upd's loaded static inputs; the 4 stats (loss, grad norm, agreement with the
+        expert, the expert action's mean probability)."""
+        distributed = self._distributed()
+        upd.run(graph=self.graph_update and not distributed, allreduce=distributed)
+        self.network.weights_updated()        # replays bump no tensor version: drop the fp16 acting copies
+        return [np.asarray(v) for v in upd.stats.cpu().numpy()]       # one device -> host copy
+
+    def imitate_rows(self, source, rows, checked=False):
+        """One imitation update on the env-major rows `rows` of source's last rollout, the twin of
+        train_rows: one gather launch (env.gather_rows) moves the rows' observations (packed rows are
+        unpacked by one more launch, as _DeviceUpdate.load_rows does), vectors and expert actions into
+        _DeviceImitation's static inputs.  source: anything with T, env, packed, obs / obs_bits (T + 1
+        slots, slot t = the state the expert saw at step t), vec and expert_actions (int32 [T, B, N]) --
+        imitation.DemoRunner, or a DeviceRunner built with expert=.  rows as in train_rows.  Returns
+        the 4 stats (loss, grad norm, agreement, expert probability).  A model that is not on the GPU,
+        or has fused_loss off, trains through imitation_train() on torch-indexed rows (2 stats)."""
+        from .runner import _row_index
+        T, B = source.T, source.env.B
+        dev = self.device
+        if getattr(source, "expert_actions", None) is None:
+            raise RuntimeError("imitate_rows: the source holds no expert actions")
+        if not (checked and isinstance(rows, torch.Tensor) and rows.dtype == torch.int64 and rows.dim() == 1):
+            rows, _ = _row_index(rows, T * B, dev)
+        if isinstance(rows, np.ndarray):
+            rows = torch.from_numpy(rows)
+        packed = bool(getattr(source, "packed", False))
+        obs = source.obs_bits[:T] if packed else source.obs[:T]
+        vec, act = source.vec[:T], source.expert_actions
+        if dev.type != "cuda" or not self.fused_loss:
+            r = rows.to(obs.device)
+            ts, bs = r % T, r // T
+            return self.imitation_train(obs[ts, bs], vec[ts, bs], act[ts, bs], None)
+        rows = rows.to(dev, non_blocking=True).contiguous()
+        M = rows.numel()
+        C_, F_ = source.env.C, source.env.F
+        obs_shape = (M, obs.shape[2], C_, F_, F_) if packed else (M,) + tuple(obs.shape[2:])
+        upd = self._device_imitation(obs_shape, (M,) + tuple(vec.shape[2:]), (M,) + tuple(act.shape[2:]))
+        upd.load_rows((obs, vec, act), T, B, rows, packed=(C_, F_) if packed else None)
+        return self._run_device_imitation(upd)
+
     def _finish_update(self, all_loss, policy_loss, entropy, critic_loss, valid_loss, cost_critic_loss, cost_loss,
                        clip_frac, advantage, cost_advantage, episode_cost, distributed):
         """model.py:177-199: backward, gradient exchange, Lagrangian step, clip, Adam, stats."""
@@ -442,13 +588,20 @@ class _DeviceUpdate:
         self.action = e(action, torch.int64)
         self.old_ps, self.tv = e(old_ps), e(train_valid)
         self.dyn = torch.zeros(8, dtype=torch.float32, device=dev)     # coef[6], lam, f32(lam + 1)
+        self.nstats = torch.zeros(4, dtype=torch.float64, device=dev)    # global advantage statistics (distributed)
+        self._init_tail(11)
+
+    def _init_tail(self, n_stats):
+        """the state of the shared tail (_tail) and of run(): the AMP tensors, found-inf, the stats, the
+        gradient bucket and the captured graph"""
+        model = self.model
+        dev = model.device
         sc = model.net_scaler                  # its live state and settings (GradScaler: 2^16, x2 / 2000, x0.5)
         self.scaler = sc
         self.scale, self.growth = sc._scale, sc._growth_tracker        # 0-dim device tensors, updated in place
         self.amp = self._amp_settings(sc)
         self.found_inf = torch.zeros((), dtype=torch.float32, device=dev)
-        self.stats = torch.zeros(11, dtype=torch.float32, device=dev)
-        self.nstats = torch.zeros(4, dtype=torch.float64, device=dev)    # global advantage statistics (distributed)
+        self.stats = torch.zeros(n_stats, dtype=torch.float32, device=dev)
         self.grad_params, self.flat = None, None                          # the gradient bucket (distributed)
         self.live = None
         self.graph = None                    # one CUDAGraph, or (segment A, segment B) when distributed
@@ -519,20 +672,25 @@ class _DeviceUpdate:
         (all_loss * self.scale).backward()
         self.live = (all_loss, terms, adv, cadv)       # read by _back (kept alive: graph A writes them)
         if allreduce:    # the flattened gradient bucket (model.py:177-185: all-reduced between backward and unscale)
-            gp = [p for p in net.parameters() if p.grad is not None]
-            if self.grad_params is None:
-                self.grad_params = gp
-                self.flat = torch.empty(sum(p.numel() for p in gp), dtype=torch.float32, device=self.model.device)
-            assert len(gp) == len(self.grad_params) and all(a is b for a, b in zip(gp, self.grad_params))
-            # each gradient's elements in memory order (AccumulateGrad lays a dense parameter's gradient out
-            # like the parameter: contiguous or channels_last), so _back's views of the bucket take the
-            # parameter's own strides -- fused Adam wants parameter and gradient alike
-            assert all(p.grad.stride() == p.stride() for p in gp)
-            torch.cat([p.grad.as_strided((p.numel(),), (1,)) for p in gp], out=self.flat)
+            self._fill_bucket()
 
-    def _back(self, allreduce):
+    def _fill_bucket(self):
+        """the gradients of the backward just run, flattened into the static bucket the ranks all-reduce"""
+        gp = [p for p in self.model.network.parameters() if p.grad is not None]
+        if self.grad_params is None:
+            self.grad_params = gp
+            self.flat = torch.empty(sum(p.numel() for p in gp), dtype=torch.float32, device=self.model.device)
+        assert len(gp) == len(self.grad_params) and all(a is b for a, b in zip(gp, self.grad_params))
+        # each gradient's elements in memory order (AccumulateGrad lays a dense parameter's gradient out
+        # like the parameter: contiguous or channels_last), so _tail's views of the bucket take the
+        # parameter's own strides -- fused Adam wants parameter and gradient alike
+        assert all(p.grad.stride() == p.stride() for p in gp)
+        torch.cat([p.grad.as_strided((p.numel(),), (1,)) for p in gp], out=self.flat)
+
+    def _tail(self, allreduce):
         """[bucket averaged over the ranks] -> unscale + found-inf -> clip -> fused Adam -> loss-scale
-        update -> stats (graph segment B when distributed)"""
+        update: the tail the PPO update and the imitation update (_DeviceImitation) share.  Returns the
+        gradient norm before clipping."""
         net, opt = self.model.network, self.model.net_optimizer
         T = TrainingParameters
         if allreduce:    # the parameters' gradients become views of the all-reduced bucket (no copy back)
@@ -550,6 +708,11 @@ class _DeviceUpdate:
         opt.step()
         opt.grad_scale = opt.found_inf = None
         torch._amp_update_scale_(self.scale, self.growth, self.found_inf, *self.amp)
+        return grad_norm
+
+    def _back(self, allreduce):
+        """_tail -> stats (graph segment B when distributed)"""
+        grad_norm = self._tail(allreduce)
         all_loss, terms, adv, cadv = self.live
         self.stats.copy_(torch.stack([t.detach().float().reshape(()) for t in (
             all_loss, terms[0], terms[1], terms[2], terms[3], terms[4], terms[5], terms[6], grad_norm,
@@ -631,3 +794,58 @@ class _DeviceUpdate:
             self._exchange_stats()
         else:
             self.graph.replay()
+
+
+class _DeviceImitation(_DeviceUpdate):
+    """The static buffers and the body of one minibatch shape's device imitation update
+    (Model.imitation_train / imitate_rows): zero-grad -> autocast forward -> fused cross-entropy
+    (mapf_imitation_loss) -> (loss * scale).backward(), then _DeviceUpdate's own tail (unscale with
+    found-inf, clip, fused Adam, loss-scale update) on the model's one optimizer and one GradScaler.
+    Warm-ups, capture and replay are _DeviceUpdate.run's.  stats[4] = loss, grad norm, agreement with
+    the expert, the expert action's mean probability."""
+
+    def __init__(self, model, obs_shape, vec_shape, action_shape):
+        dev = model.device
+        self.model = model
+        self.obs = torch.zeros(tuple(obs_shape), dtype=torch.float32, device=dev)
+        self.vec = torch.zeros(tuple(vec_shape), dtype=torch.float32, device=dev)
+        self.action = torch.zeros(tuple(action_shape), dtype=torch.int32, device=dev)    # the rollouts' format
+        self._init_tail(4)
+
+    def load(self, observation, vector, action):
+        self.obs.copy_(observation.reshape(self.obs.shape), non_blocking=True)
+        self.vec.copy_(vector.reshape(self.vec.shape), non_blocking=True)
+        self.action.copy_(action.reshape(self.action.shape), non_blocking=True)      # int64 -> int32 in the copy
+
+    def load_rows(self, buffers, T, B, rows, packed=None):
+        """load() straight from t-major [T, B, ...] device buffers (observations or packed observations,
+        vec, expert actions int32) in one gather launch; packed = (C, F): as _DeviceUpdate.load_rows."""
+        from .env import gather_rows, unpack_obs
+        obs_dst = self.obs
+        if packed is not None:
+            shape = (rows.numel(),) + tuple(buffers[0].shape[2:])
+            if getattr(self, "obs_stage", None) is None or tuple(self.obs_stage.shape) != shape:
+                self.obs_stage = torch.zeros(shape, dtype=torch.int32, device=self.obs.device)
+            obs_dst = self.obs_stage
+        gather_rows(buffers, T, B, rows, (obs_dst, self.vec, self.action))
+        if packed is not None:
+            unpack_obs(self.obs_stage, packed[0], packed[1], out=self.obs)
+
+    def _front(self, allreduce):
+        net, opt = self.model.network, self.model.net_optimizer
+        opt.zero_grad(set_to_none=True)
+        with torch.autocast(device_type="cuda", cache_enabled=False):
+            _, _, _, _, _, logits, _ = net(self.obs, self.vec, None)
+        loss, terms = _FusedImitationLoss.apply(logits, self.action)
+        (loss * self.scale).backward()
+        self.live = (loss, terms)          # read by _back (kept alive: the graph writes them)
+        if allreduce:
+            self._fill_bucket()
+
+    def _back(self, allreduce):
+        grad_norm = self._tail(allreduce)
+        loss, terms = self.live
+        self.stats.copy_(torch.stack([t.detach().float().reshape(()) for t in (loss, grad_norm, terms[0], terms[1])]))
+
+    def _moments(self):
+        """nothing to normalise: the imitation loss has no advantage statistics"""

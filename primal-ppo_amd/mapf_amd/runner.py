@@ -312,9 +312,19 @@ class DeviceRunner:
     [T + 1, B, N, WPA] instead of the float `obs` [T + 1, B, N, C, F, F] (32 times smaller); the env
     writes them (observe_bits / step_observe_bits), the policy reads them (Model.step / value accept
     packed input), batch().observations unpacks the rows it is indexed with, and Model.train_rows
-    gathers packed rows and unpacks them into the update's static input."""
+    gathers packed rows and unpacks them into the update's static input.
+    expert: "pibt" or "descent" -- label the learner's own states (DAgger-style): before the policy acts
+    at step t, env.pibt_actions / env.descent_actions writes the expert's choice for that state into
+    expert_actions[t] (int32 [T, B, N]; one small launch per step), which Model.imitate_rows and
+    DeviceTrainer.imitate read next to obs[:T] / vec[:T].  Needs an env built with keep_bfs.  None
+    (the default): no labels, no launch, no buffer."""
 
-    def __init__(self, env: BatchedMapfGym, model, n_steps=None, seed=0, new_maps=None, obs_bits=False):
+    def __init__(self, env: BatchedMapfGym, model, n_steps=None, seed=0, new_maps=None, obs_bits=False, expert=None):
+        if expert not in (None, "pibt", "descent"):
+            raise ValueError(f"expert: expected None, 'pibt' or 'descent', got {expert!r}")
+        if expert is not None and not env.cfg.keep_bfs:
+            raise ValueError(f"expert={expert!r} reads the agents' BFS maps: build the env with keep_bfs=True")
+        self.expert = expert
         self.env = env
         self.model = model
         self.T = TrainingParameters.N_STEPS if n_steps is None else n_steps
@@ -344,6 +354,7 @@ class DeviceRunner:
         self.constraints = z(T, B, N)
         self.shadow = z(T, B, dt=torch.int32)
         self.adv = self.returns = self.cost_adv = self.cost_returns = None
+        self.expert_actions = z(T, B, N, dt=torch.int32) if expert is not None else None
 
     @torch.no_grad()
     def run(self, weights=None):
@@ -359,7 +370,10 @@ class DeviceRunner:
         ob = self.obs_bits if self.packed else self.obs
         (env.observe_bits if self.packed else env.observe)(ob[0], self.vec[0])
         step_observe = env.step_observe_bits if self.packed else env.step_observe
+        label = {None: None, "pibt": env.pibt_actions, "descent": env.descent_actions}[self.expert]
         for t in range(T):
+            if label is not None:      # the expert's choice in the state the learner is about to act in
+                label(out=self.expert_actions[t])
             a, ps, v, _, _, cv = self.model.step(ob[t], self.vec[t], None, seed=self.seed,
                                                  step=self.rollouts * T + t, actions_out=self.actions[t],
                                                  actions32_out=self.actions32)

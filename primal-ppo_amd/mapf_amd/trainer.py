@@ -14,9 +14,14 @@ K = (B * T) // minibatch minibatches and leaves the (B * T) % minibatch last row
 permutation out; the epoch counter moves on across update() calls, so no two epochs share a
 permutation and other rows are left out each time.
 
+imitate(source) walks the same kind of epochs over a source of demonstrations (imitation.DemoRunner,
+or a DeviceRunner built with expert=) through Model.imitate_rows, and fit(n, demo=, demonstration_prob=)
+draws per rollout which of the two it is (TrainingParameters.DEMONSTRATION_PROB).
+
 Several ranks: every rank must hold the same B and T (Model's distributed update needs equal
 minibatch counts on every rank); each rank shuffles its own rollout.
 """
+import numpy as np
 import torch
 
 from .config import TrainingParameters
@@ -56,13 +61,56 @@ class DeviceTrainer:
             self.epoch_counter += 1
         return mb_loss
 
-    def fit(self, n_rollouts):
+    def imitate(self, source, n_epochs=1):
+        """n_epochs epochs of behaviour cloning over source's last rollout (imitation.DemoRunner, or a
+        DeviceRunner built with expert=): per epoch (source.T * B) // minibatch updates, minibatch k on rows
+        [k * M, (k + 1) * M) of that epoch's permutation, through Model.imitate_rows.  The epoch counter is
+        update()'s, so PPO and imitation epochs never share a permutation.  Returns the per-minibatch stats
+        (loss, grad norm, agreement with the expert, the expert action's mean probability)."""
+        M = self.minibatch
+        n = source.T * source.env.B
+        if not 1 <= M <= n:
+            raise ValueError(f"minibatch {M} for a rollout of {n} rows")
+        on_gpu = self.model.device.type == "cuda"
+        if self.rows is None:
+            self.rows = torch.empty(M, dtype=torch.int64, device=source.env.device if on_gpu else "cpu")
+        mb_loss = []
+        for _ in range(int(n_epochs)):
+            for k in range(n // M):
+                minibatch_rows(n, self.seed, self.epoch_counter, k * M, M, out=self.rows)
+                mb_loss.append(self.model.imitate_rows(source, self.rows, checked=True))
+            self.epoch_counter += 1
+        return mb_loss
+
+    def fit(self, n_rollouts, demo=None, demonstration_prob=None):
         """n_rollouts times: runner.run(), then update() on it.  The trained weights are handed to the
         runner only when it acts with another Model object than the one trained.  Returns the list of
-        (performance, mb_loss) per rollout."""
+        (performance, mb_loss) per rollout.
+        demo: a source of demonstrations (imitation.DemoRunner).  Each rollout index is then an imitation
+        rollout -- demo.run(), then imitate(demo) -- with probability demonstration_prob (default
+        TrainingParameters.DEMONSTRATION_PROB = 0: never, driver.py's setting), drawn from a host generator
+        seeded with the trainer's seed; otherwise the PPO rollout.  With demo given, the entries are
+        (kind, performance, mb_loss), kind "ppo" or "imitation" (an imitation entry's performance is
+        demo.run()'s per-env counters)."""
+        if demo is None:
+            if demonstration_prob:
+                raise ValueError("demonstration_prob needs a source of demonstrations: demo=...")
+            prob, draw = 0.0, None
+        else:
+            prob = float(TrainingParameters.DEMONSTRATION_PROB if demonstration_prob is None else demonstration_prob)
+            if not 0.0 <= prob <= 1.0:
+                raise ValueError(f"demonstration_prob {prob} outside [0, 1]")
+            if getattr(self, "_demo_rng", None) is None:
+                self._demo_rng = np.random.default_rng([self.seed & 0xFFFFFFFF, 0x1A17A7E])
+            draw = self._demo_rng
         out = []
         for _ in range(int(n_rollouts)):
+            if prob > 0.0 and draw.random() < prob:
+                performance = demo.run()
+                out.append(("imitation", performance, self.imitate(demo)))
+                continue
             weights = None if self.runner.model is self.model else self.model.network.state_dict()
             _, performance = self.runner.run(weights)
-            out.append((performance, self.update(performance)))
+            mb_loss = self.update(performance)
+            out.append((performance, mb_loss) if demo is None else ("ppo", performance, mb_loss))
         return out

@@ -1,0 +1,125 @@
+"""Behaviour cloning at the c3 shape (4096 envs x 8 agents, 20 x 20 warehouse, FOV 9, packed observations):
+
+  python tools/bench_imitation.py                       # all three parts
+  python tools/bench_imitation.py --envs 256 --updates 40   # a quick look
+
+  1. DemoRunner.run() per rollout (T = 32 PIBT steps in one launch, plus the slot-0 observe), HIP events
+     around the call, median of --reps after one untimed call.
+  2. One update at 256 x 8 and 256 x 16 rows, imitation beside PPO of the same build, eager and captured:
+     HIP events around _DeviceImitation.run / _DeviceUpdate.run on loaded static inputs (the loads are
+     not timed), median of 20 after the two warm-ups and the capture.  The four series are alternated.
+  3. The loss and agreement-with-PIBT curves over --updates captured updates (256 x 8 rows each) on PIBT
+     demonstrations: a new rollout (the envs run on) every (T * B) // 256 updates, dropout on, the default
+     learning rate.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "primal-ppo_amd")]
+
+
+def timed(fn, reps):
+    import torch
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--T", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--updates", type=int, default=300)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    import mapf_amd  # noqa: F401
+    import torch
+    from mapf_amd.config import make_config
+    from mapf_amd.env import BatchedMapfGym
+    from mapf_amd.imitation import DemoRunner
+    from mapf_amd.maps import generate_warehouse
+    from mapf_amd.model import Model
+    from mapf_amd.trainer import DeviceTrainer
+    torch.cuda.set_device(0)
+    B, N, S, F, C, T = args.envs, 8, 20, 9, 6, args.T
+
+    # ---- 1. demonstrations
+    env = BatchedMapfGym(make_config(B, S, S, num_agents=N, fov=F, num_channel=C, human_mode="random",
+                                     goal_mode="random", fix_choice=1, keep_bfs=True, seed=1234))
+    env.reset_seeded(generate_warehouse(S, S))
+    demo = DemoRunner(env, n_steps=T, policy="pibt", obs_bits=True, seed=args.seed)
+    demo.run()
+    ms = timed(demo.run, args.reps)
+    perf = demo.performance_per_env()
+    print(json.dumps({"part": "demo", "envs": B, "agents": N, "T": T, "plan": env.rollout_plan(True, False, True, policy="pibt"),
+                      "ms_per_rollout": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3),
+                      "us_per_step": round(statistics.median(ms) * 1e3 / T, 2),
+                      "agent_steps_per_s": round(B * N * T / (statistics.median(ms) * 1e-3)),
+                      "goals_per_env_step": round(float(perf["totalGoals"].mean()) / T, 4),
+                      "agent_collisions": float(perf["agentCollide"].sum())}), flush=True)
+
+    # ---- 2. update times
+    torch.manual_seed(args.seed)
+    g = torch.Generator(device="cuda").manual_seed(1)
+    for n in (8, 16):
+        rows = 256
+        series = {}
+        for graph in (False, True):
+            model = Model(0, "cuda", global_model=True, numChannel=C, num_agents=n, fov=F)
+            model.graph_update = graph
+            obs = (torch.rand(rows, n, C, F, F, device="cuda", generator=g) < 0.3).float()
+            vec = torch.randn(rows, n, 4, device="cuda", generator=g)
+            act = torch.randint(0, 5, (rows, n), device="cuda", generator=g)
+            ret, v, cret, cv = (torch.randn(rows, n, device="cuda", generator=g) for _ in range(4))
+            ps = torch.softmax(torch.randn(rows, n, 5, device="cuda", generator=g), -1)
+            tv = (torch.rand(rows, n, 5, device="cuda", generator=g) < 0.7).float()
+            for _ in range(4):                       # two warm-ups, the capture, one replay
+                model.imitation_train(obs, vec, act, None)
+                model.train(obs, vec, ret, cret, v, cv, act, ps, None, tv, 1.0)
+            il = model._updates[next(k for k in model._updates if k[0] == "imitation")]
+            ppo = model._updates[next(k for k in model._updates if k[0] != "imitation")]
+            assert (il.graph is not None) == graph and (ppo.graph is not None) == graph
+            t_il, t_ppo = [], []
+            for _ in range(args.reps):               # alternated
+                t_il += timed(lambda: il.run(graph=graph), 1)
+                t_ppo += timed(lambda: ppo.run(graph=graph), 1)
+            mode = "captured" if graph else "eager"
+            series[f"imitation {mode}"], series[f"ppo {mode}"] = t_il, t_ppo
+            del model, il, ppo
+        print(json.dumps({"part": "update", "rows": rows, "agents": n,
+                          "ms": {k: {"median": round(statistics.median(x), 3), "min": round(min(x), 3),
+                                     "max": round(max(x), 3)} for k, x in series.items()}}), flush=True)
+
+    # ---- 3. learning curve on PIBT demonstrations (the envs run on from rollout to rollout: new states every time)
+    env.reset_seeded(generate_warehouse(S, S), seed=7)
+    model = Model(0, "cuda", global_model=True, numChannel=C, num_agents=N, fov=F)
+    tr = DeviceTrainer(demo, model, minibatch=256, n_epochs=1, seed=args.seed)
+    curve, k = [], 0
+    while k < args.updates:
+        demo.run()
+        for s in tr.imitate(demo)[:args.updates - k]:
+            curve.append([float(x) for x in s])
+            k += 1
+    step = max(1, len(curve) // 30)
+    for i in range(0, len(curve), step):
+        w = curve[i:i + step]
+        print(json.dumps({"part": "curve", "updates": f"{i}..{i + len(w) - 1}",
+                          "loss": round(statistics.mean(x[0] for x in w), 4),
+                          "agreement": round(statistics.mean(x[2] for x in w), 4),
+                          "expert_prob": round(statistics.mean(x[3] for x in w), 4)}), flush=True)
+    assert not env.counters()[:8].any()
+
+
+if __name__ == "__main__":
+    main()
