@@ -248,6 +248,16 @@ int mapf_obs_band_skip(const mapf_config *cfg, int32_t unit, uint64_t byte_offse
  * 0 if step t needs no wait at all (t <= slack), or a negative error.  slack >= 0; more than 14 is
  * paced as 14. */
 int mapf_pace_gate(int32_t t, int32_t slack, int32_t live, int32_t *word, uint32_t *target);
+/* LDS bytes the mapf_observe launch requests with `obs_envs` envs per workgroup (0: the default
+ * rule, 64 / N for N <= 8 else 1, at most num_envs), computed on the host (no device call) by the
+ * functions the launch and mapf_create / mapf_set_tuning run.  The request is the observing workgroup's
+ * own LDS or, where the launch may host the step's searches (W <= 32, H <= 64) and that is more, the
+ * four search waves'.  If max_lds > 0 and envs_out != NULL, *envs_out = the envs per workgroup the
+ * library uses under that limit: the largest count up to the requested one whose request fits (0, and
+ * MAPF_EINVAL, if not even one env fits: mapf_create refuses such a configuration on such a device).
+ * With max_lds = 0 nothing is fitted and *envs_out is the requested count.
+ * Returns the bytes of THAT choice when max_lds > 0, of the requested one otherwise; negative on error. */
+int64_t mapf_observe_lds(const mapf_config *cfg, int32_t obs_envs, int32_t max_lds, int32_t *envs_out);
 
 /* Launch tuning of one handle: which form of a kernel the launches take (the measured choices
  * of DESIGN.md §4 / §9).  The reference has no counterpart (its env is Python); these fields
@@ -276,7 +286,9 @@ typedef struct mapf_tuning {
     int32_t wide_bfsobs;     /* three-wave form: the observers search the rebuilt BFS maps (0: the stepper)  */
     int32_t xcd_remap;       /* persistent kernels: XCD-aware env order (0 off)                            */
     /* per-step launches */
-    int32_t obs_envs;        /* envs per observe workgroup: 0 auto (64 / N for N <= 8, else 1), 1..64      */
+    int32_t obs_envs;        /* envs per observe workgroup: 0 auto (64 / N for N <= 8, else 1, reduced until
+                                the launch's LDS fits the device: mapf_observe_lds), 1..64 (at most B; a value
+                                whose LDS does not fit is refused, the message names the largest that does)  */
     int32_t step_block;      /* threads per step workgroup: 64, 128 or 256                                 */
     int32_t search_blocks;   /* workgroups of an observe launch that run search work: 1..1024              */
     int32_t band_blocks;     /* zero-band workgroups of the fused step+observe launch: 0..4096             */

@@ -70,6 +70,7 @@ struct mapf_env {
     long def_due[2] = {-1, -1};            // join before the step that would make nsteps exceed this
     int def_next = 0;
     mapf_tuning tune;                      // launch forms (mapf_set_tuning); never the process environment
+    int max_lds = 0;                       // device_max_group_lds() of `device`: what the observe launch is fitted to
     ArgRing args;                          // device-resident argument blocks of the persistent kernels
     // the PIBT policy's age arrays [B][N] (mapf.h: mapf_pibt_actions): the packed goal last seen and
     // the clock it was first seen at; policy-owned, no step kernel touches them
@@ -85,12 +86,56 @@ struct mapf_env {
     }
 };
 
-// the per-step launches' tuning fields live in DevEnv (the kernels read them)
-static void apply_tuning(DevEnv &d, const mapf_tuning &t) {
-    // envs per observe_kernel workgroup: 64/N fills a wave's lanes for N <= 8; above that one
-    // env per workgroup measured fastest (c4, 16 agents: 12.4 us vs 14.2 us at 4 envs, tools/sweep_c45.sh)
-    d.obs_envs = t.obs_envs > 0 ? t.obs_envs : (d.N > 8 ? 1 : 64 / d.N);
-    if (d.obs_envs > d.B) d.obs_envs = d.B;
+// what mapf_create checks before any device call
+static int check_config(const mapf_config &c) {
+    if (c.num_envs < 1) return fail(MAPF_EINVAL, "num_envs must be >= 1");
+    if (c.num_agents < 1 || c.num_agents > 64) return fail(MAPF_EINVAL, "num_agents must be in 1..64");
+    if (c.height < 1 || c.height > 128 || c.width < 1 || c.width > 128) return fail(MAPF_EINVAL, "height/width must be in 1..128");
+    if (c.fov < 1 || c.fov > 16) return fail(MAPF_EINVAL, "fov must be in 1..16");
+    if (c.num_channel < 5 || c.num_channel > 7) return fail(MAPF_EINVAL, "num_channel must be 5, 6 or 7");
+    if (c.num_channel == 7 && !c.keep_bfs) return fail(MAPF_EINVAL, "num_channel 7 (BFS channel) needs keep_bfs");
+    if (c.human_mode < 0 || c.human_mode > 2) return fail(MAPF_EINVAL, "human_mode must be 0, 1 or 2");
+    if (c.goal_mode < 0 || c.goal_mode > 1) return fail(MAPF_EINVAL, "goal_mode must be 0 or 1");
+    if (c.fix_choice < 0 || c.fix_choice > 1) return fail(MAPF_EINVAL, "fix_choice must be 0 or 1");
+    if (c.max_seq < 1) return fail(MAPF_EINVAL, "max_seq must be >= 1");
+    if (c.human_mode == 2 && c.max_human_seq < 2) return fail(MAPF_EINVAL, "max_human_seq must be >= 2");
+    if (c.penalty_radius < 1 || c.penalty_radius > 64) return fail(MAPF_EINVAL, "penalty_radius must be in 1..64");
+    if (c.k_predict < 0 || c.k_predict > 64) return fail(MAPF_EINVAL, "k_predict must be in 0..64");
+    return MAPF_OK;
+}
+
+// the sizes and switches of a checked config, as the kernels read them (no pointers, no tuning)
+static void config_geometry(const mapf_config &c, DevEnv &d) {
+    d.B = c.num_envs; d.N = c.num_agents; d.H = c.height; d.W = c.width; d.F = c.fov; d.C = c.num_channel;
+    d.P = c.fov / 2 > 1 ? c.fov / 2 : 1;
+    d.Hp = d.H + 2 * d.P;
+    d.WW = (d.W + 2 * d.P + 31) / 32;
+    d.G = next_pow2(d.N);
+    d.S = c.max_seq;
+    d.HS = c.max_human_seq > 2 ? c.max_human_seq : 2;
+    d.Lmax = 2 * d.H * d.W + 1;
+    d.use_da = c.use_da; d.use_hp = c.use_hp; d.lifelong = c.lifelong; d.human_mode = c.human_mode;
+    d.goal_mode = c.goal_mode; d.fix_choice = c.fix_choice; d.shared_map = c.shared_map ? 1 : 0;
+    d.keep_bfs = c.keep_bfs ? 1 : 0; d.k_predict = c.k_predict; d.R = c.penalty_radius;
+    d.action_cost = c.action_cost; d.collision_cost = c.collision_cost; d.human_collision_cost = c.human_collision_cost;
+    d.repeat_cost = c.repeat_cost; d.goal_reward = c.goal_reward;
+    d.env_offset = (uint32_t)c.env_offset;
+    d.seed = c.seed;
+}
+
+// Envs per observe_kernel workgroup for the tuning value obs_envs.  `want`: that value, or for 0 the
+// default rule (64/N fills a wave's lanes for N <= 8; above that one env per workgroup measured
+// fastest -- c4, 16 agents: 12.4 us vs 14.2 us at 4 envs, tools/sweep_c45.sh), at most B.  Returns the
+// largest count <= want whose launch fits max_lds bytes of LDS (0: not even one env does): the index
+// image alone is H*W bytes per env, so few agents on a large map do not fit at 64/N.
+static int observe_envs(const DevEnv &d, int obs_envs, size_t max_lds, int &want) {
+    want = obs_envs > 0 ? std::min(obs_envs, d.B) : observe_default_envs(d);
+    return observe_fit_envs(d, want, max_lds);
+}
+
+// the per-step launches' tuning fields live in DevEnv (the kernels read them); obs_envs as observe_envs fitted it
+static void apply_tuning(DevEnv &d, const mapf_tuning &t, int obs_envs) {
+    d.obs_envs = obs_envs;
     d.step_block = t.step_block;
     d.search_blocks = t.search_blocks;
     d.band_blocks = t.band_blocks;   // zero-band workgroups: slower than the waves' table-driven stores (0)
@@ -158,8 +203,15 @@ int mapf_set_tuning(mapf_env *e, const mapf_tuning *t) {
     if (!in(t->search_blocks, 1, 1024)) return fail(MAPF_EINVAL, "search_blocks must be in 1..1024");
     if (!in(t->band_blocks, 0, 4096)) return fail(MAPF_EINVAL, "band_blocks must be in 0..4096");
     if (!in(t->diag_exp, 0, 3)) return fail(MAPF_EINVAL, "diag_exp must be in 0..3");
+    int want = 0;
+    const int envs = observe_envs(e->d, t->obs_envs, (size_t)e->max_lds, want);
+    if (t->obs_envs > 0 && envs != want)      // (the default, 0, is reduced instead: mapf_create saw one env fit)
+        return fail(MAPF_EINVAL, "obs_envs " + std::to_string(want) + " needs " +
+                                     std::to_string(observe_launch_lds(e->d, want)) + " bytes of LDS per observe workgroup, "
+                                     "over the device's " + std::to_string(e->max_lds) + ": the largest value that fits is " +
+                                     std::to_string(envs));
     e->tune = *t;
-    apply_tuning(e->d, e->tune);
+    apply_tuning(e->d, e->tune, envs);
     return MAPF_OK;
 }
 
@@ -169,44 +221,25 @@ int mapf_abi_version(void) { return MAPF_ABI_VERSION; }
 int mapf_create(const mapf_config *cfg, int device, mapf_env **out) {
     if (!cfg || !out) return fail(MAPF_EINVAL, "null argument");
     const mapf_config &c = *cfg;
-    if (c.num_envs < 1) return fail(MAPF_EINVAL, "num_envs must be >= 1");
-    if (c.num_agents < 1 || c.num_agents > 64) return fail(MAPF_EINVAL, "num_agents must be in 1..64");
-    if (c.height < 1 || c.height > 128 || c.width < 1 || c.width > 128) return fail(MAPF_EINVAL, "height/width must be in 1..128");
-    if (c.fov < 1 || c.fov > 16) return fail(MAPF_EINVAL, "fov must be in 1..16");
-    if (c.num_channel < 5 || c.num_channel > 7) return fail(MAPF_EINVAL, "num_channel must be 5, 6 or 7");
-    if (c.num_channel == 7 && !c.keep_bfs) return fail(MAPF_EINVAL, "num_channel 7 (BFS channel) needs keep_bfs");
-    if (c.human_mode < 0 || c.human_mode > 2) return fail(MAPF_EINVAL, "human_mode must be 0, 1 or 2");
-    if (c.goal_mode < 0 || c.goal_mode > 1) return fail(MAPF_EINVAL, "goal_mode must be 0 or 1");
-    if (c.fix_choice < 0 || c.fix_choice > 1) return fail(MAPF_EINVAL, "fix_choice must be 0 or 1");
-    if (c.max_seq < 1) return fail(MAPF_EINVAL, "max_seq must be >= 1");
-    if (c.human_mode == 2 && c.max_human_seq < 2) return fail(MAPF_EINVAL, "max_human_seq must be >= 2");
-    if (c.penalty_radius < 1 || c.penalty_radius > 64) return fail(MAPF_EINVAL, "penalty_radius must be in 1..64");
-    if (c.k_predict < 0 || c.k_predict > 64) return fail(MAPF_EINVAL, "k_predict must be in 0..64");
+    if (int rc = check_config(c)) return rc;
     if (hipSetDevice(device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
 
     auto *e = new mapf_env();
     e->cfg = c;
     e->device = device;
     DevEnv &d = e->d;
-    d.B = c.num_envs; d.N = c.num_agents; d.H = c.height; d.W = c.width; d.F = c.fov; d.C = c.num_channel;
-    d.P = c.fov / 2 > 1 ? c.fov / 2 : 1;
-    d.Hp = d.H + 2 * d.P;
-    d.WW = (d.W + 2 * d.P + 31) / 32;
-    d.G = next_pow2(d.N);
-    d.S = c.max_seq;
-    d.HS = c.max_human_seq > 2 ? c.max_human_seq : 2;
-    d.Lmax = 2 * d.H * d.W + 1;
-    d.use_da = c.use_da; d.use_hp = c.use_hp; d.lifelong = c.lifelong; d.human_mode = c.human_mode;
-    d.goal_mode = c.goal_mode; d.fix_choice = c.fix_choice; d.shared_map = c.shared_map ? 1 : 0;
-    d.keep_bfs = c.keep_bfs ? 1 : 0; d.k_predict = c.k_predict; d.R = c.penalty_radius;
-    d.action_cost = c.action_cost; d.collision_cost = c.collision_cost; d.human_collision_cost = c.human_collision_cost;
-    d.repeat_cost = c.repeat_cost; d.goal_reward = c.goal_reward;
-    d.env_offset = (uint32_t)c.env_offset;
-    d.seed = c.seed;
-    // envs per observe_kernel workgroup: 64/N fills a wave's lanes for N <= 8; above that one
-    // env per workgroup measured fastest (c4, 16 agents: 12.4 us vs 14.2 us at 4 envs, tools/sweep_c45.sh)
+    config_geometry(c, d);
     mapf_tuning_default(&e->tune);
-    apply_tuning(d, e->tune);
+    e->max_lds = device_max_group_lds();
+    int want = 0;
+    const int envs = observe_envs(d, e->tune.obs_envs, (size_t)e->max_lds, want);
+    if (envs < 1) {     // refused here, not by the first observe launch
+        const size_t need = observe_launch_lds(d, 1);
+        delete e;
+        return fail(MAPF_EINVAL, "one env's observe workgroup needs " + std::to_string(need) + " bytes of LDS, over the device's " +
+                                     std::to_string(device_max_group_lds()));
+    }
+    apply_tuning(d, e->tune, envs);
 
     // fp64 lookup table, computed exactly like the reference (numpy sqrt)
     const double R = (double)c.penalty_radius;
@@ -457,6 +490,23 @@ int mapf_pace_gate(int32_t t, int32_t slack, int32_t live, int32_t *word, uint32
     *word = w;
     *target = v;
     return 1;
+}
+
+int64_t mapf_observe_lds(const mapf_config *cfg, int32_t obs_envs, int32_t max_lds, int32_t *envs_out) {
+    if (!cfg) return fail(MAPF_EINVAL, "null argument");
+    if (int rc = check_config(*cfg)) return rc;
+    if (obs_envs < 0 || obs_envs > 64) return fail(MAPF_EINVAL, "obs_envs must be in 0..64");
+    if (max_lds < 0) return fail(MAPF_EINVAL, "max_lds must be >= 0");
+    DevEnv d{};
+    config_geometry(*cfg, d);
+    int want = 0;
+    // (no limit: the requested count as it is)
+    const int envs = observe_envs(d, obs_envs, max_lds > 0 ? (size_t)max_lds : ~(size_t)0, want);
+    if (envs_out) *envs_out = envs;
+    if (envs < 1)
+        return fail(MAPF_EINVAL, "one env's observe workgroup needs " + std::to_string(observe_launch_lds(d, 1)) +
+                                     " bytes of LDS, over " + std::to_string(max_lds));
+    return (int64_t)observe_launch_lds(d, envs);
 }
 
 // s waits for the deferred aux-stream searches: every one (all), or those due before the

@@ -83,6 +83,15 @@ void launch_plan(const DevEnv &e, int promote, hipStream_t s);
 // bits (here and in launch_step_observe): obs is the packed uint32 [B][N][WPA] buffer (mapf_obs_bits.h)
 void launch_observe(const DevEnv &e, float *obs, float *vec, int nsearch, int parity, hipStream_t s, bool bits = false);
 bool observe_hosts_search(const DevEnv &e);
+// LDS of an observe_kernel workgroup of E envs (bit-stream .. index image, 16-byte round-up, nibble
+// table), and what launch_observe requests for it at most: the four search waves' LDS where the launch
+// may host the search and that is more
+size_t observe_lds(const DevEnv &e, int E);
+size_t observe_launch_lds(const DevEnv &e, int E);
+// envs per observe workgroup: the default rule (64 / N fills a wave's lanes for N <= 8, else 1; at most B),
+// and the largest E <= want whose launch request fits max_lds bytes (0: not even one env does)
+int observe_default_envs(const DevEnv &e);
+int observe_fit_envs(const DevEnv &e, int want, size_t max_lds);
 // after a concurrent search: rewrite the BFS channel of the agents in bfs_list[parity]
 void launch_bfs_fixup(const DevEnv &e, int parity, float *obs, hipStream_t s);
 // committed step + observations in one launch (mapf_fused.hip); the first nsearch

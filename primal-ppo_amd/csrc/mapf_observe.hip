@@ -35,7 +35,7 @@ __global__ __launch_bounds__(256) void observe_kernel(DevEnv e, float *__restric
     const int b0 = ((int)blockIdx.x - nsearch) * E;
     const int nenv = min(E, e.B - b0);
     ObsLds L = obs_layout(e, E, smem);
-    float4 *lut = reinterpret_cast<float4 *>(smem + ((obs_lds_bytes(e, E) + 15) & ~(size_t)15));
+    float4 *lut = reinterpret_cast<float4 *>(smem + ((obs_lds_bytes(e, E) + 15) & ~(size_t)15));   // observe_lds
     obs_lut_init(lut);              // ordered before use by the barrier below
     L.lut = lut;
     obs_init(e, L, E, b0, nenv, obs_map_word(e, b0, nenv, threadIdx.x));
@@ -80,19 +80,34 @@ void launch_bfs_fixup(const DevEnv &e, int parity, float *obs, hipStream_t s) {
     hipLaunchKernelGGL(bfs_fixup_kernel, dim3(64), dim3(256), 0, s, e, parity, obs);
 }
 
-size_t observe_lds(const DevEnv &e) { return ((obs_lds_bytes(e, e.obs_envs) + 15) & ~(size_t)15) + 256; }   // + nibble table
+size_t observe_lds(const DevEnv &e, int E) { return ((obs_lds_bytes(e, E) + 15) & ~(size_t)15) + 256; }   // + nibble table
 
 bool observe_hosts_search(const DevEnv &e) { return e.W <= 32 && e.H <= 64; }
+
+size_t observe_launch_lds(const DevEnv &e, int E) {
+    const size_t lds = observe_lds(e, E);
+    const size_t sl = observe_hosts_search(e) ? 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W) : 0;
+    return sl > lds ? sl : lds;
+}
+
+int observe_default_envs(const DevEnv &e) {
+    const int E = e.N > 8 ? 1 : 64 / e.N;
+    return E > e.B ? e.B : E;
+}
+
+int observe_fit_envs(const DevEnv &e, int want, size_t max_lds) {
+    int E = want;
+    while (E > 0 && observe_launch_lds(e, E) > max_lds) --E;   // the request grows with E
+    return E;
+}
 
 // bits: obs is the packed buffer (the caller never follows a packed launch with launch_bfs_fixup,
 // which writes floats)
 void launch_observe(const DevEnv &e, float *obs, float *vec, int nsearch, int parity, hipStream_t s, bool bits) {
     if (!observe_hosts_search(e)) nsearch = 0;
     const int grid = (e.B + e.obs_envs - 1) / e.obs_envs + nsearch;
-    size_t lds = observe_lds(e);
+    const size_t lds = nsearch > 0 ? observe_launch_lds(e, e.obs_envs) : observe_lds(e, e.obs_envs);
     if (nsearch > 0) {
-        const size_t sl = 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W);
-        if (sl > lds) lds = sl;
         if (bits) hipLaunchKernelGGL((observe_kernel<true, true>), dim3(grid), dim3(256), lds, s, e, obs, vec, nsearch, parity);
         else hipLaunchKernelGGL(observe_kernel<true>, dim3(grid), dim3(256), lds, s, e, obs, vec, nsearch, parity);
     } else {

@@ -90,6 +90,7 @@ SIGNATURES = {
     "mapf_rollout_random_fused": (ctypes.c_int, [P]),
     "mapf_obs_band_skip": (ctypes.c_int, [ctypes.POINTER(MapfConfig), I32, ctypes.c_uint64, P, I32]),
     "mapf_pace_gate": (ctypes.c_int, [I32, I32, I32, P, P]),
+    "mapf_observe_lds": (I64, [ctypes.POINTER(MapfConfig), I32, I32, P]),
     "mapf_tuning_default": (None,[ctypes.POINTER(Tuning)]),
     "mapf_get_tuning": (ctypes.c_int, [P, ctypes.POINTER(Tuning)]),
     "mapf_set_tuning": (ctypes.c_int, [P, ctypes.POINTER(Tuning)]),

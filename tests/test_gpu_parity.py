@@ -424,7 +424,10 @@ def test_rollout_in_place_matches_oracle(name, path):
     run_random_case(name, case, path, expect_rollout_kernel=(1, 2))
 
 
-def run_random_case(name, case, path, expect_rollout_kernel=None, tuning=None, expect_name=None):
+def run_random_case(name, case, path, expect_rollout_kernel=None, tuning=None, expect_name=None, expect_fused=None,
+                    expect_tuning=None):
+    """expect_fused: what env.fused (mapf_step_observe in one launch) must report; expect_tuning:
+    mapf_tuning fields the handle must read back (the forms under test were really set)."""
     B, H, W, n, fov, nch = case["B"], case["H"], case["W"], case["n"], case["fov"], case["nch"]
     rng = np.random.default_rng(5)
     maps, shared = build_maps(case, B, rng)
@@ -436,6 +439,11 @@ def run_random_case(name, case, path, expect_rollout_kernel=None, tuning=None, e
     env.reset_seeded(maps)
     if expect_rollout_kernel is not None:
         assert env.rollout_kernel in np.atleast_1d(expect_rollout_kernel), name
+    if expect_fused is not None:
+        assert env.fused == expect_fused, name
+    if expect_tuning:
+        got = env.tuning()
+        assert {k: got[k] for k in expect_tuning} == dict(expect_tuning), name
     rolling = path in ("rollout", "inplace", "inplace1")
     if rolling:
         kname = env.rollout_kernel_name(slots=path == "rollout")
@@ -852,21 +860,41 @@ def test_split_path_back_to_back_steps_match_oracle(name, B, H, n, fov, nch, ste
     join_deferred) driven back to back with NO host synchronisation, get_state or bfs in
     between -- every step's outputs and observation into [T]-slot device buffers -- so each
     deferred search really runs beside the next step.  Compared with the oracle at the end."""
+    run_split_case(name, B, H, n, fov, nch, steps)
+
+
+def run_split_case(name, B, H, n, fov, nch, steps, tuning=None, bits=False):
+    """tuning: mapf_tuning fields (where the search runs and when it is joined: serial_search,
+    no_defer).  bits: mapf_step_random + mapf_observe_bits in place of mapf_step_observe_random --
+    the packed observation, whose call always joins the search first -- unpacked at the end."""
     rng = np.random.default_rng(11)
+    from mapf_amd.env import unpack_obs as unpack_bits
     from mapf_amd.maps import keep_largest_component, random_map
     maps = np.stack([keep_largest_component(random_map(rng, H, H, 0.3)) for _ in range(B)])
     seed = 0xD0F + B
     env = mk_env(B=B, H=H, W=H, num_agents=n, fov=fov, num_channel=nch, human_mode="random", goal_mode="random",
-                 fix_choice=1, shared_map=False, seed=seed, env_offset=3)
+                 fix_choice=1, shared_map=False, seed=seed, env_offset=3, tuning=tuning)
     env.reset_seeded(maps)
     assert not env.fused, "expected the split (step + observe) path"
+    if tuning:
+        got = env.tuning()
+        assert {k: got[k] for k in tuning} == dict(tuning), name
     dev = env.device
     acts = torch.zeros(steps, B, n, dtype=torch.int32, device=dev)
     obs = torch.full((steps, B, n, nch, fov, fov), float("nan"), device=dev)
     vec = torch.full((steps, B, n, 4), float("nan"), device=dev)
     outs = {k: torch.zeros((steps,) + tuple(v.shape), dtype=v.dtype, device=dev) for k, v in env.out.items()}
+    packed = torch.full((steps, B, n, env.obs_words), -1, dtype=torch.int32, device=dev) if bits else None
     for t in range(steps):
-        env.step_observe(acts[t], obs[t], vec[t], random_policy=True, out={k: v[t] for k, v in outs.items()})
+        if bits:
+            env.step_random(acts[t])
+            for k, v in outs.items():             # stream-ordered device copies: still no host synchronisation
+                v[t].copy_(env.out[k])
+            env.observe_bits(packed[t], vec[t])
+        else:
+            env.step_observe(acts[t], obs[t], vec[t], random_policy=True, out={k: v[t] for k, v in outs.items()})
+    if bits:
+        unpack_bits(packed, nch, fov, out=obs)
     torch.cuda.synchronize()
     acts, obs, vec, outs = acts.cpu().numpy(), obs.cpu().numpy(), vec.cpu().numpy(), host(outs)
     cfg = O.make_config(H, H, n, fov, nch, human_mode=1, goal_mode=1, fix_choice=1, seed=seed, env_offset=3)
