@@ -30,14 +30,16 @@ class OracleConfig(ctypes.Structure):
 
 def make_config(H, W, N, F=11, C=6, *, use_da=0, use_hp=0, lifelong=1, human_mode=0, goal_mode=0,
                 fix_choice=0, keep_bfs=1, max_seq=1, max_human_seq=1, seed=1234, num_envs=1,
-                env_offset=0, shared_map=1):
+                env_offset=0, shared_map=1, k_predict=5, penalty_radius=5, action_cost=-0.3, collision_cost=-2.0,
+                human_collision_cost=-2.0, repeat_cost=-0.35, goal_reward=1.5):
     """Defaults follow alg_parameters.py (EnvParameters :27-48, TrainingParameters :76-78)."""
     c = OracleConfig()
     c.num_envs, c.num_agents, c.height, c.width, c.fov, c.num_channel = num_envs, N, H, W, F, C
     c.use_da, c.use_hp, c.lifelong, c.human_mode, c.goal_mode, c.fix_choice = use_da, use_hp, lifelong, human_mode, goal_mode, fix_choice
     c.shared_map, c.keep_bfs, c.max_seq, c.max_human_seq = shared_map, keep_bfs, max_seq, max_human_seq
-    c.k_predict, c.penalty_radius = 5, 5
-    c.action_cost, c.collision_cost, c.human_collision_cost, c.repeat_cost, c.goal_reward = -0.3, -2.0, -2.0, -0.35, 1.5
+    c.k_predict, c.penalty_radius = k_predict, penalty_radius
+    c.action_cost, c.collision_cost, c.human_collision_cost = action_cost, collision_cost, human_collision_cost
+    c.repeat_cost, c.goal_reward = repeat_cost, goal_reward
     c.env_offset, c.seed = env_offset, seed
     return c
 

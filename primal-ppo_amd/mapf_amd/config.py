@@ -97,8 +97,13 @@ GOAL_MODES = {"sequence": 0, "random": 1}
 
 def make_config(num_envs, height, width, *, num_agents=None, fov=None, num_channel=None, use_da=False,
                 use_hp=False, human_mode="random", goal_mode="random", fix_choice=1, shared_map=True,
-                keep_bfs=True, max_seq=1, max_human_seq=2, env_offset=0, seed=None):
-    """Build a mapf_config from the reference's parameter classes."""
+                keep_bfs=True, max_seq=1, max_human_seq=2, env_offset=0, seed=None, k_predict=None,
+                penalty_radius=None, lifelong=None, action_cost=None, collision_cost=None, human_collision_cost=None,
+                repeat_cost=None, goal_reward=None):
+    """Build a mapf_config from the reference's parameter classes (None: the class's value)."""
+    def pick(value, default):
+        return default if value is None else value
+
     c = MapfConfig()
     c.num_envs = num_envs
     c.num_agents = EnvParameters.N_AGENTS if num_agents is None else num_agents
@@ -106,7 +111,7 @@ def make_config(num_envs, height, width, *, num_agents=None, fov=None, num_chann
     c.fov = EnvParameters.FOV_SIZE if fov is None else fov
     c.num_channel = NetParameters.NUM_CHANNEL if num_channel is None else num_channel
     c.use_da, c.use_hp = int(use_da), int(use_hp)
-    c.lifelong = int(EnvParameters.LIFELONG)
+    c.lifelong = int(pick(lifelong, EnvParameters.LIFELONG))
     c.human_mode = HUMAN_MODES[human_mode] if isinstance(human_mode, str) else int(human_mode)
     c.goal_mode = GOAL_MODES[goal_mode] if isinstance(goal_mode, str) else int(goal_mode)
     c.fix_choice = int(fix_choice)
@@ -114,13 +119,13 @@ def make_config(num_envs, height, width, *, num_agents=None, fov=None, num_chann
     c.keep_bfs = int(keep_bfs)
     c.max_seq = max_seq
     c.max_human_seq = max_human_seq
-    c.k_predict = TrainingParameters.K_TIMESTEP_PREDICT
-    c.penalty_radius = EnvParameters.PENALTY_RADIUS
-    c.action_cost = EnvParameters.ACTION_COST
-    c.collision_cost = EnvParameters.COLLISION_COST
-    c.human_collision_cost = EnvParameters.HUMAN_COLLISION_COST
-    c.repeat_cost = EnvParameters.REPEAT_POS
-    c.goal_reward = EnvParameters.GOAL_REWARD
+    c.k_predict = pick(k_predict, TrainingParameters.K_TIMESTEP_PREDICT)
+    c.penalty_radius = pick(penalty_radius, EnvParameters.PENALTY_RADIUS)
+    c.action_cost = pick(action_cost, EnvParameters.ACTION_COST)
+    c.collision_cost = pick(collision_cost, EnvParameters.COLLISION_COST)
+    c.human_collision_cost = pick(human_collision_cost, EnvParameters.HUMAN_COLLISION_COST)
+    c.repeat_cost = pick(repeat_cost, EnvParameters.REPEAT_POS)
+    c.goal_reward = pick(goal_reward, EnvParameters.GOAL_REWARD)
     c.env_offset = env_offset
     c.seed = SetupParameters.SEED if seed is None else seed
     return c

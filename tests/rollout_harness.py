@@ -32,11 +32,14 @@ def case_setup(cases, name, seed_base):
     return case, maps, shared, seed_base + len(name)
 
 
-def case_env(cases, name, seed_base, tuning=None, **kw):
+def case_env(cases, name, seed_base, tuning=None, cfg=None, **kw):
+    """cfg: config fields off their defaults (k_predict, penalty_radius, lifelong, the costs); the same
+    dict goes to oracle_rollout, so that the device and the oracle cannot differ in them."""
     case, maps, shared, seed = case_setup(cases, name, seed_base)
     env = mk_env(B=case["B"], H=case["H"], W=case["W"], num_agents=case["n"], fov=case["fov"], num_channel=case["nch"],
                  use_da=case.get("da", 0), use_hp=case.get("hp", 0), human_mode=case.get("human", "random"),
-                 goal_mode="random", fix_choice=1, shared_map=shared, seed=seed, env_offset=7, tuning=tuning, **kw)
+                 goal_mode="random", fix_choice=1, shared_map=shared, seed=seed, env_offset=7, tuning=tuning, **dict(cfg or {}),
+                 **kw)
     env.reset_seeded(maps)
     return env, case, maps, shared, seed
 
@@ -69,18 +72,18 @@ def preset_envs(cfg, count):
 
 
 # ------------------------------------------------------------------ the oracle
-def oracle_rollout(cases, name, seed_base, steps, bounds, pick):
-    """`steps` steps of the case on the CPU oracle, one OracleEnv per env.  pick(oe, b, t, maps_b) ->
+def oracle_rollout(cases, name, seed_base, steps, bounds, pick, cfg=None):
+    """`steps` steps of the case on the CPU oracle, one OracleEnv per env (cfg: as case_env's).  pick(oe, b, t, maps_b) ->
     (actions of env b at step t, None or a dict of extras).  Returns (ref, state), read-only: ref[k] =
     [steps, B, ...] for the step outputs, "obs", "vec", "actions" and the extras; state[t] = cells,
     goals, human, BFS maps and the oracle's error count after t steps, for every t in `bounds`."""
     case, maps, shared, seed = case_setup(cases, name, seed_base)
-    cfg = O.make_config(case["H"], case["W"], case["n"], case["fov"], case["nch"], use_da=case.get("da", 0),
-                        use_hp=case.get("hp", 0), human_mode={"random": 1, "looping": 0}[case.get("human", "random")],
-                        goal_mode=1, fix_choice=1, seed=seed, env_offset=7)
+    ocfg = O.make_config(case["H"], case["W"], case["n"], case["fov"], case["nch"], use_da=case.get("da", 0),
+                         use_hp=case.get("hp", 0), human_mode={"random": 1, "looping": 0}[case.get("human", "random")],
+                         goal_mode=1, fix_choice=1, seed=seed, env_offset=7, **dict(cfg or {}))
     oracles = []
     for b in range(case["B"]):
-        oe = O.OracleEnv(cfg, env_id=7 + b)
+        oe = O.OracleEnv(ocfg, env_id=7 + b)
         oe.reset_random(maps if shared else maps[b])
         oracles.append(oe)
     rows, state = [], {}

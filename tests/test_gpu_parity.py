@@ -425,9 +425,14 @@ def test_rollout_in_place_matches_oracle(name, path):
 
 
 def run_random_case(name, case, path, expect_rollout_kernel=None, tuning=None, expect_name=None, expect_fused=None,
-                    expect_tuning=None):
+                    expect_tuning=None, cfg=None, obs_bits=False):
     """expect_fused: what env.fused (mapf_step_observe in one launch) must report; expect_tuning:
-    mapf_tuning fields the handle must read back (the forms under test were really set)."""
+    mapf_tuning fields the handle must read back (the forms under test were really set).  cfg: config
+    fields off their defaults (k_predict, penalty_radius, lifelong, the costs), given to the device's
+    and the oracle's make_config alike.  obs_bits (rollout paths): the launches write the packed
+    observation, unpacked for the comparison."""
+    cfg = dict(cfg or {})
+    goal_reward = np.float32(cfg.get("goal_reward", 1.5))
     B, H, W, n, fov, nch = case["B"], case["H"], case["W"], case["n"], case["fov"], case["nch"]
     rng = np.random.default_rng(5)
     maps, shared = build_maps(case, B, rng)
@@ -435,7 +440,7 @@ def run_random_case(name, case, path, expect_rollout_kernel=None, tuning=None, e
     seed = 0x5EED0000 + len(name)
     env = mk_env(B=B, H=H, W=W, num_agents=n, fov=fov, num_channel=nch, use_da=case.get("da", 0),
                  use_hp=case.get("hp", 0), human_mode=human, goal_mode="random", fix_choice=1, shared_map=shared,
-                 seed=seed, env_offset=7, tuning=tuning)
+                 seed=seed, env_offset=7, tuning=tuning, **cfg)
     env.reset_seeded(maps)
     if expect_rollout_kernel is not None:
         assert env.rollout_kernel in np.atleast_1d(expect_rollout_kernel), name
@@ -446,15 +451,17 @@ def run_random_case(name, case, path, expect_rollout_kernel=None, tuning=None, e
         assert {k: got[k] for k in expect_tuning} == dict(expect_tuning), name
     rolling = path in ("rollout", "inplace", "inplace1")
     if rolling:
-        kname = env.rollout_kernel_name(slots=path == "rollout")
+        kname = env.rollout_kernel_name(slots=path == "rollout", obs_bits=obs_bits)
         if expect_name is not None:
-            assert kname == expect_name, (name, env.rollout_plan(slots=path == "rollout"))
+            assert kname == expect_name, (name, env.rollout_plan(slots=path == "rollout", obs_bits=obs_bits))
+    else:
+        assert not obs_bits, "obs_bits goes with the rollout paths"
     hm = {"random": 1, "looping": 0}[human]
-    cfg = O.make_config(H, W, n, fov, nch, use_da=case.get("da", 0), use_hp=case.get("hp", 0), human_mode=hm,
-                        goal_mode=1, fix_choice=1, seed=seed, env_offset=7)
+    ocfg = O.make_config(H, W, n, fov, nch, use_da=case.get("da", 0), use_hp=case.get("hp", 0), human_mode=hm,
+                         goal_mode=1, fix_choice=1, seed=seed, env_offset=7, **cfg)
     oracles = []
     for b in range(B):
-        oe = O.OracleEnv(cfg, env_id=7 + b)
+        oe = O.OracleEnv(ocfg, env_id=7 + b)
         oe.reset_random(maps if shared else maps[b])
         oracles.append(oe)
     st = env.get_state()
@@ -475,11 +482,15 @@ def run_random_case(name, case, path, expect_rollout_kernel=None, tuning=None, e
                 T = min(RT, case["steps"] - t)
                 k = T if path == "rollout" else 1          # in place: one [B]-leading set of buffers
                 roll = dict(actions=torch.full((k, B, n), -9, dtype=torch.int32, device=env.device),
-                            obs=torch.full((k, B, n, nch, fov, fov), float("nan"), device=env.device),
+                            obs=torch.full((k, B, n, env.obs_words), -1, dtype=torch.int32, device=env.device) if obs_bits
+                            else torch.full((k, B, n, nch, fov, fov), float("nan"), device=env.device),
                             vec=torch.full((k, B, n, 4), float("nan"), device=env.device),
                             out={key: torch.full((k,) + tuple(v.shape), -7, dtype=v.dtype, device=env.device)
                                  for key, v in env.out.items()})
-                env.rollout_random(T, slots=path == "rollout", **roll)
+                env.rollout_random(T, slots=path == "rollout", obs_bits=obs_bits, **roll)
+                if obs_bits:      # unpacked on the host (torch bit operations), not by the library's kernel
+                    from mapf_amd.env import unpack_obs as unpack_bits
+                    roll["obs"] = unpack_bits(roll["obs"].cpu(), nch, fov)
                 roll = dict(actions=roll["actions"].cpu().numpy(), obs=roll["obs"], vec=roll["vec"],
                             out=host(roll["out"]))
             k = t % RT if path == "rollout" else 0
@@ -517,6 +528,9 @@ def run_random_case(name, case, path, expect_rollout_kernel=None, tuning=None, e
                            ("actions_fixed", "fixed"), ("goals_reached", "goals"), ("constraints", "constr")]:
                 np.testing.assert_array_equal(out[k][b], o[key].astype(out[k].dtype), err_msg=f"{name} t={t} b={b} {k}")
             assert out["shadow_goals"][b] == o["shadow"]
+            # runner.py:89-91, in float32 like the reward itself
+            total = np.where(o["goals"] == 1, o["reward"] + goal_reward, o["reward"]).astype(np.float32)
+            np.testing.assert_array_equal(out["reward_total"][b], total, err_msg=f"{name} t={t} b={b} reward_total")
             if b % 4 == t % 4 or path in ("inplace", "inplace1"):
                 oo, ov = oe.observe()
                 np.testing.assert_array_equal(obs[b], oo, err_msg=f"{name} t={t} b={b} obs")

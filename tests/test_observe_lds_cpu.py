@@ -21,10 +21,12 @@ LIMITS = (65536, 163840)
 K_PREDICT = 5      # make_config: TrainingParameters.K_TIMESTEP_PREDICT
 
 
-def config(N, H, W, F, C, shared, B, keep_bfs=True):
+def config(N, H, W, F, C, shared, B, keep_bfs=True, k_predict=None):
+    """k_predict None: make_config's own value, which must be K_PREDICT (what regions() assumes by default)."""
     from mapf_amd.config import make_config
-    cfg = make_config(B, H, W, num_agents=N, fov=F, num_channel=C, shared_map=shared, keep_bfs=keep_bfs)
-    assert cfg.k_predict == K_PREDICT
+    cfg = make_config(B, H, W, num_agents=N, fov=F, num_channel=C, shared_map=shared, keep_bfs=keep_bfs,
+                      k_predict=k_predict)
+    assert cfg.k_predict == (K_PREDICT if k_predict is None else k_predict)
     return cfg
 
 
@@ -66,8 +68,8 @@ def search_lds(H, W):
     return 4 * ((max(3 * 64 * 4, ((H * W + 7) & ~7) * 2) + 15) & ~15)
 
 
-def request(N, H, W, F, C, shared, keep_bfs, E):
-    return max(sum(regions(N, H, W, F, C, shared, keep_bfs, E).values()), search_lds(H, W))
+def request(N, H, W, F, C, shared, keep_bfs, E, K=K_PREDICT):
+    return max(sum(regions(N, H, W, F, C, shared, keep_bfs, E, K).values()), search_lds(H, W))
 
 
 SIZES = [(s, s) for s in (10, 20, 40, 64, 80, 128)] + [(64, 32)]
@@ -177,6 +179,24 @@ def test_request_is_the_sum_of_its_regions():
     # stream 5,824 + occupancy 960 + map 120 + agents 544 + prediction 192 + image 3,200 = 10,840 -> 10,848 + 256
     assert sum(regions(8, 20, 20, 11, 6, True, True, 8).values()) == 11104
     assert regions(1, 80, 80, 11, 6, False, True, 64)["index_image"] == 409600
+
+
+@pytest.mark.parametrize("K", [0, 1, 64])
+def test_request_follows_k_predict(K):
+    """The prediction rows are E * k_predict words (+ E counts): at K = 0 the region is the counts alone,
+    and the request at every byte point equals the plain sum with that K -- 4 * E * (K - 5) bytes from the
+    default's, before the 16-byte round-up."""
+    for N, H, W, F, C, shared, keep_bfs, E in BYTE_POINTS:
+        cfg = config(N, H, W, F, C, shared, 4096, keep_bfs=keep_bfs, k_predict=K)
+        r = regions(N, H, W, F, C, shared, keep_bfs, E, K=K)
+        assert r["prediction"] == 4 * E * (K + 1)
+        base = regions(N, H, W, F, C, shared, keep_bfs, E)
+        assert sum(r.values()) - r["round_up"] == sum(base.values()) - base["round_up"] + 4 * E * (K - K_PREDICT)
+        want = request(N, H, W, F, C, shared, keep_bfs, E, K)
+        assert observe_lds(cfg, E, 0) == (want, E), (K, N, H, W, F, C, shared, keep_bfs, E)
+    # c2, 8 envs, by hand: 11,104 B at K = 5 is 10,840 + 8 + 256; K = 64 adds 8 * 59 * 4 = 1,888 -> 12,728 -> 12,736 + 256
+    assert observe_lds(config(8, 20, 20, 11, 6, True, 4096, k_predict=64), 8, 0)[0] == 12992
+    assert observe_lds(config(8, 20, 20, 11, 6, True, 4096, k_predict=0), 8, 0)[0] == 10688 + 256
 
 
 NAMED = [(1, 80, 80, 11, False, 64), (2, 80, 80, 9, True, 32), (1, 64, 64, 7, False, 64)]
