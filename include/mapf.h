@@ -392,7 +392,18 @@ int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent);
  *      twice at the same clock changes nothing the second time.
  *   2. Candidates: action a in 0..4 with target q = p_i + d(a) is admitted iff the step would give
  *      it neither status -1 nor -2: q inside the map and free, q != hn, and not (p_i == hn and
- *      q == h).  C_i = the admitted actions in ascending mapf_pibt_key(D_i[q], a, t, i).
+ *      q == h).  C_i = the admitted actions in ascending mapf_pibt_key(dist', a, t, i), where
+ *      dist = D_i[q] and, with the handle's human weight w in 0..16 (mapf_set_pibt_human_weight; 0
+ *      by default) and R = penalty_radius:
+ *        d2 = |q - hn|^2 in cells;
+ *        level(R, d2) = 0 if d2 > constr_d2(R), else R - floor(sqrt(d2)), constr_d2(R) = the largest
+ *          d2 with (R - sqrt(d2)) / R >= 0.01 in fp64 (24 for R = 5): level >= 1 exactly where an
+ *          agent that ends the step on q is counted in `constraints` -- hn is the human's cell after
+ *          the step --, one more per cell nearer the human, as the cost reward rises;
+ *        dist' = dist if dist < 0 (unreachable stays 0x7FFF), else min(dist + w * level(R, d2), 0x7FFE).
+ *      Staying (a = 0) is priced at the agent's own cell like any other target.  With w = 0,
+ *      dist' = dist.  The weight only reorders the admitted actions: admission, the ages and the
+ *      solve do not depend on it.
  *   3. Solve: next_i undecided for all agents; in the order (age descending, index ascending)
  *      every still undecided agent calls PIBT(i, none):
  *        PIBT(i, parent): for (a, q) in C_i:
@@ -415,6 +426,17 @@ int mapf_pibt_actions(mapf_env *env, int32_t *actions, void *stream);
  * k0 = (clock + agent) & 3 (the descent policy's rotation).  The five keys of one agent are
  * distinct. */
 int mapf_pibt_key(int32_t dist, int32_t action, uint32_t clock, int32_t agent);
+/* The human weight w of step 2: MAPF_EINVAL on a null env or a weight outside 0..16, and nothing
+ * changes then.  No device call; the weight is an argument of the next mapf_pibt_actions /
+ * mapf_rollout_pibt launch.  A captured launch keeps the weight it was captured with (its
+ * argument block is stored at capture): set the weight before capturing.  Resets and
+ * mapf_set_state do not touch it. */
+int mapf_set_pibt_human_weight(mapf_env *env, int32_t weight);
+/* The handle's human weight, or MAPF_EINVAL on a null env. */
+int mapf_get_pibt_human_weight(const mapf_env *env);
+/* level(penalty_radius, d2) of step 2, on the host (the function the kernels run).  MAPF_EINVAL
+ * for a radius outside 1..64 or d2 < 0. */
+int mapf_pibt_human_level(int32_t penalty_radius, int32_t d2);
 /* Step 3 on the host, plain sequential code with no device call: pos [n][2] (row, col), key [n][5]
  * (negative = not admitted), age [n] -> actions [n]; bit i of *failed = agent i's pick failed.
  * MAPF_EINVAL on n outside 1..64, a null pointer or two agents on one cell. */
@@ -437,7 +459,8 @@ int mapf_rollout_pibt(mapf_env *env, int32_t T, int32_t slots, int32_t *actions_
  * rollout_random_pibt_kernel<ST,SUBS,BAND>, rollout_wide_pibt_kernel<T,RW,ST> and
  * rollout_wide3_pibt_kernel<T,RW,ST> with the same leading template arguments (ST: 0 plain stores,
  * 1 nontemporal -- printed "false" / "true" --, 2 packed bits).  Kind 0:
- * "pibt_actions+step_observe", the per-step launches. */
+ * "pibt_actions+step_observe", the per-step launches.  With a human weight w > 0 the text ends
+ * with " human_weight=<w>" -- a run-time argument of the same kernels --; with w = 0 nothing is added. */
 int mapf_rollout_pibt_plan(const mapf_env *env, int32_t slots, char *buf, int32_t n);
 
 /* Copy agent.bfsMap for every agent: DEVICE int16 [B][N][H][W] (requires keep_bfs). */

@@ -240,6 +240,7 @@ int mapf_create(const mapf_config *cfg, int device, mapf_env **out) {
                                      std::to_string(device_max_group_lds()));
     }
     apply_tuning(d, e->tune, envs);
+    d.pibt_w = 0;       // the PIBT policy is blind to the safety radius until mapf_set_pibt_human_weight
 
     // fp64 lookup table, computed exactly like the reference (numpy sqrt)
     const double R = (double)c.penalty_radius;
@@ -354,7 +355,12 @@ int mapf_rollout_descent_plan(const mapf_env *e, int32_t slots, char *buf, int32
 }
 
 int mapf_rollout_pibt_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
-    return rollout_plan_impl(e, ROLLOUT_PIBT, slots, buf, n);
+    const int kind = rollout_plan_impl(e, ROLLOUT_PIBT, slots, buf, n);
+    if (kind >= 0 && e->d.pibt_w != 0) {    // the weight is a run-time value of the same kernel: a trailing word
+        const size_t len = std::strlen(buf);
+        std::snprintf(buf + len, (size_t)n - len, " human_weight=%d", pibt_w_weight(e->d.pibt_w));
+    }
+    return kind;
 }
 
 int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent) {
@@ -363,6 +369,37 @@ int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent) {
 
 int mapf_pibt_key(int32_t dist, int32_t action, uint32_t clock, int32_t agent) {
     return pibt_key((int)dist, (int)action, clock, (int)agent);
+}
+
+// the largest d2 with (R - sqrt(d2)) / R >= 0.01 in fp64: mapf_create's rule for DevEnv::constr_d2
+static int constr_d2_of(int radius) {
+    const double R = (double)radius;
+    int best = -1;
+    for (int k = 0; k <= radius * radius; ++k) {
+        double v = R - std::sqrt((double)k);
+        if (!(v > 0.0)) v = 0.0;
+        if (v / R >= 0.01) best = k;
+    }
+    return best;
+}
+
+int mapf_pibt_human_level(int32_t penalty_radius, int32_t d2) {
+    if (penalty_radius < 1 || penalty_radius > 64) return fail(MAPF_EINVAL, "penalty_radius must be in 1..64");
+    if (d2 < 0) return fail(MAPF_EINVAL, "d2 must be >= 0");
+    return pibt_human_level((int)penalty_radius, constr_d2_of((int)penalty_radius), (int)d2);
+}
+
+int mapf_set_pibt_human_weight(mapf_env *e, int32_t weight) {
+    if (!e) return fail(MAPF_EINVAL, "null argument");
+    if (weight < 0 || weight > 16) return fail(MAPF_EINVAL, "the PIBT human weight must be in 0..16");
+    // a kernel argument of the next pick or rollout launch: no device call
+    e->d.pibt_w = pibt_w_pack((int)weight, e->d.R, e->d.constr_d2);
+    return MAPF_OK;
+}
+
+int mapf_get_pibt_human_weight(const mapf_env *e) {
+    if (!e) return fail(MAPF_EINVAL, "null argument");
+    return pibt_w_weight(e->d.pibt_w);
 }
 
 // Step 3 of the policy (mapf.h: mapf_pibt_actions), sequentially: the recursion as the chain of

@@ -49,6 +49,10 @@ struct DevEnv {
     int use_da, use_hp, lifelong, human_mode, goal_mode, fix_choice, shared_map, keep_bfs, k_predict, R;
     float action_cost, collision_cost, human_collision_cost, repeat_cost, goal_reward;
     uint32_t env_offset;
+    int pibt_w;               // the PIBT policy's human weight (mapf_set_pibt_human_weight): 0 = off, else
+                              // pibt_w_pack(w, R, constr_d2) -- one word, so the rollout kernels hold one SGPR for
+                              // the rule, not three.  In the 4 bytes that padded `seed`: no other field and no
+                              // kernel argument moves
     uint64_t seed;
     int constr_d2;            // largest d2 with (R - sqrt(d2)) / R >= 0.01 in fp64 (mapf_gym.py:633)
     int obs_envs;             // envs per observe workgroup
@@ -75,6 +79,8 @@ struct DevEnv {
     int search_blocks;        // workgroups of the observe launch that run search work
     int band_blocks;          // workgroups of the fused launch that write the zero band (0 = none)
 };
+
+static_assert(offsetof(DevEnv, pibt_w) == 116 && offsetof(DevEnv, seed) == 120, "pibt_w fills the hole before seed");
 
 constexpr uint32_t NO_CELL = 0xFFFFFFFFu;
 // diagnostic buffer prof[]: [PROF_WAVES][8] per-wave phase cycles, then the
@@ -232,6 +238,28 @@ __host__ __device__ inline int pibt_key(int dist, int action, uint32_t clock, in
     const int cost = dist >= 0 ? dist : 0x7FFF;
     const int rank = action == 0 ? 0 : 1 + (int)(((uint32_t)(action - 1) - k0) & 3u);
     return cost * 8 + rank;
+}
+// DevEnv::pibt_w: weight 1..16 | R (1..64) << 8 | constr_d2 (0..4095) << 16; 0 for weight 0
+__host__ __device__ inline int pibt_w_pack(int w, int R, int constr_d2) { return w ? w | (R << 8) | (constr_d2 << 16) : 0; }
+__host__ __device__ inline int pibt_w_weight(int packed) { return packed & 0xFF; }
+__host__ __device__ inline int pibt_w_radius(int packed) { return (packed >> 8) & 0xFF; }
+__host__ __device__ inline int pibt_w_constr_d2(int packed) { return packed >> 16; }
+// The human level of a target cell (include/mapf.h: mapf_pibt_actions step 2, mapf_pibt_human_level):
+// 0 where d2 = |q - hn|^2 > constr_d2 (the step's own `constraints` rule, DevEnv::constr_d2), else
+// R - floor(sqrt(d2)).  The root is taken in fp32 -- any estimate within 1 of the floor will do, so
+// the device takes the bare v_sqrt_f32 -- and two integer compares make it the exact floor.  Straight
+// code: no table, no memory, no division, no branch.  The one function every kernel and the host
+// export run.
+__host__ __device__ inline int pibt_human_level(int R, int constr_d2, int d2) {
+    const uint32_t n = (uint32_t)d2;
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t s = (uint32_t)__builtin_amdgcn_sqrtf((float)n);
+#else
+    uint32_t s = (uint32_t)__builtin_sqrtf((float)n);
+#endif
+    s -= s * s > n ? 1u : 0u;
+    s += (s + 1u) * (s + 1u) <= n ? 1u : 0u;
+    return d2 <= constr_d2 ? R - (int)s : 0;
 }
 
 __device__ inline uint32_t *human_path(const DevEnv &e, int b, int buf) {

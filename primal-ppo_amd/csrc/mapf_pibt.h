@@ -42,11 +42,26 @@ __device__ inline void pibt_candidates(const DevEnv &e, const int16_t *D, uint32
         const bool in = in_map(e, rr, cc);
         v[k] = (int)D[bfs_at(e.W, in ? rr : r, in ? cc : col)];
     }
+    // The human weight (mapf.h, step 2): a reachable target costs pen = w * level(R, |q - hn|^2) more, up
+    // to 0x7FFE.  e.pibt_w (weight, R and constr_d2 in one word) is a kernel argument, so the branch is
+    // wave-uniform and weight 0 runs none of it; the block needs no loaded value, so it runs while the
+    // five map cells are in flight.
+    int pen[NA] = {0, 0, 0, 0, 0};
+    if (e.pibt_w != 0) {
+        const int w = pibt_w_weight(e.pibt_w), R = pibt_w_radius(e.pibt_w), cd2 = pibt_w_constr_d2(e.pibt_w);
+        const int hr = prow(hn), hc = pcol(hn);
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const int y = r + dr(k) - hr, x = col + dc(k) - hc;
+            pen[k] = w * pibt_human_level(R, cd2, y * y + x * x);
+        }
+    }
 #pragma unroll
     for (int k = 0; k < NA; ++k) {
         const uint32_t q = pack(r + dr(k), col + dc(k));
         const bool ok = !((st_mask >> k) & 1u) && q != hn && !(p == hn && q == hp);
-        c[k] = ok ? ((uint32_t)pibt_key(v[k], k, clock, agent) << 3) | (uint32_t)k : PIBT_NONE;
+        const int dist = v[k] < 0 ? v[k] : min(v[k] + pen[k], 0x7FFE);
+        c[k] = ok ? ((uint32_t)pibt_key(dist, k, clock, agent) << 3) | (uint32_t)k : PIBT_NONE;
     }
     // optimal 9-comparator network for 5 keys
     pibt_cx(c[0], c[1]); pibt_cx(c[3], c[4]); pibt_cx(c[2], c[4]); pibt_cx(c[2], c[3]); pibt_cx(c[1], c[4]);

@@ -106,6 +106,9 @@ SIGNATURES = {
     "mapf_pibt_actions": (ctypes.c_int, [P, P, P]),
     "mapf_pibt_key": (ctypes.c_int, [I32, I32, ctypes.c_uint32, I32]),
     "mapf_pibt_host": (ctypes.c_int, [I32, P, P, P, P, P]),
+    "mapf_set_pibt_human_weight": (ctypes.c_int, [P, I32]),
+    "mapf_get_pibt_human_weight": (ctypes.c_int, [P]),
+    "mapf_pibt_human_level": (ctypes.c_int, [I32, I32]),
     "mapf_flush": (ctypes.c_int, [P, P]),
     "mapf_release_captures": (ctypes.c_int, [P]),
     "mapf_random_actions": (ctypes.c_int, [P, P, P]),

@@ -564,6 +564,24 @@ class BatchedMapfGym:
         _lib.check(_lib.lib().mapf_pibt_actions(self.h, _ptr(out), _stream(self.device)))
         return out
 
+    def set_pibt_human_weight(self, weight):
+        """The PIBT policy's human weight w, an int in 0..16 (mapf_set_pibt_human_weight; mapf.h has the
+        rule): a reachable target inside the human's safety radius costs w per level more.  0, the
+        default, is the plain policy.  Takes effect at the next pibt_actions / rollout(T, "pibt");
+        a captured launch keeps the weight it was captured with.  Resets leave it alone."""
+        if isinstance(weight, bool) or not isinstance(weight, (int, np.integer)):
+            raise TypeError(f"human weight: expected an int in 0..16, got {type(weight).__name__}")
+        if not 0 <= int(weight) <= 16:
+            raise ValueError(f"human weight must be in 0..16, got {int(weight)}")
+        _lib.check(_lib.lib().mapf_set_pibt_human_weight(self.h, int(weight)))
+
+    @property
+    def pibt_human_weight(self):
+        """The PIBT policy's human weight (mapf_get_pibt_human_weight)."""
+        w = _lib.lib().mapf_get_pibt_human_weight(self.h)
+        _lib.check(min(w, 0))
+        return w
+
     def random_actions(self, out=None):
         out = self.actions if out is None else out
         _check(out, torch.int32, self.B * self.N, self.device, "actions")

@@ -192,10 +192,22 @@ def descent_policy():
     return _bfs_policy("descent_actions", "descent_policy")
 
 
-def pibt_policy():
+def pibt_policy(human_weight=None):
     """The PIBT planner: one collision-free step for all agents from their BFS maps
-    (env.pibt_actions, mapf_pibt_actions)."""
-    return _bfs_policy("pibt_actions", "pibt_policy")
+    (env.pibt_actions, mapf_pibt_actions).  human_weight: None leaves the env's setting alone; an int
+    in 0..16 is set on the env the policy is called with (env.set_pibt_human_weight)."""
+    pick = _bfs_policy("pibt_actions", "pibt_policy")
+    if human_weight is None:
+        return pick
+
+    done = []                           # the env the weight was last set on: one library call per env, not per step
+
+    def policy(obs, vec, env, t):
+        if not done or done[0] is not env:
+            env.set_pibt_human_weight(human_weight)
+            done[:] = [env]
+        return pick(obs, vec, env, t)
+    return policy
 
 
 def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, use_da=False, use_hp=False,

@@ -4,18 +4,23 @@ one GPU.
 
   python tools/bench_pibt.py --config c2                       # this build: random / descent / pibt / per-step
   python tools/bench_pibt.py --config c2 --baseline-lib primal-ppo_amd/lib/libmapf_parent.so --rounds 3
+  python tools/bench_pibt.py --config c4 --human-weight 2 --skip-per-step      # the planner at human weight 2
 
 Each measurement process builds the preset's env (bench.py's presets and maps), prepares one launcher
 per policy over the same [T]-slot buffers (T = 256, c5: 87), every policy on a handle of its own (so
 each plays its own episode from the same reset), runs one untimed round, then `--pairs` alternated
 rounds random / descent / pibt, each launch between two HIP events, and then `--pairs` per-step
 series: PIBT as T x (pibt_actions, step_observe) calls in place, between two HIP events over the whole
-series.  From the last timed launch of descent and of PIBT, per env-step: goals reached, agents with
-status -3, and actions fixActions rewrote (actions_fixed != actions).  With --baseline-lib the driver
-(which never opens the GPU) starts fresh child processes in turn, baseline / this build, `--rounds`
-times: the baseline library (the parent commit's build, which has no PIBT entry points) runs its
-random and descent policies only.  The verdicts printed at the end:
-  (i)   this build's random and descent medians lie inside the baseline's own min..max spreads;
+series (--skip-per-step leaves it out).  --human-weight W sets the PIBT handle's human weight
+(mapf_set_pibt_human_weight; 0, the default, is the plain policy) before its launches.  From the last
+timed launch of descent and of PIBT, per env-step: goals reached, agents with status -3 and -2, actions
+fixActions rewrote (actions_fixed != actions), agents counted in `constraints`, and the mean cost reward
+per agent-step.  With --baseline-lib the driver (which never opens the GPU) starts fresh child processes
+in turn, baseline / this build, `--rounds` times: a baseline library runs the policies it has -- a build
+from before the PIBT entry points its random and descent policies only, one from before the human weight
+its PIBT policy at weight 0 whatever W is.  The verdicts printed at the end:
+  (i)   this build's random, descent and (at weight 0, where the baseline has it) pibt medians lie inside
+        the baseline's own min..max spreads;
   (ii)  the one-launch PIBT median is below the per-step median by more than the per-step series' own
         min..max spread.
 """
@@ -30,6 +35,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "primal-ppo_amd")]
 PIBT_FNS = ("mapf_rollout_pibt", "mapf_rollout_pibt_plan", "mapf_pibt_actions", "mapf_pibt_key", "mapf_pibt_host")
+HUMAN_FNS = ("mapf_set_pibt_human_weight", "mapf_get_pibt_human_weight", "mapf_pibt_human_level")
 
 
 def measure(args):
@@ -41,8 +47,12 @@ def measure(args):
     import bench
     from mapf_amd import _lib
     has = all(hasattr(ctypes.CDLL(_lib.LIB_PATH), n) for n in PIBT_FNS)
+    has_weight = has and all(hasattr(ctypes.CDLL(_lib.LIB_PATH), n) for n in HUMAN_FNS)
     if not has:                           # a build from before the PIBT entry points: random and descent only
         for n in PIBT_FNS:
+            _lib.SIGNATURES.pop(n)
+    if not has_weight:                    # a build from before the human weight: the plain policy
+        for n in HUMAN_FNS:
             _lib.SIGNATURES.pop(n)
     from mapf_amd.config import make_config
     from mapf_amd.env import BatchedMapfGym
@@ -71,6 +81,8 @@ def measure(args):
     plan = {"random": envs["random"].rollout_plan(slots, slots), "descent": envs["descent"].rollout_descent_plan(slots, slots)}
     if has:
         envs["pibt"] = penv = make_env()
+        if has_weight:
+            penv.set_pibt_human_weight(args.human_weight)
         launch["pibt"] = penv.rollout_launcher(T, policy="pibt", **kw)
         plan["pibt"] = penv.rollout_pibt_plan(slots, slots)
         out0 = {k: v[0] for k, v in out.items()}
@@ -78,7 +90,8 @@ def measure(args):
         def per_step():
             for _ in range(T):
                 penv.step_observe(penv.pibt_actions(acts[0]), obs[0], vec[0], out=out0)
-        launch["per-step"] = per_step
+        if not args.skip_per_step:
+            launch["per-step"] = per_step
     times = {k: [] for k in launch}
     quality = {}
     # the persistent launches first, the per-step series after them: its launches leave the GPU mostly
@@ -102,10 +115,13 @@ def measure(args):
                 quality[k] = {"goals": round(float(out["goals_reached"].sum()) / steps, 5),
                               "status_-3": round(float((out["status"] == -3).sum()) / steps, 5),
                               "status_-2": round(float((out["status"] == -2).sum()) / steps, 5),
-                              "rewritten": round(float((out["actions_fixed"] != acts).sum()) / steps, 5)}
+                              "rewritten": round(float((out["actions_fixed"] != acts).sum()) / steps, 5),
+                              "constraints": round(float(out["constraints"].sum()) / steps, 5),
+                              "mean_cost": round(float(out["cost"].sum()) / (steps * N), 6)}
     c = sum(e.counters() for e in envs.values())
     print(json.dumps({"config": args.config, "envs": B, "buffers": "slots" if slots else "in place",
-                      "lib": os.path.basename(_lib.LIB_PATH), "T": T, "us_per_step": times, "plan": plan,
+                      "lib": os.path.basename(_lib.LIB_PATH), "T": T,
+                      "human_weight": args.human_weight if has_weight else 0, "us_per_step": times, "plan": plan,
                       "per_env_step": quality, "counters": [int(x) for x in c[:8]]}), flush=True)
 
 
@@ -117,18 +133,22 @@ def main():
     ap.add_argument("--pairs", type=int, default=6, help="timed rounds per process")
     ap.add_argument("--rounds", type=int, default=3, help="with --baseline-lib: baseline / this build alternations")
     ap.add_argument("--lib", default=None, help="library to measure (default: the package's)")
-    ap.add_argument("--baseline-lib", default=None, help="a baseline build to alternate with (random and descent only)")
+    ap.add_argument("--baseline-lib", default=None, help="a baseline build to alternate with (the policies it has)")
+    ap.add_argument("--human-weight", type=int, default=0, help="the PIBT policy's human weight, 0..16 (default 0: off)")
+    ap.add_argument("--skip-per-step", action="store_true", help="leave out the per-step PIBT series")
     ap.add_argument("--inplace", action="store_true", help="the [B]-leading buffers instead of [T]-slot buffers")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child or not args.baseline_lib:
         measure(args)
         return
-    series = {"baseline random": [], "baseline descent": [], "random": [], "descent": [], "pibt": [], "per-step": []}
+    series = {"baseline random": [], "baseline descent": [], "baseline pibt": [], "baseline per-step": [],
+              "random": [], "descent": [], "pibt": [], "per-step": []}
     for r in range(args.rounds):
         for which, lib in (("baseline", args.baseline_lib), ("new", args.lib)):
             cmd = [sys.executable, os.path.abspath(__file__), "--child", "--config", args.config, "--T", str(args.T),
-                   "--pairs", str(args.pairs)] + (["--lib", lib] if lib else []) + (["--inplace"] if args.inplace else []) + ["--envs", str(args.envs)]
+                   "--pairs", str(args.pairs)] + (["--lib", lib] if lib else []) + (["--inplace"] if args.inplace else []) + ["--envs", str(args.envs)] + \
+                ["--human-weight", str(args.human_weight)] + (["--skip-per-step"] if args.skip_per_step else [])
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             if res.returncode != 0:
                 sys.stderr.write(res.stderr[-3000:])
@@ -137,17 +157,23 @@ def main():
             print(r, which, json.dumps(d), flush=True)
             for k, v in d["us_per_step"].items():
                 series[("baseline " if which == "baseline" else "") + k] += v
+            if which == "new":
+                new = d
     print(f"\n{args.config} ({d['envs']} envs): us per step, per launch of T = {d['T']} steps " +
           ("in place" if args.inplace else "into slots (launcher, band-clean after its first call)"))
     stat = {}
     for k, v in series.items():
+        if not v:                         # a series this run or the baseline does not have
+            continue
         stat[k] = (statistics.median(v), min(v), max(v))
         print(f"  {k:16s} n={len(v):3d} median {stat[k][0]:9.3f} min {stat[k][1]:9.3f} max {stat[k][2]:9.3f}")
-    print(f"  per env-step, last launch: {d['per_env_step']}")
-    for k in ("random", "descent"):
+    print(f"  per env-step, last launch (pibt at human weight {new['human_weight']}): {new['per_env_step']}")
+    for k in ("random", "descent") + (("pibt",) if "baseline pibt" in stat and args.human_weight == 0 else ()):
         bm, lo, hi = stat["baseline " + k]
         print(f"  (i)  {k} median {stat[k][0]:.3f} inside the baseline's [{lo:.3f}, {hi:.3f}]: "
               f"{'PASS' if lo <= stat[k][0] <= hi else 'FAIL'}")
+    if "per-step" not in stat:
+        return
     pm, plo, phi = stat["per-step"]
     print(f"  (ii) pibt median {stat['pibt'][0]:.3f} < per-step {pm:.3f} - spread {phi - plo:.3f} = {pm - (phi - plo):.3f}: "
           f"{'PASS' if stat['pibt'][0] < pm - (phi - plo) else 'FAIL'}")
