@@ -394,16 +394,23 @@ int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent);
  *      it neither status -1 nor -2: q inside the map and free, q != hn, and not (p_i == hn and
  *      q == h).  C_i = the admitted actions in ascending mapf_pibt_key(dist', a, t, i), where
  *      dist = D_i[q] and, with the handle's human weight w in 0..16 (mapf_set_pibt_human_weight; 0
- *      by default) and R = penalty_radius:
- *        d2 = |q - hn|^2 in cells;
+ *      by default), its human horizon K in 1..8 (mapf_set_pibt_human_horizon; 1 by default) and
+ *      R = penalty_radius:
+ *        the human's predicted cells, where it stands on path[s] of its current path of L cells:
+ *          P_1 = hn, whatever the path situation; P_j = path[s + j] for j = 2..K where
+ *          s + j <= L - 1 -- past the path's end there is no cell, and the path that follows is not
+ *          consulted (its search may still be running);
+ *        d2_j = |q - P_j|^2 in cells;
  *        level(R, d2) = 0 if d2 > constr_d2(R), else R - floor(sqrt(d2)), constr_d2(R) = the largest
- *          d2 with (R - sqrt(d2)) / R >= 0.01 in fp64 (24 for R = 5): level >= 1 exactly where an
- *          agent that ends the step on q is counted in `constraints` -- hn is the human's cell after
- *          the step --, one more per cell nearer the human, as the cost reward rises;
- *        dist' = dist if dist < 0 (unreachable stays 0x7FFF), else min(dist + w * level(R, d2), 0x7FFE).
+ *          d2 with (R - sqrt(d2)) / R >= 0.01 in fp64 (24 for R = 5): level(R, d2_1) >= 1 exactly where
+ *          an agent that ends the step on q is counted in `constraints` -- hn is the human's cell
+ *          after the step --, one more per cell nearer the human, as the cost reward rises; for
+ *          j >= 2 the same of the step j - 1 steps later, had the agent stayed on q;
+ *        dist' = dist if dist < 0 (unreachable stays 0x7FFF), else
+ *          min(dist + w * max_j level(R, d2_j), 0x7FFE), the maximum over the cells that exist.
  *      Staying (a = 0) is priced at the agent's own cell like any other target.  With w = 0,
- *      dist' = dist.  The weight only reorders the admitted actions: admission, the ages and the
- *      solve do not depend on it.
+ *      dist' = dist at any K; with K = 1 the price is that of hn alone.  Weight and horizon only
+ *      reorder the admitted actions: admission, the ages and the solve do not depend on them.
  *   3. Solve: next_i undecided for all agents; in the order (age descending, index ascending)
  *      every still undecided agent calls PIBT(i, none):
  *        PIBT(i, parent): for (a, q) in C_i:
@@ -434,6 +441,24 @@ int mapf_pibt_key(int32_t dist, int32_t action, uint32_t clock, int32_t agent);
 int mapf_set_pibt_human_weight(mapf_env *env, int32_t weight);
 /* The handle's human weight, or MAPF_EINVAL on a null env. */
 int mapf_get_pibt_human_weight(const mapf_env *env);
+/* The human horizon K of step 2: MAPF_EINVAL on a null env or k outside 1..8, and nothing changes
+ * then.  It has an effect only while the human weight is above 0.  No device call; in force from the
+ * next mapf_pibt_actions / mapf_rollout_pibt launch; a captured launch keeps the horizon of its
+ * capture.  Resets and mapf_set_state do not touch it. */
+int mapf_set_pibt_human_horizon(mapf_env *env, int32_t k);
+/* The handle's human horizon, or MAPF_EINVAL on a null env. */
+int mapf_get_pibt_human_horizon(const mapf_env *env);
+/* P_1..P_8 of step 2 for the current state of every env: cells DEVICE uint32 [B][8], packed as `pos`
+ * is (row | col << 16), 0xFFFFFFFF (NO_CELL) past the path's end -- all eight, whatever the handle's
+ * horizon, by the lookup the picks run: a wrong cell can be told from a wrong price.  MAPF_ESTATE
+ * before mapf_reset. */
+int mapf_pibt_human_cells(mapf_env *env, uint32_t *cells, void *stream);
+/* The word the kernels take weight, radius, constr_d2 and horizon in, on the host (the functions
+ * the kernels run): returns it (0 for weight 0) and, with fields != NULL, unpacks it into
+ * fields[4] = weight, radius, constr_d2, horizon.  With k = 1 the word is
+ * weight | radius << 8 | constr_d2 << 16.  -1 for weight outside 0..16, radius outside 1..64,
+ * constr_d2 outside 0..4095 or k outside 1..8. */
+int mapf_pibt_w_word(int32_t weight, int32_t penalty_radius, int32_t constr_d2, int32_t k, int32_t *fields);
 /* level(penalty_radius, d2) of step 2, on the host (the function the kernels run).  MAPF_EINVAL
  * for a radius outside 1..64 or d2 < 0. */
 int mapf_pibt_human_level(int32_t penalty_radius, int32_t d2);
@@ -460,7 +485,8 @@ int mapf_rollout_pibt(mapf_env *env, int32_t T, int32_t slots, int32_t *actions_
  * rollout_wide3_pibt_kernel<T,RW,ST> with the same leading template arguments (ST: 0 plain stores,
  * 1 nontemporal -- printed "false" / "true" --, 2 packed bits).  Kind 0:
  * "pibt_actions+step_observe", the per-step launches.  With a human weight w > 0 the text ends
- * with " human_weight=<w>" -- a run-time argument of the same kernels --; with w = 0 nothing is added. */
+ * with " human_weight=<w>" -- a run-time argument of the same kernels --, followed by
+ * " human_horizon=<K>" where K > 1; with w = 0 nothing is added. */
 int mapf_rollout_pibt_plan(const mapf_env *env, int32_t slots, char *buf, int32_t n);
 
 /* Copy agent.bfsMap for every agent: DEVICE int16 [B][N][H][W] (requires keep_bfs). */

@@ -75,6 +75,7 @@ struct mapf_env {
     // the PIBT policy's age arrays [B][N] (mapf.h: mapf_pibt_actions): the packed goal last seen and
     // the clock it was first seen at; policy-owned, no step kernel touches them
     uint32_t *pibt_seen = nullptr, *pibt_since = nullptr;
+    int pibt_horizon = 1;     // the PIBT policy's human horizon K (mapf_set_pibt_human_horizon); in d.pibt_w while the weight is above 0
     template <class T>
     int alloc(T *&p, size_t n) {
         void *q = nullptr;
@@ -358,7 +359,11 @@ int mapf_rollout_pibt_plan(const mapf_env *e, int32_t slots, char *buf, int32_t 
     const int kind = rollout_plan_impl(e, ROLLOUT_PIBT, slots, buf, n);
     if (kind >= 0 && e->d.pibt_w != 0) {    // the weight is a run-time value of the same kernel: a trailing word
         const size_t len = std::strlen(buf);
-        std::snprintf(buf + len, (size_t)n - len, " human_weight=%d", pibt_w_weight(e->d.pibt_w));
+        if (e->pibt_horizon > 1)
+            std::snprintf(buf + len, (size_t)n - len, " human_weight=%d human_horizon=%d", pibt_w_weight(e->d.pibt_w),
+                          e->pibt_horizon);
+        else
+            std::snprintf(buf + len, (size_t)n - len, " human_weight=%d", pibt_w_weight(e->d.pibt_w));
     }
     return kind;
 }
@@ -393,8 +398,38 @@ int mapf_set_pibt_human_weight(mapf_env *e, int32_t weight) {
     if (!e) return fail(MAPF_EINVAL, "null argument");
     if (weight < 0 || weight > 16) return fail(MAPF_EINVAL, "the PIBT human weight must be in 0..16");
     // a kernel argument of the next pick or rollout launch: no device call
-    e->d.pibt_w = pibt_w_pack((int)weight, e->d.R, e->d.constr_d2);
+    e->d.pibt_w = pibt_w_pack((int)weight, e->d.R, e->d.constr_d2, e->pibt_horizon);
     return MAPF_OK;
+}
+
+int mapf_set_pibt_human_horizon(mapf_env *e, int32_t k) {
+    if (!e) return fail(MAPF_EINVAL, "null argument");
+    if (k < 1 || k > PIBT_HORIZON_MAX) return fail(MAPF_EINVAL, "the PIBT human horizon must be in 1..8");
+    // kept on the handle (at weight 0 the kernels' word is 0 whatever the horizon) and in the word: no device call
+    e->pibt_horizon = (int)k;
+    e->d.pibt_w = pibt_w_pack(pibt_w_weight(e->d.pibt_w), e->d.R, e->d.constr_d2, e->pibt_horizon);
+    return MAPF_OK;
+}
+
+int mapf_get_pibt_human_horizon(const mapf_env *e) {
+    if (!e) return fail(MAPF_EINVAL, "null argument");
+    return e->pibt_horizon;
+}
+
+int mapf_pibt_w_word(int32_t weight, int32_t penalty_radius, int32_t constr_d2, int32_t k, int32_t *fields) {
+    if (weight < 0 || weight > 16 || penalty_radius < 1 || penalty_radius > 64 || constr_d2 < 0 || constr_d2 > 4095 ||
+        k < 1 || k > PIBT_HORIZON_MAX) {
+        fail(MAPF_EINVAL, "mapf_pibt_w_word: a field out of range");
+        return -1;
+    }
+    const int word = pibt_w_pack((int)weight, (int)penalty_radius, (int)constr_d2, (int)k);
+    if (fields) {
+        fields[0] = pibt_w_weight(word);
+        fields[1] = pibt_w_radius(word);
+        fields[2] = pibt_w_constr_d2(word);
+        fields[3] = pibt_w_horizon(word);
+    }
+    return word;
 }
 
 int mapf_get_pibt_human_weight(const mapf_env *e) {
@@ -1000,6 +1035,16 @@ int mapf_pibt_actions(mapf_env *e, int32_t *actions, void *stream) {
     HIPCHK(hipSetDevice(e->device));
     if (int rc = flush_search(e, (hipStream_t)stream)) return rc;      // the maps of the last step's new goals
     launch_pibt_actions(e->d, actions, e->pibt_seen, e->pibt_since, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+int mapf_pibt_human_cells(mapf_env *e, uint32_t *cells, void *stream) {
+    if (!e || !cells) return fail(MAPF_EINVAL, "null argument");
+    if (!e->ready) return fail(MAPF_ESTATE, "mapf_pibt_human_cells before mapf_reset");
+    HIPCHK(hipSetDevice(e->device));
+    // the current path only: the path that follows may still be searched beside the step (join_deferred)
+    launch_pibt_human_cells(e->d, cells, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return MAPF_OK;
 }

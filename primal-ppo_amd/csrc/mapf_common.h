@@ -239,11 +239,17 @@ __host__ __device__ inline int pibt_key(int dist, int action, uint32_t clock, in
     const int rank = action == 0 ? 0 : 1 + (int)(((uint32_t)(action - 1) - k0) & 3u);
     return cost * 8 + rank;
 }
-// DevEnv::pibt_w: weight 1..16 | R (1..64) << 8 | constr_d2 (0..4095) << 16; 0 for weight 0
-__host__ __device__ inline int pibt_w_pack(int w, int R, int constr_d2) { return w ? w | (R << 8) | (constr_d2 << 16) : 0; }
+// DevEnv::pibt_w: weight 1..16 | R (1..64) << 8 | constr_d2 (0..4095: at most 4,014 at R = 64) << 16 |
+// (human horizon K - 1, K in 1..8) << 28; 0 for weight 0, whatever the horizon.  At K = 1 the word is
+// the word of a build without the horizon.
+constexpr int PIBT_HORIZON_MAX = 8;
+__host__ __device__ inline int pibt_w_pack(int w, int R, int constr_d2, int K = 1) {
+    return w ? w | (R << 8) | (constr_d2 << 16) | ((K - 1) << 28) : 0;
+}
 __host__ __device__ inline int pibt_w_weight(int packed) { return packed & 0xFF; }
 __host__ __device__ inline int pibt_w_radius(int packed) { return (packed >> 8) & 0xFF; }
-__host__ __device__ inline int pibt_w_constr_d2(int packed) { return packed >> 16; }
+__host__ __device__ inline int pibt_w_constr_d2(int packed) { return (packed >> 16) & 0xFFF; }
+__host__ __device__ inline int pibt_w_horizon(int packed) { return ((packed >> 28) & 7) + 1; }
 // The human level of a target cell (include/mapf.h: mapf_pibt_actions step 2, mapf_pibt_human_level):
 // 0 where d2 = |q - hn|^2 > constr_d2 (the step's own `constraints` rule, DevEnv::constr_d2), else
 // R - floor(sqrt(d2)).  The root is taken in fp32 -- any estimate within 1 of the floor will do, so
@@ -267,6 +273,14 @@ __device__ inline uint32_t *human_path(const DevEnv &e, int b, int buf) {
 }
 // Human.getNextPos (mapf_gym.py:46-50), maintained in hnext[b] by the step kernel.
 __device__ inline uint32_t human_next(const DevEnv &e, int b) { return e.hnext[b]; }
+// The PIBT policy's human horizon (include/mapf.h: mapf_pibt_actions step 2): P_j for j >= 2, the cell
+// j steps ahead on the human's current path -- `path` its buffer (HBM, or a kernel's LDS copy), s the
+// step it stands on, L the path's length --, NO_CELL past the path's end.  P_1 is human_next().  The
+// one lookup every kernel and mapf_pibt_human_cells run.
+template <class P>
+__host__ __device__ inline uint32_t human_ahead(P path, int s, int L, int j) {
+    return s + j < L ? path[s + j] : NO_CELL;
+}
 
 
 // Wave-level helpers ---------------------------------------------------------

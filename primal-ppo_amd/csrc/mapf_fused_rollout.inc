@@ -140,7 +140,12 @@
                 if (head) {
                     age = pibt_age(pseen, psince, rs.gi, rs.clock);
                     const unsigned sm = E.smask[(E.shared_map ? 0 : (size_t)(b0 + le) * E.H * E.W) + prow(rs.pi) * E.W + pcol(rs.pi)];
-                    pibt_candidates(E, E.bfs + ai * bfs_cells(E.H, E.W), rs.pi, sm, rs.hp, rs.hn, rs.clock, i, cand);
+                    // the human's predicted cells past hn: uniform-address reads of the wave's LDS copy of
+                    // its current path (re-copied at a switch), made scalars for the loop's branch
+                    pibt_candidates(E, E.bfs + ai * bfs_cells(E.H, E.W), rs.pi, sm, rs.hp, rs.hn, rs.clock, i, cand, [&](int j) {
+                        return (uint32_t)__builtin_amdgcn_readfirstlane(
+                            (int)human_ahead(as_lds(rs.lp), rs.hs, rs.hcur ? rs.hlen1 : rs.hlen0, j));
+                    });
                 }
                 const int a = pibt_solve_wave<8>(E.N, lane, head ? rs.pi : NO_CELL, cand, age);
                 if (head) {

@@ -71,6 +71,7 @@ void launch_descent_actions(const DevEnv &e, int32_t *actions, hipStream_t s);
 // the PIBT policy's actions from the state, the tiled BFS maps and the handle's age arrays seen /
 // since [B][N], which it updates (keep_bfs; mapf_pibt_actions, mapf_pibt.hip): one wave per env
 void launch_pibt_actions(const DevEnv &e, int32_t *actions, uint32_t *seen, uint32_t *since, hipStream_t s);
+void launch_pibt_human_cells(const DevEnv &e, uint32_t *cells, hipStream_t s);
 // humans' next paths (replan_list[parity]) + agent BFS maps (bfs_list[parity]);
 // all = 1: every env's next path and every agent's map, 2: every env's next path,
 // 3 / 4: the step's human paths / BFS maps only

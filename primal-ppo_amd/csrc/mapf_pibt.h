@@ -30,10 +30,13 @@ __device__ inline void pibt_cx(uint32_t &a, uint32_t &b) {
 // Step 2: the lane's candidates c[0..4] in ascending key, each (key << 3) | action, PIBT_NONE for
 // the actions that are not admitted (they sort to the end).  D = the agent's tiled BFS map;
 // st_mask = the static-invalid mask of its cell (smask: off the map or an obstacle), hp / hn the
-// human's cell and next cell: the tests of step_group's getInvalidActions.  Five loads in flight,
-// one wait, as descent_action().
+// human's cell and next cell: the tests of step_group's getInvalidActions.  ahead(j), j in 2..K =
+// the human's predicted cell P_j as a wave-uniform scalar (human_ahead(): NO_CELL past the path's
+// end), from wherever the caller keeps the path; it is called only at a human horizon above 1.
+// Five loads in flight, one wait, as descent_action().
+template <class Ahead>
 __device__ inline void pibt_candidates(const DevEnv &e, const int16_t *D, uint32_t p, unsigned st_mask, uint32_t hp,
-                                       uint32_t hn, uint32_t clock, int agent, uint32_t c[NA]) {
+                                       uint32_t hn, uint32_t clock, int agent, uint32_t c[NA], Ahead ahead) {
     const int r = prow(p), col = pcol(p);
     int v[NA];
 #pragma unroll
@@ -42,19 +45,37 @@ __device__ inline void pibt_candidates(const DevEnv &e, const int16_t *D, uint32
         const bool in = in_map(e, rr, cc);
         v[k] = (int)D[bfs_at(e.W, in ? rr : r, in ? cc : col)];
     }
-    // The human weight (mapf.h, step 2): a reachable target costs pen = w * level(R, |q - hn|^2) more, up
-    // to 0x7FFE.  e.pibt_w (weight, R and constr_d2 in one word) is a kernel argument, so the branch is
-    // wave-uniform and weight 0 runs none of it; the block needs no loaded value, so it runs while the
-    // five map cells are in flight.
+    // The human weight (mapf.h, step 2): a reachable target costs pen = w * max_j level(R, |q - P_j|^2)
+    // more, up to 0x7FFE.  The level never rises with d2, so the highest level over the cells is the
+    // level of the smallest d2: the loop over j keeps five running minima of d2 (three VALU
+    // instructions per target and cell) and the level is taken once, after it.  e.pibt_w (weight, R,
+    // constr_d2 and the horizon in one word) is a kernel argument, so the branch and the loop are
+    // wave-uniform: weight 0 runs none of it, and horizon 1 runs the j = 1 round (P_1 = hn) alone, with
+    // no call of ahead().  None of it needs a loaded value, so it runs while the five map cells are in
+    // flight.  The cells are consecutive on one path, so the first NO_CELL ends the loop.
     int pen[NA] = {0, 0, 0, 0, 0};
     if (e.pibt_w != 0) {
         const int w = pibt_w_weight(e.pibt_w), R = pibt_w_radius(e.pibt_w), cd2 = pibt_w_constr_d2(e.pibt_w);
+        const int K = pibt_w_horizon(e.pibt_w);
+        int d2[NA];
         const int hr = prow(hn), hc = pcol(hn);
 #pragma unroll
         for (int k = 0; k < NA; ++k) {
             const int y = r + dr(k) - hr, x = col + dc(k) - hc;
-            pen[k] = w * pibt_human_level(R, cd2, y * y + x * x);
+            d2[k] = y * y + x * x;
         }
+        for (int j = 2; j <= K; ++j) {
+            const uint32_t pj = ahead(j);
+            if (pj == NO_CELL) break;
+            const int jr = prow(pj), jc = pcol(pj);
+#pragma unroll
+            for (int k = 0; k < NA; ++k) {
+                const int y = r + dr(k) - jr, x = col + dc(k) - jc;
+                d2[k] = min(d2[k], y * y + x * x);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NA; ++k) pen[k] = w * pibt_human_level(R, cd2, d2[k]);
     }
 #pragma unroll
     for (int k = 0; k < NA; ++k) {

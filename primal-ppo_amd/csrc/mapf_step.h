@@ -52,6 +52,8 @@ struct StepRegs {
     int hs, hcur, hl0, hl1;
     uint32_t hq;         // per lane q in 1..k_predict: human.path[q] after the step (NO_CELL past its end)
     uint32_t pseen, psince;   // per lane, PIBT launches only: the agent's age pair (loaded and stored by the caller)
+    uint32_t hf;         // per lane j in 2..K, PIBT launches at a human horizon K above 1 only: the human's
+                         // predicted cell P_j of the state the registers hold (human_ahead(); NO_CELL elsewhere)
 };
 
 __device__ inline void step_regs_load(const DevEnv &e, int b, int i, StepRegs &r) {
@@ -68,6 +70,10 @@ __device__ inline void step_regs_load(const DevEnv &e, int b, int i, StepRegs &r
     r.hl0 = e.hlen[b * 2];
     r.hl1 = e.hlen[b * 2 + 1];
     r.hq = NO_CELL;
+    // a launch's first pick; dead code in every kernel that is not a PIBT kernel (nothing reads hf there)
+    r.hf = NO_CELL;
+    if (pibt_w_horizon(e.pibt_w) > 1 && i >= 2 && i <= pibt_w_horizon(e.pibt_w))
+        r.hf = human_ahead(human_path(e, b, r.hcur), r.hs, r.hcur ? r.hl1 : r.hl0, i);
 }
 
 // The cells within distance 2 of an agent (the neighbour grid's 12 slots) and, per slot, the
@@ -205,6 +211,15 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
     // (only with the HP channel: an unused load still holds its register, and the next step's
     // reload of it would wait vmcnt behind every store issued meanwhile)
     if constexpr (REGS) rg.hq = (e.use_hp && e.C >= 6 && i >= 1 && i <= e.k_predict && i < hL2) ? hpath2[i] : NO_CELL;
+    // likewise the next pick's predicted cells P_2..P_K of the PIBT policy's human horizon, lane j
+    // taking P_j from the path the human is on after this step (after a swap: the new buffer);
+    // no load at horizon 1 or weight 0 (a scalar branch: e.pibt_w is a kernel argument)
+    uint32_t hf = NO_CELL;      // this step's pick takes the cells loaded a step ago
+    if constexpr (PIBT) {
+        hf = rg.hf;
+        if (pibt_w_horizon(e.pibt_w) > 1)
+            rg.hf = i >= 2 && i <= pibt_w_horizon(e.pibt_w) ? human_ahead(hpath2, hs2, hL2, i) : NO_CELL;
+    }
 
     // ---- state -----------------------------------------------------------
     const uint32_t pp = REGS ? rg.pp : (act ? e.pos[ai] : 0xFFFFFFFFu);
@@ -242,7 +257,7 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
             for (int k = 0; k < NA; ++k) w[k] = rows[(pr + dr(k) + e.P) * e.WW + ((pc + dc(k) + e.P) >> 5)];
 #pragma unroll
             for (int k = 0; k < NA; ++k) sm |= ((w[k] >> ((pc + dc(k) + e.P) & 31)) & 1u) << k;
-            pibt_candidates(e, e.bfs + ai * bfs_cells(e.H, e.W), pp, sm, rg.hp, rg.hn, clock, i, cand);
+            pibt_candidates(e, e.bfs + ai * bfs_cells(e.H, e.W), pp, sm, rg.hp, rg.hn, clock, i, cand, [&](int j) { return pibt_rl(hf, j); });
         }
         a = pibt_solve_wave(N, i, pp, cand, age);     // every lane: pp is NO_CELL past N
         if (act) actions[oi] = a;

@@ -109,6 +109,10 @@ SIGNATURES = {
     "mapf_set_pibt_human_weight": (ctypes.c_int, [P, I32]),
     "mapf_get_pibt_human_weight": (ctypes.c_int, [P]),
     "mapf_pibt_human_level": (ctypes.c_int, [I32, I32]),
+    "mapf_set_pibt_human_horizon": (ctypes.c_int, [P, I32]),
+    "mapf_get_pibt_human_horizon": (ctypes.c_int, [P]),
+    "mapf_pibt_human_cells": (ctypes.c_int, [P, P, P]),
+    "mapf_pibt_w_word": (ctypes.c_int, [I32, I32, I32, I32, P]),
     "mapf_flush": (ctypes.c_int, [P, P]),
     "mapf_release_captures": (ctypes.c_int, [P]),
     "mapf_random_actions": (ctypes.c_int, [P, P, P]),

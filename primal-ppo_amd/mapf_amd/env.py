@@ -582,6 +582,36 @@ class BatchedMapfGym:
         _lib.check(min(w, 0))
         return w
 
+    def set_pibt_human_horizon(self, k):
+        """The PIBT policy's human horizon K, an int in 1..8 (mapf_set_pibt_human_horizon; mapf.h has the
+        rule): a target is priced against the human's next K predicted cells -- its next cell and the
+        K - 1 that follow on its current path -- by the highest level among them.  1, the default,
+        prices the next cell alone.  It has an effect only at a human weight above 0.  Takes effect at
+        the next pibt_actions / rollout(T, "pibt"); a captured launch keeps the horizon it was captured
+        with.  Resets leave it alone."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"human horizon: expected an int in 1..8, got {type(k).__name__}")
+        if not 1 <= int(k) <= 8:
+            raise ValueError(f"human horizon must be in 1..8, got {int(k)}")
+        _lib.check(_lib.lib().mapf_set_pibt_human_horizon(self.h, int(k)))
+
+    @property
+    def pibt_human_horizon(self):
+        """The PIBT policy's human horizon (mapf_get_pibt_human_horizon)."""
+        k = _lib.lib().mapf_get_pibt_human_horizon(self.h)
+        _lib.check(min(k, 0))
+        return k
+
+    def pibt_human_cells(self, out=None):
+        """The human's predicted cells P_1..P_8 of the current state (mapf_pibt_human_cells), whatever
+        the horizon: int32 [B, 8], each row | col << 16 as the state's cells are packed, -1 past the
+        end of the human's current path."""
+        if out is None:
+            out = torch.empty((self.B, 8), dtype=torch.int32, device=self.device)
+        _check(out, torch.int32, self.B * 8, self.device, "cells")
+        _lib.check(_lib.lib().mapf_pibt_human_cells(self.h, _ptr(out), _stream(self.device)))
+        return out
+
     def random_actions(self, out=None):
         out = self.actions if out is None else out
         _check(out, torch.int32, self.B * self.N, self.device, "actions")

@@ -192,19 +192,23 @@ def descent_policy():
     return _bfs_policy("descent_actions", "descent_policy")
 
 
-def pibt_policy(human_weight=None):
+def pibt_policy(human_weight=None, human_horizon=None):
     """The PIBT planner: one collision-free step for all agents from their BFS maps
-    (env.pibt_actions, mapf_pibt_actions).  human_weight: None leaves the env's setting alone; an int
-    in 0..16 is set on the env the policy is called with (env.set_pibt_human_weight)."""
+    (env.pibt_actions, mapf_pibt_actions).  human_weight / human_horizon: None leaves the env's setting
+    alone; an int in 0..16 / 1..8 is set on the env the policy is called with
+    (env.set_pibt_human_weight / env.set_pibt_human_horizon)."""
     pick = _bfs_policy("pibt_actions", "pibt_policy")
-    if human_weight is None:
+    if human_weight is None and human_horizon is None:
         return pick
 
-    done = []                           # the env the weight was last set on: one library call per env, not per step
+    done = []                           # the env the settings were last made on: one library call per env, not per step
 
     def policy(obs, vec, env, t):
         if not done or done[0] is not env:
-            env.set_pibt_human_weight(human_weight)
+            if human_weight is not None:
+                env.set_pibt_human_weight(human_weight)
+            if human_horizon is not None:
+                env.set_pibt_human_horizon(human_horizon)
             done[:] = [env]
         return pick(obs, vec, env, t)
     return policy

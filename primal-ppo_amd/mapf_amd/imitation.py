@@ -23,20 +23,25 @@ class DemoRunner:
     """env: a BatchedMapfGym ("pibt" and "descent" need keep_bfs).  policy: "pibt", "descent" or "tape"
     (run(tape=...) then takes the int32 [T, B, N] actions to play); "random" is no expert and raises.
     human_weight (policy="pibt" only, ValueError otherwise): the planner's human weight, set on the env once
-    here (env.set_pibt_human_weight); None leaves the env's setting alone.
+    here (env.set_pibt_human_weight); None leaves the env's setting alone.  human_horizon: likewise the
+    planner's human horizon (env.set_pibt_human_horizon).
     new_maps, seed: as DeviceRunner.  obs_bits: keep the observations packed (`obs_bits` int32
     [T + 1, B, N, WPA]; the default) or as floats (`obs` [T + 1, B, N, C, F, F]).
     Exposes T, env, packed, obs / obs_bits, vec and expert_actions (int32 [T, B, N]): a source of
     Model.imitate_rows and DeviceTrainer.imitate."""
 
     def __init__(self, env: BatchedMapfGym, n_steps=None, policy="pibt", new_maps=None, obs_bits=True, seed=0,
-                 human_weight=None):
+                 human_weight=None, human_horizon=None):
         if policy not in ("pibt", "descent", "tape"):
             raise ValueError(f"DemoRunner: policy must be 'pibt', 'descent' or 'tape' (an expert), got {policy!r}")
+        if human_weight is not None and policy != "pibt":
+            raise ValueError(f"human_weight belongs to policy='pibt', not {policy!r}")
+        if human_horizon is not None and policy != "pibt":
+            raise ValueError(f"human_horizon belongs to policy='pibt', not {policy!r}")
         if human_weight is not None:
-            if policy != "pibt":
-                raise ValueError(f"human_weight belongs to policy='pibt', not {policy!r}")
             env.set_pibt_human_weight(human_weight)
+        if human_horizon is not None:
+            env.set_pibt_human_horizon(human_horizon)
         self.env, self.policy = env, policy
         self.T = TrainingParameters.N_STEPS if n_steps is None else int(n_steps)
         if self.T < 1:

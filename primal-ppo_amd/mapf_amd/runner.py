@@ -319,18 +319,23 @@ class DeviceRunner:
     DeviceTrainer.imitate read next to obs[:T] / vec[:T].  Needs an env built with keep_bfs.  None
     (the default): no labels, no launch, no buffer.
     expert_human_weight (expert="pibt" only, ValueError otherwise): the planner's human weight, set on
-    the env once here (env.set_pibt_human_weight); None leaves the env's setting alone."""
+    the env once here (env.set_pibt_human_weight); None leaves the env's setting alone.
+    expert_human_horizon: likewise the planner's human horizon (env.set_pibt_human_horizon)."""
 
     def __init__(self, env: BatchedMapfGym, model, n_steps=None, seed=0, new_maps=None, obs_bits=False, expert=None,
-                 expert_human_weight=None):
+                 expert_human_weight=None, expert_human_horizon=None):
         if expert not in (None, "pibt", "descent"):
             raise ValueError(f"expert: expected None, 'pibt' or 'descent', got {expert!r}")
         if expert is not None and not env.cfg.keep_bfs:
             raise ValueError(f"expert={expert!r} reads the agents' BFS maps: build the env with keep_bfs=True")
+        if expert_human_weight is not None and expert != "pibt":
+            raise ValueError(f"expert_human_weight belongs to expert='pibt', not {expert!r}")
+        if expert_human_horizon is not None and expert != "pibt":
+            raise ValueError(f"expert_human_horizon belongs to expert='pibt', not {expert!r}")
         if expert_human_weight is not None:
-            if expert != "pibt":
-                raise ValueError(f"expert_human_weight belongs to expert='pibt', not {expert!r}")
             env.set_pibt_human_weight(expert_human_weight)
+        if expert_human_horizon is not None:
+            env.set_pibt_human_horizon(expert_human_horizon)
         self.expert = expert
         self.env = env
         self.model = model

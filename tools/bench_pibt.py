@@ -5,6 +5,7 @@ one GPU.
   python tools/bench_pibt.py --config c2                       # this build: random / descent / pibt / per-step
   python tools/bench_pibt.py --config c2 --baseline-lib primal-ppo_amd/lib/libmapf_parent.so --rounds 3
   python tools/bench_pibt.py --config c4 --human-weight 2 --skip-per-step      # the planner at human weight 2
+  python tools/bench_pibt.py --config c4 --human-weight 2 --human-horizon 3 --skip-per-step      # ... pricing 3 cells ahead
 
 Each measurement process builds the preset's env (bench.py's presets and maps), prepares one launcher
 per policy over the same [T]-slot buffers (T = 256, c5: 87), every policy on a handle of its own (so
@@ -12,14 +13,16 @@ each plays its own episode from the same reset), runs one untimed round, then `-
 rounds random / descent / pibt, each launch between two HIP events, and then `--pairs` per-step
 series: PIBT as T x (pibt_actions, step_observe) calls in place, between two HIP events over the whole
 series (--skip-per-step leaves it out).  --human-weight W sets the PIBT handle's human weight
-(mapf_set_pibt_human_weight; 0, the default, is the plain policy) before its launches.  From the last
+(mapf_set_pibt_human_weight; 0, the default, is the plain policy) and --human-horizon K its human horizon
+(mapf_set_pibt_human_horizon; 1, the default, prices the human's next cell alone) before its launches.  From the last
 timed launch of descent and of PIBT, per env-step: goals reached, agents with status -3 and -2, actions
 fixActions rewrote (actions_fixed != actions), agents counted in `constraints`, and the mean cost reward
 per agent-step.  With --baseline-lib the driver (which never opens the GPU) starts fresh child processes
 in turn, baseline / this build, `--rounds` times: a baseline library runs the policies it has -- a build
 from before the PIBT entry points its random and descent policies only, one from before the human weight
-its PIBT policy at weight 0 whatever W is.  The verdicts printed at the end:
-  (i)   this build's random, descent and (at weight 0, where the baseline has it) pibt medians lie inside
+its PIBT policy at weight 0 whatever W is, one from before the human horizon at horizon 1 whatever K is.  The
+verdicts printed at the end:
+  (i)   this build's random, descent and (at weight 0 or horizon 1, where the baseline has it) pibt medians lie inside
         the baseline's own min..max spreads;
   (ii)  the one-launch PIBT median is below the per-step median by more than the per-step series' own
         min..max spread.
@@ -36,6 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "primal-ppo_amd")]
 PIBT_FNS = ("mapf_rollout_pibt", "mapf_rollout_pibt_plan", "mapf_pibt_actions", "mapf_pibt_key", "mapf_pibt_host")
 HUMAN_FNS = ("mapf_set_pibt_human_weight", "mapf_get_pibt_human_weight", "mapf_pibt_human_level")
+HORIZON_FNS = ("mapf_set_pibt_human_horizon", "mapf_get_pibt_human_horizon", "mapf_pibt_human_cells", "mapf_pibt_w_word")
 
 
 def measure(args):
@@ -53,6 +57,10 @@ def measure(args):
             _lib.SIGNATURES.pop(n)
     if not has_weight:                    # a build from before the human weight: the plain policy
         for n in HUMAN_FNS:
+            _lib.SIGNATURES.pop(n)
+    has_horizon = has_weight and all(hasattr(ctypes.CDLL(_lib.LIB_PATH), n) for n in HORIZON_FNS)
+    if not has_horizon:                   # a build from before the human horizon: the next cell alone
+        for n in HORIZON_FNS:
             _lib.SIGNATURES.pop(n)
     from mapf_amd.config import make_config
     from mapf_amd.env import BatchedMapfGym
@@ -83,6 +91,8 @@ def measure(args):
         envs["pibt"] = penv = make_env()
         if has_weight:
             penv.set_pibt_human_weight(args.human_weight)
+        if has_horizon:
+            penv.set_pibt_human_horizon(args.human_horizon)
         launch["pibt"] = penv.rollout_launcher(T, policy="pibt", **kw)
         plan["pibt"] = penv.rollout_pibt_plan(slots, slots)
         out0 = {k: v[0] for k, v in out.items()}
@@ -121,7 +131,8 @@ def measure(args):
     c = sum(e.counters() for e in envs.values())
     print(json.dumps({"config": args.config, "envs": B, "buffers": "slots" if slots else "in place",
                       "lib": os.path.basename(_lib.LIB_PATH), "T": T,
-                      "human_weight": args.human_weight if has_weight else 0, "us_per_step": times, "plan": plan,
+                      "human_weight": args.human_weight if has_weight else 0,
+                      "human_horizon": args.human_horizon if has_horizon else 1, "us_per_step": times, "plan": plan,
                       "per_env_step": quality, "counters": [int(x) for x in c[:8]]}), flush=True)
 
 
@@ -135,6 +146,7 @@ def main():
     ap.add_argument("--lib", default=None, help="library to measure (default: the package's)")
     ap.add_argument("--baseline-lib", default=None, help="a baseline build to alternate with (the policies it has)")
     ap.add_argument("--human-weight", type=int, default=0, help="the PIBT policy's human weight, 0..16 (default 0: off)")
+    ap.add_argument("--human-horizon", type=int, default=1, help="the PIBT policy's human horizon, 1..8 (default 1: the next cell alone)")
     ap.add_argument("--skip-per-step", action="store_true", help="leave out the per-step PIBT series")
     ap.add_argument("--inplace", action="store_true", help="the [B]-leading buffers instead of [T]-slot buffers")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -148,7 +160,7 @@ def main():
         for which, lib in (("baseline", args.baseline_lib), ("new", args.lib)):
             cmd = [sys.executable, os.path.abspath(__file__), "--child", "--config", args.config, "--T", str(args.T),
                    "--pairs", str(args.pairs)] + (["--lib", lib] if lib else []) + (["--inplace"] if args.inplace else []) + ["--envs", str(args.envs)] + \
-                ["--human-weight", str(args.human_weight)] + (["--skip-per-step"] if args.skip_per_step else [])
+                ["--human-weight", str(args.human_weight), "--human-horizon", str(args.human_horizon)] + (["--skip-per-step"] if args.skip_per_step else [])
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             if res.returncode != 0:
                 sys.stderr.write(res.stderr[-3000:])
@@ -167,8 +179,11 @@ def main():
             continue
         stat[k] = (statistics.median(v), min(v), max(v))
         print(f"  {k:16s} n={len(v):3d} median {stat[k][0]:9.3f} min {stat[k][1]:9.3f} max {stat[k][2]:9.3f}")
-    print(f"  per env-step, last launch (pibt at human weight {new['human_weight']}): {new['per_env_step']}")
-    for k in ("random", "descent") + (("pibt",) if "baseline pibt" in stat and args.human_weight == 0 else ()):
+    print(f"  per env-step, last launch (pibt at human weight {new['human_weight']}, horizon {new['human_horizon']}): "
+          f"{new['per_env_step']}")
+    # the baseline plays the same policy: weight 0, or its own weight W at horizon 1 (a baseline with the weight)
+    same_policy = args.human_weight == 0 or args.human_horizon == 1
+    for k in ("random", "descent") + (("pibt",) if "baseline pibt" in stat and same_policy else ()):
         bm, lo, hi = stat["baseline " + k]
         print(f"  (i)  {k} median {stat[k][0]:.3f} inside the baseline's [{lo:.3f}, {hi:.3f}]: "
               f"{'PASS' if lo <= stat[k][0] <= hi else 'FAIL'}")
