@@ -241,6 +241,32 @@ int mapf_rollout_random_fused(const mapf_env *env);
  * address: pass the address of the very slot and env asked about, obs + ((t * B + b) * N*C*F*F) * 4.
  * Returns the float4s per env, or a negative error. */
 int mapf_obs_band_skip(const mapf_config *cfg, int32_t unit, uint64_t byte_offset, uint8_t *skip, int32_t n);
+/* Sparse slot-buffer rollouts: store only the observation pieces that change.  The policy's rollout
+ * (policy 0 random, 1 the caller's tape in `actions`, 2 descent, 3 pibt; as mapf_rollout_random /
+ * _actions / _descent / _pibt with slots = MAPF_SLOTS) over rollout buffers that are used again and
+ * again.  Every observation float is 0.0 or 1.0 and most are 0.0; a piece is 16 consecutive floats
+ * (64 bytes) of an env's [N][C][F][F] slice in one slot.
+ *   shadow  DEVICE uint32 [T][B][16], 64-byte aligned, the caller's: bit p of an env-slot's 16 words
+ *           is 1 iff piece p of that env in that slot holds a non-zero float.
+ *   valid   the promise, as MAPF_SLOTS_BAND_CLEAN's: for every slot t < valid the shadow says what
+ *           `obs` holds now (typically: an earlier mapf_rollout_sparse wrote these slots with this
+ *           shadow and nothing else has written `obs` or the shadow since).  0 promises nothing.
+ * For t < valid the launch stores exactly the pieces that the shadow names or that hold a non-zero
+ * now; for t >= valid it stores every float.  Either way it writes the slot's new shadow, and `obs`,
+ * like every other output, ends byte for byte as after a mapf_rollout_random with MAPF_SLOTS -- as
+ * long as the promise holds.  Whoever writes `obs` in between (another library, a raw pointer) passes
+ * valid = 0 next time.  The library keeps no record of buffers.
+ * The form takes effect in the pair-lane kernel where an env's slice is a whole number of pieces and
+ * `obs` is 64-byte aligned (mapf_obs_sparse_applies: N = 8 with an even channel count).  Elsewhere the
+ * shadow is neither read nor written and the launch is the MAPF_SLOTS one, with MAPF_SLOTS_BAND_CLEAN
+ * if valid >= T.  mapf_rollout_sparse_plan: the launch's form as text, as mapf_rollout_plan; the sparse
+ * form reads e.g. "rollout_random_kernel<true,4,sparse64>". */
+int mapf_rollout_sparse(mapf_env *env, int32_t policy, int32_t T, int32_t *actions, const mapf_step_out *out,
+                        float *obs, float *vec, uint32_t *shadow, int32_t valid, void *stream);
+int mapf_rollout_sparse_plan(const mapf_env *env, int32_t policy, const float *obs, char *buf, int32_t n);
+/* Host only: 1 if the sparse form applies to this configuration with `obs` at this address, else 0
+ * (negative on error). */
+int mapf_obs_sparse_applies(const mapf_config *cfg, uint64_t obs_address);
 /* The pacing gate of the grouped pair-lane kernel (roll_group with roll_slack >= 0), computed on the
  * host (no device call) by the function the kernel runs.  The `live` waves of a workgroup (1..64, those
  * that own an env) share a ring of 16 counters; a wave that has finished step t adds 1 to counter
@@ -269,7 +295,7 @@ typedef struct mapf_tuning {
     /* pair-lane rollout (mapf_rollout_random_fused == 1: N in 5..8, shared map) */
     int32_t roll_occ;        /* workgroups per CU the LDS request admits: 0 = ceil(grid / CUs), 1..16      */
     int32_t roll_group;      /* the 16 waves of a CU in one workgroup: -1 auto (slots, or roll_fair > 0), 0, 1 */
-    int32_t roll_fair;       /* grouped, issue priority by progress: -1 auto (4 in place, 0 slots), 0 off, n */
+    int32_t roll_fair;       /* grouped, issue priority by progress: -1 auto (4 in place and sparse, 0 slots), 0 off, n */
     int32_t roll_slack;      /* grouped, roll_fair 0: waves paced within n steps of the slowest (< 0 off;
                                 more than 14 paces as 14: mapf_pace_gate)                                 */
     /* one-wave-per-env rollout (mapf_rollout_random_fused == 2: up to 64 agents, per-env maps, C = 7) */

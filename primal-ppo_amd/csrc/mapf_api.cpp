@@ -940,8 +940,10 @@ static mapf_step_out step_out_slot(const mapf_step_out &out, size_t k, const Dev
 
 // mapf_rollout_random / _actions / _descent / _pibt (`name`, for the error text).  policy (ROLLOUT_*) says
 // where the actions come from; `actions` is the caller's tape with ROLLOUT_TAPE (read only), else out.
+// shadow / valid: mapf_rollout_sparse's (NULL: every other entry point)
 static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, int32_t slots, int32_t *actions,
-                        const mapf_step_out *out, float *obs, float *vec, void *stream) {
+                        const mapf_step_out *out, float *obs, float *vec, void *stream, uint32_t *shadow = nullptr,
+                        int32_t valid = 0) {
     if (!e || !actions || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
     if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
     if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN | MAPF_SLOTS_OBS_BITS)) return fail(MAPF_EINVAL, "slots: unknown bits");
@@ -966,7 +968,7 @@ static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, in
         // LDS included); they store everything (MAPF_SLOTS_BAND_CLEAN ignored)
         const StepOut o = step_out_of(out);
         int rc = launch_rollout_random(e->d, T, actions, o, obs, vec, slots, e->tune, e->args, s, policy, e->pibt_seen,
-                                       e->pibt_since);
+                                       e->pibt_since, shadow, valid);
         if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
             rc = launch_rollout_wide(e->d, T, actions, o, obs, vec, slots & (MAPF_SLOTS | MAPF_SLOTS_OBS_BITS), e->tune,
                                      e->args, s, policy, e->pibt_seen, e->pibt_since);
@@ -1052,6 +1054,36 @@ int mapf_pibt_human_cells(mapf_env *e, uint32_t *cells, void *stream) {
 int mapf_rollout_pibt(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
                       float *obs, float *vec, void *stream) {
     return rollout_impl(e, ROLLOUT_PIBT, "mapf_rollout_pibt", T, slots, actions_out, out, obs, vec, stream);
+}
+
+int mapf_rollout_sparse(mapf_env *e, int32_t policy, int32_t T, int32_t *actions, const mapf_step_out *out, float *obs,
+                        float *vec, uint32_t *shadow, int32_t valid, void *stream) {
+    if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
+    if (!shadow) return fail(MAPF_EINVAL, "null argument");
+    if (valid < 0) return fail(MAPF_EINVAL, "valid must be >= 0");
+    if ((uintptr_t)shadow & 63) return fail(MAPF_EINVAL, "shadow must be 64-byte aligned");
+    // where the sparse form does not take the launch it is the band-clean one: the band's pieces are
+    // zeros over zeros in every slot the shadow describes, but only there
+    const int32_t slots = MAPF_SLOTS | (valid >= T ? MAPF_SLOTS_BAND_CLEAN : 0);
+    return rollout_impl(e, policy, "mapf_rollout_sparse", T, slots, actions, out, obs, vec, stream, shadow, valid);
+}
+
+int mapf_rollout_sparse_plan(const mapf_env *e, int32_t policy, const float *obs, char *buf, int32_t n) {
+    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
+    if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
+    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
+    if (rollout_random_fusable(e->d) &&
+        describe_rollout_random(e->d, MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN, e->tune, buf, (size_t)n, policy, true, obs))
+        return 1;
+    return rollout_plan_impl(e, policy, MAPF_SLOTS, buf, n);
+}
+
+int mapf_obs_sparse_applies(const mapf_config *cfg, uint64_t obs_address) {
+    if (!cfg) return fail(MAPF_EINVAL, "null argument");
+    if (cfg->num_agents < 1 || cfg->num_agents > 64 || cfg->fov < 1 || cfg->fov > 16 || cfg->num_channel < 5 ||
+        cfg->num_channel > 7)
+        return fail(MAPF_EINVAL, "num_agents, fov or num_channel out of range");
+    return obs_sparse_applies(cfg->num_agents, cfg->num_channel, cfg->fov, (size_t)obs_address) ? 1 : 0;
 }
 
 int mapf_release_captures(mapf_env *e) {

@@ -165,6 +165,28 @@ struct RolloutArgsPibt {
     DevEnv e;
     RolloutOutPibt ro;
 };
+// Sparse launches (mapf_rollout_sparse): the same with the caller's shadow, uint32 [slots][B][16], and the
+// number of leading slots it describes.  Types and a kernel of their own again (rollout_sparse_kernel):
+// every other kernel keeps its arguments and its code.
+struct RolloutOutSparse : RolloutOut {
+    uint32_t *shadow;
+    int valid;
+};
+struct RolloutOutPibtSparse : RolloutOutPibt {
+    uint32_t *shadow;
+    int valid;
+};
+template <class RO>
+struct RolloutArgsOf {
+    DevEnv e;
+    RO ro;
+};
+__device__ inline uint32_t *ro_shadow(const RolloutOut &) { return nullptr; }
+__device__ inline uint32_t *ro_shadow(const RolloutOutSparse &r) { return r.shadow; }
+__device__ inline uint32_t *ro_shadow(const RolloutOutPibtSparse &r) { return r.shadow; }
+__device__ inline int ro_valid(const RolloutOut &) { return 0; }
+__device__ inline int ro_valid(const RolloutOutSparse &r) { return r.valid; }
+__device__ inline int ro_valid(const RolloutOutPibtSparse &r) { return r.valid; }
 
 __host__ __device__ inline bool rollout_fusable(const DevEnv &e) {
     return e.G == 8 && e.human_mode != 2 && e.goal_mode == 1 && e.C < 7 && !e.force_agent_lanes && fused_per_wave(e) &&
@@ -190,8 +212,11 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy)
 // never with BAND.
 // SUBS 4-env quarters per workgroup: SUBS = 4 puts all 16 waves of a CU in one workgroup, so
 // each can see how far the others are (pacing, below)
-// BAND: a slot-buffer launch with MAPF_SLOTS_BAND_CLEAN -- the wave leaves out the stores that lie
-// wholly inside its env's zero band (obs_band_skip; the band of every slot already holds zeros)
+// BAND (0, OBS_BAND, OBS_SPARSE): OBS_BAND, a slot-buffer launch with MAPF_SLOTS_BAND_CLEAN -- the wave leaves
+// out the stores that lie wholly inside its env's zero band (obs_band_skip; the band of every slot
+// already holds zeros).  OBS_SPARSE (rollout_sparse_kernel, mapf_rollout_sparse): the wave leaves out
+// every 64-B piece that held zeros by the caller's shadow and holds zeros again, and writes the
+// shadow of what the slot holds now (mapf_observe.h); the band's pieces are always among those.
 // TAPE: the caller's actions (mapf_rollout_actions) instead of the Philox draw.  Step t plays row
 // [t][b] of ro.actions, [T][B][N] whatever `slots` says.  A vector load in the loop is waited
 // for behind the wave's own observation stores (vmcnt counts both, in order) at every step:
@@ -209,7 +234,7 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy)
 // pair stays in registers across the steps and is written back after the last (RO = RolloutOutPibt).
 // The loop is one text, mapf_fused_rollout.inc, included into both kernels below: as a device function
 // called from them the other policies' kernels compiled to other code (the band form with scratch).
-template <int ST, int SUBS, bool BAND, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
+template <int ST, int SUBS, int BAND, int POL>      // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_kernel(
 #if MAPF_ARGS_PTR      // experiment build: arguments through a device pointer (mapf_rollout_wide.hip)
     const RolloutArgs *__restrict__ args, int T) {
@@ -223,7 +248,7 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
 }
 // the PIBT form: the same loop, a kernel of its own because its arguments differ (RolloutOutPibt);
 // the plan text names it by the form it shares, rollout_random_kernel<..,pibt>
-template <int ST, int SUBS, bool BAND>
+template <int ST, int SUBS, int BAND>
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_pibt_kernel(
 #if MAPF_ARGS_PTR
     const RolloutArgsPibt *__restrict__ args, int T) {
@@ -236,7 +261,21 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
     using RO = RolloutOutPibt;
 #include "mapf_fused_rollout.inc"
 }
-template <int ST, int SUBS, bool BAND, int POL>
+// the sparse form: the same loop for all four policies (RO is a dependent type here), slot buffers only
+template <int SUBS, int POL>
+__global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_sparse_kernel(
+#if MAPF_ARGS_PTR
+    const RolloutArgsOf<std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse>> *__restrict__ args, int T) {
+    const DevEnv &e = args->e;
+    const auto &ro = args->ro;
+#else
+    DevEnv e, int T, std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse> ro) {
+#endif
+    using RO = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse>;
+    constexpr int ST = OBS_NT, BAND = OBS_SPARSE;
+#include "mapf_fused_rollout.inc"
+}
+template <int ST, int SUBS, int BAND, int POL>
 constexpr auto rollout_kernel_fn() {
     if constexpr (POL == ROLLOUT_PIBT) return &rollout_random_pibt_kernel<ST, SUBS, BAND>;
     else return &rollout_random_kernel<ST, SUBS, BAND, POL>;
@@ -255,7 +294,8 @@ struct RolloutPlan {
 
 // policy ROLLOUT_TAPE / ROLLOUT_DESCENT / ROLLOUT_PIBT: the caller's-actions, descent and PIBT forms (their LDS rows; past
 // 64 KiB the wide kernel takes over)
-static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p, int policy) {
+static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p, int policy,
+                                bool sparse = false) {
     if (!rollout_random_fusable(e) || rollout_lds_bytes(e, policy) > 64 * 1024) return false;
     const int grid = (e.B + 3) / 4;
     // Persistent waves: every CU should hold the same number of workgroups, or the
@@ -278,7 +318,10 @@ static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &t
     // rest run at 2 -- no wave ever idles, and the youngest wave of a SIMD no longer trails
     // (13.9-14.0 -> 11.9-12.0 us per step; roll_fair 0 with roll_group 0: four workgroups, unpaced).
     const size_t sub = (rollout_lds_bytes(e, policy) + 15) & ~(size_t)15;
-    const int fair = tu.roll_fair >= 0 ? tu.roll_fair : (slots ? 0 : 4);
+    // Sparse launches into slots: with two thirds of the stores gone the store drain no longer sets the
+    // pace, pacing's waits cost more than they save and priority by progress wins as it does in place
+    // (2.41e9 against 2.01-2.03e9 agent-steps/s paced, 2.12e9 unpaced, 2.07e9 ungrouped).
+    const int fair = tu.roll_fair >= 0 ? tu.roll_fair : (slots && !sparse ? 0 : 4);
     const bool want_group = occ == 4 && grid % 4 == 0 && (tu.roll_group < 0 ? slots != 0 || fair > 0 : tu.roll_group != 0);
     const bool group = want_group && 4 * sub + 64 <= (size_t)device_max_group_lds();
     p.tape_ungrouped = policy != ROLLOUT_RANDOM && want_group && !group &&
@@ -299,17 +342,27 @@ static bool rollout_band_form(const DevEnv &e, int slots) {
     return (slots & MAPF_SLOTS_BAND_CLEAN) && (slots & 1) && obs_zero_band(e, z0, z1) && obs_band_iters(e) <= 32;
 }
 
-bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy) {
+// mapf_rollout_sparse takes effect: slot buffers of floats whose env slices are whole 64-B pieces
+// (obs_sparse_applies); elsewhere the launch is the band-clean one
+static bool rollout_sparse_form(const DevEnv &e, int slots, const float *obs) {
+    return (slots & MAPF_SLOTS) && !(slots & MAPF_SLOTS_OBS_BITS) && obs_sparse_applies(e.N, e.C, e.F, (size_t)(uintptr_t)obs);
+}
+
+bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy,
+                             bool sparse, const float *obs) {
     const bool bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
-    const bool band = !bits && rollout_band_form(e, slots);      // packed zeros cost nothing to write
+    sparse = sparse && rollout_sparse_form(e, slots, obs);
+    if (!sparse && obs) slots |= MAPF_SLOTS_BAND_CLEAN;          // a sparse call where the form does not apply
+    const bool band = !bits && !sparse && rollout_band_form(e, slots);      // packed zeros cost nothing to write
     slots &= 1;
     RolloutPlan p;
-    if (!plan_rollout_random(e, slots, tu, p, policy)) {
+    if (!plan_rollout_random(e, slots, tu, p, policy, sparse)) {
         std::snprintf(buf, n, "none");
         return false;
     }
     char band_tag[16] = "";
     if (band) std::snprintf(band_tag, sizeof band_tag, ",band%d", MAPF_BAND_UNIT);
+    if (sparse) std::snprintf(band_tag, sizeof band_tag, ",sparse%d", OBS_SPARSE_PIECE * 4);
     if (bits) std::snprintf(band_tag, sizeof band_tag, ",bits");
     const int k = std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
                                 slots ? "true" : "false", p.subs, band_tag, rollout_policy_tag(policy), p.grid, 256 * p.subs,
@@ -327,12 +380,13 @@ bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, 
 // slots: the MAPF_SLOTS_* bits of mapf_rollout_random
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
                           int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy,
-                          uint32_t *pibt_seen, uint32_t *pibt_since) {
+                          uint32_t *pibt_seen, uint32_t *pibt_since, uint32_t *shadow, int valid) {
     const bool bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
-    const bool band = !bits && rollout_band_form(e, slots) && ((uintptr_t)obs & 15) == 0;     // whole float4s
+    const bool sparse = shadow && rollout_sparse_form(e, slots, obs);
+    const bool band = !bits && !sparse && rollout_band_form(e, slots) && ((uintptr_t)obs & 15) == 0;     // whole float4s
     slots &= 1;
     RolloutPlan p;
-    if (!plan_rollout_random(e, slots, tu, p, policy)) return ROLLOUT_NOT_COVERED;
+    if (!plan_rollout_random(e, slots, tu, p, policy, sparse)) return ROLLOUT_NOT_COVERED;
     const RolloutOut ro0{actions, out, obs, vec, slots, p.remap, p.sub_lds, p.slack, p.fair};
     (void)ring;
     return with_policy(policy, [&](auto pol) -> int {
@@ -356,6 +410,23 @@ int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOu
 #endif
             return MAPF_OK;
         };
+        if (sparse) {
+            using ROS = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse>;
+            ROS rs{};
+            static_cast<RO &>(rs) = ro;
+            rs.shadow = shadow;
+            rs.valid = valid;
+            const dim3 gd(p.grid), bd(256 * p.subs);
+            auto kern = p.subs == 4 ? &rollout_sparse_kernel<4, POL> : &rollout_sparse_kernel<1, POL>;
+#if MAPF_ARGS_PTR
+            const RolloutArgsOf<ROS> *args = push_args(ring, RolloutArgsOf<ROS>{e, rs}, s);
+            if (!args) return MAPF_ESTATE;
+            hipLaunchKernelGGL(kern, gd, bd, p.lds, s, args, T);
+#else
+            hipLaunchKernelGGL(kern, gd, bd, p.lds, s, e, T, rs);
+#endif
+            return MAPF_OK;
+        }
         if (bits)      // one instantiation for slots and in place (ro.slots is a run-time field)
             return p.subs == 4 ? launch(rollout_kernel_fn<OBS_BITS, 4, false, POL>()) : launch(rollout_kernel_fn<OBS_BITS, 1, false, POL>());
         if (band)

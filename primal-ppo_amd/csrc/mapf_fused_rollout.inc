@@ -1,5 +1,5 @@
 // primal-ppo_amd/csrc/mapf_fused_rollout.inc -- the body of the pair-lane rollout kernels
-// (mapf_fused.hip: rollout_random_kernel, rollout_random_pibt_kernel), included into each.  In scope:
+// (mapf_fused.hip: rollout_random_kernel, rollout_random_pibt_kernel, rollout_sparse_kernel), included into each.  In scope:
 // the template arguments ST, SUBS, BAND, the policy POL, the arguments e, T, ro and RO, the argument type of the policy's kernel (a dependent name
 // in rollout_random_kernel, so that the PIBT branches' members are looked up only where they exist).
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -59,7 +59,7 @@
     // B = 37) the set moves with t and the loop computes it again for each slot.
     uint32_t band_mask = 0;
     bool band_moves = false;
-    if constexpr (BAND) {
+    if constexpr (BAND == OBS_BAND) {
         band_moves = ((size_t)e.B * e.N * e.C * e.F * e.F * 4) % MAPF_BAND_UNIT != 0;
         if (le < nenv && !band_moves)
             band_mask = obs_band_skip_mask(e, MAPF_BAND_UNIT, (size_t)(ro.obs + (size_t)(b0 + le) * e.N * e.C * e.F * e.F),
@@ -84,6 +84,16 @@
         }
         const size_t BN = (size_t)E.B * E.N;
         const size_t s = R.slots ? (size_t)t : 0;
+        // SPARSE: the env-slot's 16 mask words.  Steps below `valid` read them here, at the top of the
+        // step, by scalar loads (obs_sparse_old), and obs_emit stores the pieces that were or become
+        // non-zero; later steps store every piece.  The address is uniform: the wave's env, the step.
+        [[maybe_unused]] uint32_t *sp_words = nullptr;
+        if constexpr (BAND == OBS_SPARSE) {
+            const int lew = __builtin_amdgcn_readfirstlane(le);
+            sp_words = ro_shadow(ro) + (s * (size_t)E.B + (size_t)(b0 + lew)) * OBS_SPARSE_WORDS;
+            band_mask = 0xFFFFFFFFu;
+            if (t < ro_valid(ro) && lew < nenv) band_mask = obs_sparse_old(sp_words, (int)(threadIdx.x & 63));
+        }
         if constexpr (TAPE) {
             if ((t & (TAPE_K - 1)) == 0) {
                 if (le < nenv) {        // rows [t, t + TAPE_K) of this env, inside [T][B][N]
@@ -173,7 +183,7 @@
             blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
         if (le < nenv) {
             const ObsGroup g = obs_wave_init(E, L, le, mreg);
-            if (BAND && band_moves)
+            if (BAND == OBS_BAND && band_moves)
                 band_mask = obs_band_skip_mask(E, MAPF_BAND_UNIT,
                                                (size_t)(R.obs + (s * BN + (size_t)(b0 + le) * E.N) * E.C * E.F * E.F),
                                                (int)(threadIdx.x & 63));
@@ -182,6 +192,9 @@
             if constexpr (ST == OBS_BITS) ob = R.obs + s * BN * (size_t)obs_bits_words(E.C, E.F);
             else ob = R.obs + s * BN * E.C * E.F * E.F;
             obs_emit<false, ST, BAND>(E, L, ob, R.vec + s * BN * 4, g, b0, false, band_mask);
+            // SPARSE: what the slot holds now, for the next launch over it (the stream is whole until the
+            // next step's obs_wave_init); ordinary vector stores of lanes 0, 4, .., 60
+            if constexpr (BAND == OBS_SPARSE) obs_sparse_store(g.stream, L.swe, sp_words, (int)(threadIdx.x & 63));
             step_pairs_search_inline(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs);
             if (pacing) pace_arrive(prog, t);
             else if (fair) publish_count(prog + gw, (uint32_t)(t + 1));

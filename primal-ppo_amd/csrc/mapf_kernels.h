@@ -123,6 +123,9 @@ void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, 
 //     rollout_wide3_pibt_kernel.
 // describe_rollout_random returns false (text "none") where the pair-lane kernel does not take the
 // launch -- with a tape or descent that includes a fusable configuration whose LDS rows do not fit.
+// shadow / valid (mapf_rollout_sparse): the caller's piece masks, uint32 [slots][B][16], and the leading
+// slots they describe; the pair-lane kernel's sparse form where rollout_sparse_form, else the launch
+// is the MAPF_SLOTS_BAND_CLEAN one (the caller ors the bit in); the plan's text carries ",sparse64".
 constexpr int ROLLOUT_NOT_COVERED = 1;
 constexpr int ROLLOUT_RANDOM = 0, ROLLOUT_TAPE = 1, ROLLOUT_DESCENT = 2, ROLLOUT_PIBT = 3;
 // f(std::integral_constant<int, policy>{}): the runtime policy as a template argument
@@ -142,8 +145,9 @@ inline const char *rollout_policy_tag(int policy) {
 bool rollout_random_fusable(const DevEnv &e);
 int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
                            int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy,
-                           uint32_t *pibt_seen, uint32_t *pibt_since);
-bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy);
+                           uint32_t *pibt_seen, uint32_t *pibt_since, uint32_t *shadow = nullptr, int valid = 0);
+bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy,
+                             bool sparse = false, const float *obs = nullptr);
 // the same for up to 64 agents / per-env maps / the BFS channel: one wave per env
 // (mapf_rollout_wide.hip); used where the pair-lane rollout does not apply.  Returns MAPF_OK or
 // MAPF_ESTATE (a captured launch found no free argument slot, ArgRing).

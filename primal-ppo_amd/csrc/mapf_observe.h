@@ -233,6 +233,48 @@ __device__ inline void obs_zero_band_store(const DevEnv &e, float *__restrict__ 
     }
 }
 
+// ---- the sparse form of a slot-buffer rollout (obs_emit<.., OBS_SPARSE>; mapf.h: mapf_rollout_sparse) ----
+// A piece is 16 consecutive floats (64 B) of an env's [N][C][F][F] slice; the caller's shadow holds
+// one bit per piece of every env-slot, uint32 [slots][B][16]: bit p of the 16 words is 1 iff piece p
+// holds a non-zero float.  A step whose slot the shadow describes stores exactly the pieces that were
+// or become non-zero; the others hold zeros and stay.  The band's pieces are among those.
+constexpr int OBS_BAND = 1, OBS_SPARSE = 2;        // obs_emit's BAND argument (0: every float stored)
+constexpr int OBS_SPARSE_WORDS = 16, OBS_SPARSE_PIECE = 16;   // words per env-slot, floats per piece
+// The form applies where an env's slice is a whole number of pieces that the 16 words can name and
+// every slice starts on a 64-B line (holes finer than 64 B cost more than they save: DESIGN.md 9d).
+__host__ __device__ inline bool obs_sparse_applies(int N, int C, int F, size_t obs_addr) {
+    const int fl = N * C * F * F;
+    return fl > 0 && fl % OBS_SPARSE_PIECE == 0 && fl / OBS_SPARSE_PIECE <= 32 * OBS_SPARSE_WORDS && (obs_addr & 63) == 0;
+}
+// The lane's share of an env-slot's old mask.  Lane l stores float4 l + 64k at iteration k: piece
+// (l >> 2) + 16k, which is bit (k & 1) * 16 + (l >> 2) of word k >> 1.  Returned: bit j = iteration 2j,
+// bit 16 + j = iteration 2j + 1.  `words` is wave-uniform and nothing in this launch has written it:
+// read through the constant address space, the 16 words come by scalar loads, which wait on lgkmcnt
+// and not, as a vector load would, behind the previous step's observation stores (vmcnt).
+__device__ inline uint32_t obs_sparse_old(const uint32_t *words, int lane) {
+    typedef const __attribute__((address_space(4))) uint32_t cu32;
+    cu32 *w = (cu32 *)(uintptr_t)words;
+    const int g = lane >> 2;
+    uint32_t a = 0;
+#pragma unroll
+    for (int j = 0; j < OBS_SPARSE_WORDS; ++j) a |= ((w[j] >> g) & 0x10001u) << j;
+    return a;
+}
+// The env-slot's new mask out of the wave's finished bit-stream (piece p = half-word p): lane l
+// folds stream words [4l, 4l + 4) into 8 bits, four lanes make a word, lanes 0, 4, .. store the 16.
+__device__ inline void obs_sparse_store(const uint32_t *stream, int swe, uint32_t *words, int lane) {
+    uint32_t b = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = 4 * lane + i;
+        const uint32_t w = idx < swe ? stream[idx] : 0u;
+        b |= (((w & 0xFFFFu) ? 1u : 0u) | ((w >> 16) ? 2u : 0u)) << (2 * i);
+    }
+    b |= (uint32_t)__shfl_down((int)b, 1) << 8;
+    b |= (uint32_t)__shfl_down((int)b, 2) << 16;
+    if ((lane & 3) == 0) words[lane >> 2] = b;
+}
+
 // Phases 1-4.  Every thread of the workgroup calls it after a __syncthreads()
 // that follows obs_init and the agents' staging.  skip_band: the zero band's
 // whole float4s were written by obs_zero_band_store in this launch.
@@ -240,7 +282,9 @@ __device__ inline void obs_zero_band_store(const DevEnv &e, float *__restrict__ 
 // has it: step_observe_fusable).  ST (OBS_*): OBS_NT, the table-driven store loop (L.lut) uses
 // nontemporal stores; OBS_BITS, phase 4 writes the packed words instead of floats (`obs` is then
 // the uint32 buffer; skip_band and band_mask are ignored: nothing else writes a packed buffer).  BAND: the one-wave table loop skips the stores of `band_mask`
-// (bit k = this lane's iteration k, obs_band_skip_mask); BAND = false compiles the test out.
+// (bit k = this lane's iteration k, obs_band_skip_mask); BAND = 0 compiles the test out; BAND = OBS_SPARSE:
+// `band_mask` is obs_sparse_old's word (all ones: store everything) and the loop stores the pieces that
+// were non-zero by it or are non-zero now.
 // The threads that observe a run of the workgroup's envs together: the whole
 // workgroup (workgroup barriers) or one wave observing its own env (per_env
 // layout; wave-level ordering only).
@@ -282,7 +326,7 @@ __device__ inline ObsGroup obs_wave_init(const DevEnv &e, const ObsLds &L, int l
     return g;
 }
 
-template <bool BFSCH = true, int ST = OBS_PLAIN, bool BAND = false>
+template <bool BFSCH = true, int ST = OBS_PLAIN, int BAND = 0>
 __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restrict__ obs, float *__restrict__ vec,
                                 const ObsGroup &G, int b0, bool skip_band = false, uint32_t band_mask = 0) {
     using namespace obsd;
@@ -475,11 +519,18 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
         const int sh = (tid & 7) * 4;
         const uint32_t *swp = stream + (tid >> 3);
         float4 *dp = reinterpret_cast<float4 *>(dst) + tid;
+        [[maybe_unused]] int it = 0;          // OBS_SPARSE: the iteration
 #pragma unroll 4
         for (int rem = ((K * CFF) >> 2) - tid; rem > 0; rem -= 64) {
-            const float4 f = L.lut[__builtin_amdgcn_ubfe(*swp, sh, 4)];
-            if (BAND && (band_mask & 1u)) {
-                // inside the clean zero band: nothing to store
+            const uint32_t sw = *swp;
+            const float4 f = L.lut[__builtin_amdgcn_ubfe(sw, sh, 4)];
+            bool skip = false;
+            if constexpr (BAND == OBS_BAND) skip = band_mask & 1u;
+            // the piece's 16 bits are the lane's half of the word; its old bit: obs_sparse_old's layout
+            if constexpr (BAND == OBS_SPARSE)
+                skip = (__builtin_amdgcn_ubfe(sw, (tid & 4) * 4, 16) | __builtin_amdgcn_ubfe(band_mask, (it & 1) * 16 + (it >> 1), 1)) == 0;
+            if (skip) {
+                // inside the clean zero band, or a piece of zeros over zeros: nothing to store
             } else if constexpr (ST == OBS_NT) {   // streaming stores (rollout slot buffers: not re-read by this launch)
                 typedef float v4f __attribute__((ext_vector_type(4)));
 #if defined(MAPF_SLOT_STORE) && MAPF_SLOT_STORE == 1     // store-policy experiment: nt only (round 2's)
@@ -509,7 +560,8 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
                 *dp = f;
 #endif
             }
-            if constexpr (BAND) band_mask >>= 1;
+            if constexpr (BAND == OBS_BAND) band_mask >>= 1;
+            if constexpr (BAND == OBS_SPARSE) ++it;
             swp += 8;
             dp += 64;
         }

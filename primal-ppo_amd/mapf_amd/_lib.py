@@ -89,6 +89,9 @@ SIGNATURES = {
     "mapf_rollout_random": (ctypes.c_int, [P, I32, I32, P, ctypes.POINTER(StepOut), P, P, P]),
     "mapf_rollout_random_fused": (ctypes.c_int, [P]),
     "mapf_obs_band_skip": (ctypes.c_int, [ctypes.POINTER(MapfConfig), I32, ctypes.c_uint64, P, I32]),
+    "mapf_rollout_sparse": (ctypes.c_int, [P, I32, I32, P, ctypes.POINTER(StepOut), P, P, P, I32, P]),
+    "mapf_rollout_sparse_plan": (ctypes.c_int, [P, I32, P, ctypes.c_char_p, I32]),
+    "mapf_obs_sparse_applies": (ctypes.c_int, [ctypes.POINTER(MapfConfig), ctypes.c_uint64]),
     "mapf_pace_gate": (ctypes.c_int, [I32, I32, I32, P, P]),
     "mapf_observe_lds": (I64, [ctypes.POINTER(MapfConfig), I32, I32, P]),
     "mapf_tuning_default": (None,[ctypes.POINTER(Tuning)]),

@@ -5,6 +5,7 @@ the current torch HIP stream; inputs and outputs are torch tensors in HBM.
 Reference API it batches: mapf_gym.MapfGym / FixedMapfGym (mapf_gym.py:163-669).
 """
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -59,6 +60,45 @@ def _policy_symbols(policy):
     if policy not in ROLLOUT_POLICIES:
         raise ValueError(f"policy: expected one of {sorted(ROLLOUT_POLICIES)}, got {policy!r}")
     return ROLLOUT_POLICIES[policy]
+
+
+# mapf_rollout_sparse's policy argument (include/mapf.h)
+SPARSE_POLICY = {"random": 0, "tape": 1, "descent": 2, "pibt": 3}
+
+
+def sparse_applies(N, C, F, address):
+    """mapf_obs_sparse_applies (include/mapf.h) without the call: an env's observation slice is a whole
+    number of 64-byte pieces that 16 mask words can name, and the buffer is 64-byte aligned."""
+    floats = N * C * F * F
+    return floats > 0 and floats % 16 == 0 and floats // 16 <= 512 and address % 64 == 0
+
+
+class _SparseEntry:
+    """What the sparse launchers over one observation buffer share (rollout_launcher): the shadow
+    masks int32 [slots][B][16] of mapf_rollout_sparse, the number of leading slots they describe,
+    and obs._version as it was after the last launch (torch counts its own in-place writes there,
+    for every view of the buffer; a launch through the raw pointer does not count)."""
+    __slots__ = ("shadow", "valid", "version", "geometry", "__weakref__")
+
+    def __init__(self, shadow, version, geometry):
+        self.shadow, self.valid, self.version, self.geometry = shadow, 0, version, geometry
+
+
+# (device, base address of the obs tensor's storage) -> _SparseEntry, alive as long as a launcher holds it
+# (each launcher also holds its buffers, so the address is not handed out again under a live entry)
+_SPARSE = weakref.WeakValueDictionary()
+
+
+def _sparse_key(obs):
+    return (str(obs.device), obs.untyped_storage().data_ptr())
+
+
+def _sparse_forget(obs):
+    """Another rollout call writes `obs`: a registered buffer's shadow no longer describes it."""
+    if _SPARSE and isinstance(obs, torch.Tensor):
+        entry = _SPARSE.get(_sparse_key(obs))
+        if entry is not None:
+            entry.valid = 0
 
 
 class BatchedMapfGym:
@@ -411,6 +451,7 @@ class BatchedMapfGym:
                                                            tape=tape, obs_bits=obs_bits)
         if T == 0 and policy != "random":   # nothing to play (an empty tensor has no address to hand over)
             return out, obs, vec
+        _sparse_forget(obs)
         _lib.check(getattr(_lib.lib(), symbol)(self.h, int(T), self._slot_bits(slots, band_clean, obs_bits), _ptr(actions),
                                                ctypes.byref(so), _ptr(obs), _ptr(vec), _stream(self.device)))
         return out, obs, vec
@@ -428,6 +469,7 @@ class BatchedMapfGym:
                 fast = self._roll_fast = (key, _lib.lib().mapf_rollout_random, self.h, ctypes.byref(self._stepout),
                                           _ptr(self.actions), _ptr(self.obs), _ptr(self.vec))
             _, fn, h, so, pa, po, pv = fast
+            _sparse_forget(self.obs)
             _lib.check(fn(h, int(T), 0, pa, so, po, pv, _stream(self.device)))
             return self.out, self.obs, self.vec
         return self.rollout(T, "random", slots=slots, actions=actions, obs=obs, vec=vec, out=out, band_clean=band_clean,
@@ -485,8 +527,55 @@ class BatchedMapfGym:
         return self.rollout(T, "pibt", slots=slots, actions=actions, obs=obs, vec=vec, out=out, band_clean=band_clean,
                             obs_bits=obs_bits)
 
+    def rollout_sparse(self, T, policy="random", *, shadow, valid, actions=None, tape=None, obs, vec, out):
+        """mapf_rollout_sparse (mapf.h): rollout(T, policy, slots=True, ...) that stores only the 64-byte
+        observation pieces that change.  shadow: int32 [T, B, 16] on the device, the caller's piece masks
+        of `obs`; valid: the leading slots for which the caller vouches that they describe what `obs`
+        holds now (0: none).  The launch leaves the slots' new masks in `shadow`.  rollout_launcher does
+        this bookkeeping by itself.  Returns (out, obs, vec)."""
+        _policy_symbols(policy)
+        T = self._check_tape(tape) if policy == "tape" else int(T)
+        actions, so, out, obs, vec = self._rollout_buffers(T, True, obs, vec, out, actions=actions,
+                                                           tape=tape if policy == "tape" else None)
+        _check(shadow, torch.int32, T * self.B * 16, self.device, "shadow")
+        if T == 0:
+            return out, obs, vec
+        _sparse_forget(obs)
+        _lib.check(_lib.lib().mapf_rollout_sparse(self.h, SPARSE_POLICY[policy], T, _ptr(actions), ctypes.byref(so),
+                                                  _ptr(obs), _ptr(vec), _ptr(shadow), int(valid), _stream(self.device)))
+        return out, obs, vec
+
+    def rollout_sparse_plan(self, obs, policy="random"):
+        """The form a mapf_rollout_sparse launch into `obs` takes, as text (mapf_rollout_sparse_plan):
+        "rollout_random_kernel<true,4,sparse64> ..." where the sparse form applies, else the band form's."""
+        _policy_symbols(policy)
+        buf = ctypes.create_string_buffer(512)
+        kind = _lib.lib().mapf_rollout_sparse_plan(self.h, SPARSE_POLICY[policy], _ptr(obs), buf, 512)
+        if kind < 0:
+            _lib.check(kind)
+        return buf.value.decode()
+
+    def _sparse_entry(self, T, obs):
+        """The shared entry of a sparse launcher over `obs` (created on first use), or None where the
+        sparse form does not apply or the registry cannot express the view: it must start at its
+        storage's first byte, so that its slot t is the buffer's slot t, with this env's geometry."""
+        if getattr(self, "rollout_kernel", 0) != 1 or not sparse_applies(self.N, self.C, self.F, obs.data_ptr()):
+            return None
+        storage = obs.untyped_storage()
+        if obs.data_ptr() != storage.data_ptr():
+            return None
+        geometry = (self.B, self.N, self.C, self.F)
+        entry = _SPARSE.get(_sparse_key(obs))
+        if entry is not None:
+            return entry if entry.geometry == geometry else None
+        slot_bytes = self.B * self.N * self.C * self.F * self.F * 4
+        slots = max(int(T), storage.nbytes() // slot_bytes)
+        entry = _SparseEntry(torch.zeros(slots, self.B, 16, dtype=torch.int32, device=obs.device), obs._version, geometry)
+        _SPARSE[_sparse_key(obs)] = entry
+        return entry
+
     def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None, actions_in=None,
-                         policy="random", obs_bits=False):
+                         policy="random", obs_bits=False, sparse=True):
         """rollout(T, policy, slots=slots, ...) prepared once: the buffers are checked and the C call's
         arguments built now, on the current stream; the returned callable issues the launch with
         no per-call host work beyond one ctypes call (a 20-step rollout is ~350 us on the GPU, the
@@ -498,6 +587,18 @@ class BatchedMapfGym:
         (MAPF_SLOTS_BAND_CLEAN, mapf.h).  The contract: between calls of one launcher nobody writes
         non-zeros into that band of `obs`.  Whoever does (or hands the memory to something that
         may) calls launch.invalidate(): the next call stores everything again.
+
+        sparse (the default, with slots and float observations): where the pair-lane kernel runs and an
+        env's observation slice is whole 64-byte pieces (N = 8 with an even channel count: c2), the
+        launcher goes further (mapf_rollout_sparse, mapf.h).  It keeps one bit per piece of every slot
+        on the device, shared by all launchers over the same buffer (views included, e.g. obs[:n]), and
+        a call stores only the pieces that held a non-zero after the previous call or hold one now;
+        the buffer ends byte for byte as if everything had been stored.  The launcher notices writes
+        made through torch (obs._version, shared by all views): the call after one uses the band form
+        above and the next stores everything again.  Any other rollout call of this module into the
+        buffer does the same.  The widened contract: whoever writes `obs` behind torch's back between
+        calls (raw pointers, another library) calls launch.invalidate().  sparse=False keeps the band
+        form alone.  A view that does not start at its storage's first byte gets the band form.
 
         actions_in: an int32 [T, B, N] tape -- the launcher then issues the "tape" policy over it (`actions`
         is not used); its contents are read at launch time: refill the tensor to play other actions.
@@ -523,15 +624,39 @@ class BatchedMapfGym:
         keep = (so, actions, obs, vec, out)
         state = [args]                  # the next call's arguments: `clean` once a call has stored the band
 
-        def launch():
-            _lib.check(fn(*state[0]))
+        entry = self._sparse_entry(T, obs) if sparse and slots and not obs_bits else None
+        if entry is None:
+            def launch():
+                _lib.check(fn(*state[0]))
+                state[0] = clean
+                return keep[4], keep[2], keep[3]
+
+            def invalidate():
+                state[0] = args
+            launch.invalidate = invalidate
+            return launch
+
+        fn_sparse = _lib.lib().mapf_rollout_sparse
+        head = (self.h, SPARSE_POLICY[policy], int(T), args[3], args[4], args[5], args[6], _ptr(entry.shadow))
+        stream, n = args[7], int(T)
+
+        def launch_sparse():
+            if obs._version != entry.version:       # torch wrote the buffer: the shadow says nothing now
+                entry.valid = 0
+                _lib.check(fn(*state[0]))
+            else:
+                _lib.check(fn_sparse(*head, entry.valid, stream))
+                entry.valid = max(entry.valid, n)
+            entry.version = obs._version
             state[0] = clean
             return keep[4], keep[2], keep[3]
 
-        def invalidate():
+        def invalidate_sparse():
             state[0] = args
-        launch.invalidate = invalidate
-        return launch
+            entry.valid = 0
+        launch_sparse.invalidate = invalidate_sparse
+        launch_sparse.sparse = entry
+        return launch_sparse
 
     def _check_out(self, out):
         for k, t in out.items():

@@ -20,6 +20,9 @@
 // "aligned": odd envs (slice base % 128 = 64) use lane l -> float4 l - 4 + 64k instead, lanes whose
 // index falls outside [0, 1452) off, so that every instruction of every env starts on a 128-B line
 // (same bytes, same 64-B pieces, same 23 instructions; fewer lines touched per instruction).
+// "scatter p": every 64-B piece of a slice is left out independently with probability p (seeded; 256
+// hole sets, wave w uses set w % 256), same lane mapping and predication: what a store of only the
+// pieces that changed would cost.  Comparable with the band form ("skip 64-B units") of the same run.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,15 +61,15 @@ __device__ inline void store4(v4f *p, v4f v) {
     else *p = v;
 }
 
-// masks: [2][64] per-lane skip bits (bit k = float4 lane + 64k) by env parity, or null (full);
+// masks: [nvar][64] per-lane skip bits (bit k = float4 lane + 64k), set w % nvar (nvar = 2: by env parity), or null (full);
 // cidx: [COMPACT_ITERS][64] float4 indices of the compacted form, or null
 // aligned: odd envs shift their lane mapping down by 4 float4s (the masks are then built for that mapping)
 template <bool NT>
 __global__ __launch_bounds__(1024) void slice_stores(float *buf, int steps, size_t step_floats, const uint32_t *masks,
-                                                     const int *cidx, int aligned) {
+                                                     const int *cidx, int aligned, int nvar) {
     const int w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int lane = (int)(threadIdx.x & 63) - (aligned ? 4 * (w & 1) : 0);
-    const uint32_t mask = masks ? masks[(w & 1) * 64 + (threadIdx.x & 63)] : 0u;      // env offset % 128 = 64 * (w & 1)
+    const uint32_t mask = masks ? masks[(w % nvar) * 64 + (threadIdx.x & 63)] : 0u;   // env offset % 128 = 64 * (w & 1)
     int idx[COMPACT_ITERS];
 #pragma unroll
     for (int k = 0; k < COMPACT_ITERS; ++k) idx[k] = cidx ? cidx[k * 64 + (threadIdx.x & 63)] : 0;
@@ -128,16 +131,33 @@ static int slice_mode(int steps, int reps) {
         if (!skip_q(16, 0, q)) hc.push_back(q);
     if ((int)hc.size() != COMPACT_ITERS * 64) return 1;
     hipMemcpy(dmask, hm.data(), hm.size() * 4, hipMemcpyHostToDevice);
+    // scattered holes: piece p = float4s [4p, 4p + 4), lane l holds float4 l + 64k at bit k
+    constexpr int NPROB = 3, NVAR = 256, PIECES = ENV_Q / 4;
+    const double probs[NPROB] = {0.55, 0.68, 0.80};
+    double sc_skipped[NPROB] = {0, 0, 0};
+    uint32_t *dscat = nullptr;
+    if (hipMalloc(&dscat, NPROB * NVAR * 64 * 4) != hipSuccess) return 1;
+    std::vector<uint32_t> hs(NPROB * NVAR * 64, 0u);
+    uint64_t rng = 0x9E3779B97F4A7C15ull;
+    for (int i = 0; i < NPROB; ++i)
+        for (int v = 0; v < NVAR; ++v)
+            for (int p = 0; p < PIECES; ++p) {
+                rng = rng * 6364136223846793005ull + 1442695040888963407ull;
+                if ((double)(rng >> 11) * (1.0 / 9007199254740992.0) >= probs[i]) continue;
+                for (int q = 4 * p; q < 4 * p + 4; ++q) hs[(i * NVAR + v) * 64 + (q & 63)] |= 1u << (q >> 6);
+                sc_skipped[i] += 64.0 / NVAR;
+            }
+    hipMemcpy(dscat, hs.data(), hs.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(dcidx, hc.data(), hc.size() * 4, hipMemcpyHostToDevice);
     hipEvent_t a, b;
     hipEventCreate(&a);
     hipEventCreate(&b);
-    auto run = [&](const char *name, bool nt, const uint32_t *masks, const int *cidx, double bytes_env, int aligned = 0) {
+    auto run = [&](const char *name, bool nt, const uint32_t *masks, const int *cidx, double bytes_env, int aligned = 0, int nvar = 2) {
         std::vector<float> us;
         for (int r = 0; r <= reps; ++r) {
             hipEventRecord(a);
-            if (nt) hipLaunchKernelGGL(slice_stores<true>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx, aligned);
-            else hipLaunchKernelGGL(slice_stores<false>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx, aligned);
+            if (nt) hipLaunchKernelGGL(slice_stores<true>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx, aligned, nvar);
+            else hipLaunchKernelGGL(slice_stores<false>, dim3(waves / wpg), dim3(64 * wpg), 0, 0, buf, steps, step_floats, masks, cidx, aligned, nvar);
             hipEventRecord(b);
             hipEventSynchronize(b);
             float ms;
@@ -161,10 +181,17 @@ static int slice_mode(int steps, int reps) {
         run("skip 64-B, aligned", nt, dmask + 3 * 2 * 64, nullptr, ENV_BYTES - skipped[1], 1);
         run("skip 64-B units (again)", nt, dmask + 1 * 2 * 64, nullptr, ENV_BYTES - skipped[1]);
         run("full (again)", nt, nullptr, nullptr, ENV_BYTES);
+        for (int i = 0; i < NPROB; ++i) {
+            char name[32];
+            snprintf(name, sizeof name, "scatter %.2f, 64-B", probs[i]);
+            run(name, nt, dscat + i * NVAR * 64, nullptr, ENV_BYTES - sc_skipped[i], 0, NVAR);
+        }
+        run("skip 64-B units (3rd)", nt, dmask + 1 * 2 * 64, nullptr, ENV_BYTES - skipped[1]);
     }
     hipFree(buf);
     hipFree(dmask);
     hipFree(dcidx);
+    hipFree(dscat);
     return 0;
 }
 
