@@ -290,7 +290,13 @@ int64_t mapf_observe_lds(const mapf_config *cfg, int32_t obs_envs, int32_t max_l
  * only pick between forms that produce identical results.  mapf_create sets the defaults
  * (mapf_tuning_default); nothing is read from the process environment.  A field at its
  * default means "the measured choice for this configuration", which may depend on B, N, the
- * map size, slots and the device (CU count, LDS size, the kernels' VGPR counts). */
+ * map size, slots and the device (CU count, LDS size, the kernels' VGPR counts).
+ * mapf_rollout_perf's kernels store nothing per step, so the fields that manage store drains do not
+ * apply to them: they honour roll_occ (pair-lane: the LDS request per workgroup), wide_grid (0: the
+ * agent loop) and xcd_remap, and ignore roll_group, roll_fair, roll_slack and every other wide_* field
+ * (always one wave per env, one env per workgroup, the neighbour grid sharing the search's LDS area,
+ * no pacing, no priority).  Their LDS holds the map rows, the search scratch, the path copies and the
+ * policy's rows only. */
 typedef struct mapf_tuning {
     /* pair-lane rollout (mapf_rollout_random_fused == 1: N in 5..8, shared map) */
     int32_t roll_occ;        /* workgroups per CU the LDS request admits: 0 = ceil(grid / CUs), 1..16      */
@@ -588,6 +594,58 @@ int mapf_normalize_advantages_stats_dlam(const float *ret, const float *v, const
  * rollout's rewards, goal reward included, or cost rewards); out DEVICE float [B] = the float32
  * sum over t, in order, of numpy's float32 np.sum of x[t][b][0..N-1] (pairwise order; N <= 128). */
 int mapf_episode_sum(const float *x, int32_t T, int32_t B, int32_t N, float *out, void *stream);
+
+/* OneEpPerformance of one env (util.py; runner.py:64-99, evaluate.py:237-265): the eight numbers a
+ * planner comparison reads, in episodes.METRIC_KEYS' order.  The float sums are the reference's own
+ * arithmetic: per step numpy's pairwise float32 np.sum over the env's N values (sequential below 8
+ * values; else 8 strided accumulators combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the remainder in
+ * order, then 0 + res), then acc = acc + step in float32 -- no contraction, no reassociation. */
+typedef struct mapf_perf {            /* 32 bytes                                                */
+    float   episode_reward;           /* sum_t np.sum(reward_total[t][b][:])  float32, in order   */
+    float   episode_cost_reward;      /* sum_t np.sum(cost[t][b][:])          float32, in order   */
+    int32_t human_collide;            /* status == -2                                            */
+    int32_t static_collide;           /* status == -1                                            */
+    int32_t agent_collide;            /* status == -3                                            */
+    int32_t total_goals;              /* goals_reached == 1                                      */
+    int32_t shadow_goals;             /* sum of shadow_goals                                     */
+    int32_t constraint_violations;    /* constraints == 1 (jointStep adds int(.. >= 0.01))        */
+} mapf_perf;
+
+/* Reduce step outputs that already exist: `out` holds DEVICE [T]-slot outputs (status, reward_total,
+ * cost, goals_reached, constraints [T][B][N]; shadow_goals [T][B]; T = 1: one step's [B] buffers),
+ * perf is DEVICE [B].  One launch; accumulate = 0 starts from zero, 1 continues from what perf holds
+ * (the float sums go on in order, so any chunking of an episode gives the bits of one call).  A NULL
+ * field of out leaves the metrics it feeds at their previous value (or zero).  Nothing is launched for
+ * T = 0.  Capturable, allocates nothing, does not synchronise; needs no env handle (as mapf_gae). */
+int mapf_perf_accumulate(const mapf_step_out *out, int32_t T, int32_t B, int32_t N, mapf_perf *perf,
+                         int32_t accumulate, void *stream);
+/* One step of one env added to *perf on the HOST by the same function the kernels run (HOST arrays of
+ * N values; a NULL array or shadow_goals < 0 leaves its metrics).  No device call. */
+int mapf_perf_add_host(mapf_perf *perf, int32_t N, const int8_t *status, const float *reward_total,
+                       const float *cost, const float *goals_reached, int32_t shadow_goals,
+                       const float *constraints);
+
+/* T committed steps of `policy` (0 random, 1 tape, 2 descent, 3 pibt: mapf_rollout_sparse's) in one
+ * launch that writes DEVICE perf [B] and nothing else per step: no observation, no vec, no step
+ * output.  `actions`: the [T][B][N] tape (policy 1, required); under the other policies NULL (nothing
+ * written) or [T][B][N] receiving the drawn / chosen actions.  Everything the handle holds ends exactly
+ * as after mapf_rollout_<policy>(T, ...): a following mapf_observe, mapf_step, mapf_pibt_actions or
+ * rollout gives the same bytes.  The PIBT human weight and horizon apply as in mapf_rollout_pibt.
+ * accumulate as in mapf_perf_accumulate; T = 0 does nothing and leaves perf untouched.
+ * Kinds (mapf_rollout_random_fused): 1 the pair-lane kernel's perf form, 2 the one-wave-per-env
+ * kernel's (the stepping role alone), 0 T x (the policy's pick, mapf_step with MAPF_STEP_COMMIT into a
+ * [B][N] step scratch the handle owns, mapf_perf_accumulate with T = 1; with NULL actions the picks of
+ * a step pass through a [B][N] row of that scratch).  mapf_create allocates the scratch only on handles
+ * the one-wave-per-env kernel does not cover; the call allocates nothing.
+ * Errors, all before any launch: MAPF_ESTATE descent / pibt without keep_bfs; MAPF_EINVAL null perf,
+ * bad policy, tape with null actions.  Capturable as the other rollouts. */
+int mapf_rollout_perf(mapf_env *env, int32_t policy, int32_t T, int32_t *actions, mapf_perf *perf,
+                      int32_t accumulate, void *stream);
+/* The form as text, with ",perf" inside the angle brackets: "rollout_random_kernel<..,pibt,perf>",
+ * "rollout_wide_kernel<u64,1,descent,perf>"; kind 0: "<pick>+step+perf_accumulate" (e.g.
+ * "pibt_actions+step+perf_accumulate", random: "step+perf_accumulate").  PIBT weight / horizon
+ * suffixes as mapf_rollout_pibt_plan.  Returns the kind. */
+int mapf_rollout_perf_plan(const mapf_env *env, int32_t policy, char *buf, int32_t n);
 
 /* Model.step sampling (model.py:38-40): per row, inverse CDF of ps[M][5]
  * with a Philox uniform (key seed, counter (row, step)).  DEVICE. */

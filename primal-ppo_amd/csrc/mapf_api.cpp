@@ -75,6 +75,12 @@ struct mapf_env {
     // the PIBT policy's age arrays [B][N] (mapf.h: mapf_pibt_actions): the packed goal last seen and
     // the clock it was first seen at; policy-owned, no step kernel touches them
     uint32_t *pibt_seen = nullptr, *pibt_since = nullptr;
+    // mapf_rollout_perf's per-step route: one step's outputs [B][N] (perf_accumulate reads them) and the
+    // [B][N] actions of a step where the caller takes none (mapf_step needs them).  Only on handles the
+    // one-wave-per-env kernel does not cover: every other handle has a perf kernel for every policy,
+    // and those store no action the caller did not ask for.
+    int32_t *perf_act = nullptr;
+    mapf_step_out perf_step{};
     int pibt_horizon = 1;     // the PIBT policy's human horizon K (mapf_set_pibt_human_horizon); in d.pibt_w while the weight is above 0
     template <class T>
     int alloc(T *&p, size_t n) {
@@ -279,6 +285,13 @@ int mapf_create(const mapf_config *cfg, int device, mapf_env **out) {
     rc |= e->alloc(cl, cost_lut.size());
     rc |= e->alloc(e->args.base, (ARG_SLOTS + ARG_CAPTURE_SLOTS) * ARG_SLOT_BYTES);
     rc |= e->alloc(e->pibt_seen, BN); rc |= e->alloc(e->pibt_since, BN);
+    if (!rollout_wide_fusable(d)) {
+        mapf_step_out &ps = e->perf_step;
+        rc |= e->alloc(e->perf_act, BN);
+        rc |= e->alloc(ps.status, BN); rc |= e->alloc(ps.reward_total, BN); rc |= e->alloc(ps.cost, BN);
+        rc |= e->alloc(ps.goals_reached, BN); rc |= e->alloc(ps.constraints, BN);
+        rc |= e->alloc(ps.shadow_goals, (size_t)d.B);
+    }
     if (rc) {
         std::string m = g_err;
         mapf_destroy(e);
@@ -1068,6 +1081,80 @@ int mapf_rollout_sparse(mapf_env *e, int32_t policy, int32_t T, int32_t *actions
     return rollout_impl(e, policy, "mapf_rollout_sparse", T, slots, actions, out, obs, vec, stream, shadow, valid);
 }
 
+// the PIBT weight / horizon words after a plan's text (mapf_rollout_pibt_plan's)
+static void pibt_plan_suffix(const mapf_env *e, char *buf, int32_t n) {
+    if (e->d.pibt_w == 0) return;
+    const size_t len = std::strlen(buf);
+    if (e->pibt_horizon > 1)
+        std::snprintf(buf + len, (size_t)n - len, " human_weight=%d human_horizon=%d", pibt_w_weight(e->d.pibt_w),
+                      e->pibt_horizon);
+    else
+        std::snprintf(buf + len, (size_t)n - len, " human_weight=%d", pibt_w_weight(e->d.pibt_w));
+}
+
+int mapf_rollout_perf_plan(const mapf_env *e, int32_t policy, char *buf, int32_t n) {
+    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
+    if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
+    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
+    int kind = 0;
+    if (rollout_random_fusable(e->d) && describe_rollout_perf(e->d, e->tune, buf, (size_t)n, policy)) {
+        kind = 1;
+    } else if (rollout_wide_fusable(e->d)) {
+        describe_rollout_wide_perf(e->d, e->tune, buf, (size_t)n, policy);
+        kind = 2;
+    } else {
+        std::snprintf(buf, (size_t)n, "%sstep+perf_accumulate",
+                      policy == ROLLOUT_PIBT ? "pibt_actions+" : (policy == ROLLOUT_DESCENT ? "descent_actions+" : ""));
+    }
+    if (policy == ROLLOUT_PIBT) pibt_plan_suffix(e, buf, n);
+    return kind;
+}
+
+int mapf_rollout_perf(mapf_env *e, int32_t policy, int32_t T, int32_t *actions, mapf_perf *perf, int32_t accumulate,
+                      void *stream) {
+    if (!e || !perf) return fail(MAPF_EINVAL, "null argument");
+    if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
+    if (policy == ROLLOUT_TAPE && !actions) return fail(MAPF_EINVAL, "the tape policy needs actions");
+    if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
+    if ((policy == ROLLOUT_DESCENT || policy == ROLLOUT_PIBT) && !e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
+    if (!e->ready) return fail(MAPF_ESTATE, "mapf_rollout_perf before mapf_reset");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (T == 0) return MAPF_OK;
+    accumulate = accumulate != 0;
+    // the kernels' picks go to the caller's [T][B][N]; with none they are stored nowhere
+    int32_t *act = actions;
+    const int slots = actions ? 1 : 0;
+    if (rollout_random_fused(e)) {
+        if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
+        int rc = launch_rollout_perf(e->d, T, act, slots, perf, accumulate, e->tune, s, policy, e->pibt_seen, e->pibt_since);
+        if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
+            rc = launch_rollout_wide_perf(e->d, T, act, slots, perf, accumulate, e->tune, s, policy, e->pibt_seen,
+                                          e->pibt_since);
+        if (rc == MAPF_OK) {
+            HIPCHK(hipGetLastError());
+            return MAPF_OK;
+        }
+    }
+    // no one-launch kernel: T x (the policy's pick, a committed step into the handle's step scratch, the
+    // record's accumulate over that one step), same results
+    if (!e->perf_step.status) return fail(MAPF_ESTATE, "no step scratch on this handle");
+    const size_t BN = (size_t)e->d.B * e->d.N;
+    const StepOut so = step_out_of(&e->perf_step);
+    for (int32_t t = 0; t < T; ++t) {
+        int32_t *a = actions ? actions + (size_t)t * BN : e->perf_act;
+        if (policy == ROLLOUT_DESCENT) {
+            if (int rc = mapf_descent_actions(e, a, stream)) return rc;
+        } else if (policy == ROLLOUT_PIBT) {
+            if (int rc = mapf_pibt_actions(e, a, stream)) return rc;
+        }
+        if (int rc = step_impl(e, a, &e->perf_step, MAPF_STEP_COMMIT | (policy == ROLLOUT_RANDOM ? 2u : 0u), stream)) return rc;
+        launch_perf_accumulate(so, 1, e->d.B, e->d.N, perf, t == 0 ? accumulate : 1, s);
+    }
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
 int mapf_rollout_sparse_plan(const mapf_env *e, int32_t policy, const float *obs, char *buf, int32_t n) {
     if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
     if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
@@ -1407,6 +1494,24 @@ int mapf_episode_sum(const float *x, int32_t T, int32_t B, int32_t N, float *out
     if (T < 0 || B < 1 || N < 1 || N > 128) return fail(MAPF_EINVAL, "need T >= 0, B >= 1, N in 1..128");
     launch_episode_sum(x, T, B, N, out, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+int mapf_perf_accumulate(const mapf_step_out *out, int32_t T, int32_t B, int32_t N, mapf_perf *perf, int32_t accumulate,
+                         void *stream) {
+    if (!out || !perf) return fail(MAPF_EINVAL, "null argument");
+    if (T < 0 || B < 1 || N < 1 || N > 128) return fail(MAPF_EINVAL, "need T >= 0, B >= 1, N in 1..128");
+    if (T == 0) return MAPF_OK;
+    launch_perf_accumulate(step_out_of(out), T, B, N, perf, accumulate != 0, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+int mapf_perf_add_host(mapf_perf *perf, int32_t N, const int8_t *status, const float *reward_total, const float *cost,
+                       const float *goals_reached, int32_t shadow_goals, const float *constraints) {
+    if (!perf) return fail(MAPF_EINVAL, "null argument");
+    if (N < 1 || N > 128) return fail(MAPF_EINVAL, "N must be in 1..128");
+    perf_add_step(*perf, N, status, reward_total, cost, goals_reached, shadow_goals, constraints);
     return MAPF_OK;
 }
 

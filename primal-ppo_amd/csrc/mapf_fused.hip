@@ -181,6 +181,17 @@ struct RolloutArgsOf {
     DevEnv e;
     RO ro;
 };
+// Perf launches (mapf_rollout_perf): every policy's, with the record [B] and whether the launch continues
+// it; obs, vec and out are unused, `actions` is the caller's [T][B][N] (slots = 1) or the handle's [B][N]
+// scratch (slots = 0: the caller asked for none).  One kernel per policy again (rollout_perf_kernel).
+struct RolloutOutPerf : RolloutOutPibt {
+    mapf_perf *perf;
+    int accumulate;
+};
+__device__ inline mapf_perf *ro_perf(const RolloutOut &) { return nullptr; }
+__device__ inline mapf_perf *ro_perf(const RolloutOutPerf &r) { return r.perf; }
+__device__ inline int ro_accumulate(const RolloutOut &) { return 0; }
+__device__ inline int ro_accumulate(const RolloutOutPerf &r) { return r.accumulate; }
 __device__ inline uint32_t *ro_shadow(const RolloutOut &) { return nullptr; }
 __device__ inline uint32_t *ro_shadow(const RolloutOutSparse &r) { return r.shadow; }
 __device__ inline uint32_t *ro_shadow(const RolloutOutPibtSparse &r) { return r.shadow; }
@@ -202,6 +213,13 @@ __host__ __device__ inline size_t rollout_lds_bytes(const DevEnv &e, int policy)
     return rollout_obs_lds(e) + 4 * srch::wave_lds<uint32_t, 1>(e.H, e.W) + 4 * (size_t)e.Lmax * 4 +
            (policy == ROLLOUT_TAPE ? 4 * (size_t)TAPE_K * 8 * 4
                                    : (policy == ROLLOUT_DESCENT || policy == ROLLOUT_PIBT ? 4 * (size_t)8 * 4 : 0));
+}
+
+// The perf form (mapf_rollout_perf) observes nothing: its LDS is the four envs' map rows | 4 search scratch |
+// 4 path copies | the policy's rows
+__host__ __device__ inline size_t rollout_perf_map_lds(const DevEnv &e) { return ((size_t)4 * e.Hp * e.WW * 4 + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t rollout_perf_lds_bytes(const DevEnv &e, int policy) {
+    return rollout_lds_bytes(e, policy) - rollout_obs_lds(e) + rollout_perf_map_lds(e);
 }
 
 // ST (OBS_*, mapf_observe.h): OBS_NT, nontemporal observation stores -- for slot buffers (fresh HBM lines every step,
@@ -244,6 +262,7 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
     DevEnv e, int T, RolloutOut ro) {
 #endif
     using RO = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibt, RolloutOut>;     // RolloutOut: never PIBT here
+    constexpr bool PERF = false;
 #include "mapf_fused_rollout.inc"
 }
 // the PIBT form: the same loop, a kernel of its own because its arguments differ (RolloutOutPibt);
@@ -259,6 +278,7 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
 #endif
     constexpr int POL = ROLLOUT_PIBT;
     using RO = RolloutOutPibt;
+    constexpr bool PERF = false;
 #include "mapf_fused_rollout.inc"
 }
 // the sparse form: the same loop for all four policies (RO is a dependent type here), slot buffers only
@@ -273,6 +293,18 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
 #endif
     using RO = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse>;
     constexpr int ST = OBS_NT, BAND = OBS_SPARSE;
+    constexpr bool PERF = false;
+#include "mapf_fused_rollout.inc"
+}
+// the perf form (mapf_rollout_perf): the same loop without the observation and without output stores,
+// four envs per 256-thread workgroup, never grouped (SUBS = 1: pacing and priority by progress manage
+// store drains, and this form has none)
+template <int POL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void rollout_perf_kernel(DevEnv e, int T,
+                                                                                                   RolloutOutPerf ro) {
+    using RO = RolloutOutPerf;
+    constexpr int ST = OBS_PLAIN, SUBS = 1, BAND = 0;
+    constexpr bool PERF = true;
 #include "mapf_fused_rollout.inc"
 }
 template <int ST, int SUBS, int BAND, int POL>
@@ -434,6 +466,57 @@ int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOu
         if (p.subs == 4)
             return slots ? launch(rollout_kernel_fn<true, 4, false, POL>()) : launch(rollout_kernel_fn<false, 4, false, POL>());
         return slots ? launch(rollout_kernel_fn<true, 1, false, POL>()) : launch(rollout_kernel_fn<false, 1, false, POL>());
+    });
+}
+
+// mapf_rollout_perf on the pair-lane kernel: the slot form's LDS layout (the searches and the picks' rows
+// sit behind the observation's areas), requested as plan_rollout_random does for its ungrouped form
+static bool plan_rollout_perf(const DevEnv &e, const mapf_tuning &tu, RolloutPlan &p, int policy) {
+    if (!rollout_random_fusable(e) || rollout_perf_lds_bytes(e, policy) > 64 * 1024) return false;
+    const int grid = (e.B + 3) / 4;
+    const int ncu = device_cu_count();
+    int occ = (grid + ncu - 1) / ncu;
+    if (tu.roll_occ >= 1 && tu.roll_occ <= 16) occ = tu.roll_occ;
+    // the form's own request: map rows, search scratch, path copies, rows (c2: 4 workgroups of 4 waves per CU,
+    // the registers' 4 waves per SIMD, which this request leaves room for); raised to the CU's even share so
+    // that no CU takes more workgroups than ceil(grid / CUs)
+    size_t lds = rollout_perf_lds_bytes(e, policy);
+    const size_t cap = ((size_t)160 * 1024 / (size_t)occ) & ~(size_t)255;
+    if (occ >= 3 && cap > lds && cap <= 64 * 1024) lds = cap;
+    p.subs = 1;
+    p.grid = grid;
+    p.lds = lds;
+    p.sub_lds = (int)((rollout_perf_lds_bytes(e, policy) + 15) & ~(size_t)15);
+    p.fair = 0;
+    p.slack = -1;
+    p.remap = tu.xcd_remap != 0;
+    return true;
+}
+
+bool describe_rollout_perf(const DevEnv &e, const mapf_tuning &tu, char *buf, size_t n, int policy) {
+    RolloutPlan p;
+    if (!plan_rollout_perf(e, tu, p, policy)) {
+        std::snprintf(buf, n, "none");
+        return false;
+    }
+    std::snprintf(buf, n, "rollout_random_kernel<1%s,perf> grid=%d block=256 lds=%zu remap=%d", rollout_policy_tag(policy),
+                  p.grid, p.lds, p.remap);
+    return true;
+}
+
+int launch_rollout_perf(const DevEnv &e, int T, int32_t *actions, int slots, mapf_perf *perf, int accumulate,
+                        const mapf_tuning &tu, hipStream_t s, int policy, uint32_t *pibt_seen, uint32_t *pibt_since) {
+    RolloutPlan p;
+    if (!plan_rollout_perf(e, tu, p, policy)) return ROLLOUT_NOT_COVERED;
+    RolloutOutPerf ro{};
+    static_cast<RolloutOut &>(ro) = RolloutOut{actions, StepOut{}, nullptr, nullptr, slots, p.remap, p.sub_lds, -1, 0};
+    ro.pibt_seen = pibt_seen;
+    ro.pibt_since = pibt_since;
+    ro.perf = perf;
+    ro.accumulate = accumulate;
+    return with_policy(policy, [&](auto pol) -> int {
+        hipLaunchKernelGGL(rollout_perf_kernel<decltype(pol)::value>, dim3(p.grid), dim3(256), p.lds, s, e, T, ro);
+        return MAPF_OK;
     });
 }
 

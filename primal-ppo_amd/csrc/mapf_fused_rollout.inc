@@ -2,6 +2,9 @@
 // (mapf_fused.hip: rollout_random_kernel, rollout_random_pibt_kernel, rollout_sparse_kernel), included into each.  In scope:
 // the template arguments ST, SUBS, BAND, the policy POL, the arguments e, T, ro and RO, the argument type of the policy's kernel (a dependent name
 // in rollout_random_kernel, so that the PIBT branches' members are looked up only where they exist).
+// PERF (rollout_perf_kernel, mapf_rollout_perf): the step, the policy's pick and the wave's own search work
+// stay; nothing is observed and no step output is stored -- the values the stores would take are added to
+// the wave's record (PerfAcc, mapf_perf.h), which is stored once after the loop.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int E = 4;                     // envs per workgroup, one per wave
     constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT, PIBT = POL == ROLLOUT_PIBT;
@@ -23,21 +26,31 @@
     uint32_t *prog = reinterpret_cast<uint32_t *>(smem + (size_t)SUBS * ro.sub_lds);
     static_assert(SUBS == 1 || 4 * SUBS == PACE_RING, "the pacing ring takes the place of the per-wave counters");
     const int gw = sub * E + le;                       // the wave's index in the workgroup
-    ObsLds L = obs_layout(e, E, qsm, true);
+    // PERF: no observation areas -- the four envs' map rows alone stand where the observation layout does
+    // (rollout_perf_map_lds), then the same search scratch, path copies and picks' rows
+    ObsLds L{};
+    if constexpr (PERF) {
+        L.rowsz = e.Hp * e.WW;
+        L.mapc = reinterpret_cast<uint32_t *>(qsm);
+    } else {
+        L = obs_layout(e, E, qsm, true);
+    }
+    const size_t obs_sz = PERF ? rollout_perf_map_lds(e) : rollout_obs_lds(e);
+    const size_t base_sz = PERF ? rollout_perf_lds_bytes(e, ROLLOUT_RANDOM) : rollout_lds_bytes(e, ROLLOUT_RANDOM);
     float4 *lut = reinterpret_cast<float4 *>(qsm + rollout_obs_lds(e) - 256);
-    if (qt < 16) lut[qt] = make_float4((float)(qt & 1), (float)((qt >> 1) & 1), (float)((qt >> 2) & 1), (float)(qt >> 3));
+    if (!PERF && qt < 16) lut[qt] = make_float4((float)(qt & 1), (float)((qt >> 1) & 1), (float)((qt >> 2) & 1), (float)(qt >> 3));
     // envs past B never count: fair, they start at the top; paced, they are not among the live waves
     if (SUBS > 1 && (int)threadIdx.x < 4 * SUBS)
         prog[threadIdx.x] = ro.fair <= 0 || wg * SUBS * E + (int)threadIdx.x < e.B ? 0u : 0xFFFFFFFFu;
     __syncthreads();
-    L.lut = lut;
+    if constexpr (!PERF) L.lut = lut;
     const size_t swl = srch::wave_lds<uint32_t, 1>(e.H, e.W);
-    char *slds = qsm + rollout_obs_lds(e) + (size_t)le * swl;
-    uint32_t *lpath = reinterpret_cast<uint32_t *>(qsm + rollout_obs_lds(e) + 4 * swl) + (size_t)le * e.Lmax;
+    char *slds = qsm + obs_sz + (size_t)le * swl;
+    uint32_t *lpath = reinterpret_cast<uint32_t *>(qsm + obs_sz + 4 * swl) + (size_t)le * e.Lmax;
     // TAPE: this wave's TAPE_K staged rows, after the quarter's path copies; DESCENT: its one row of picks
     int32_t *trow = nullptr;
-    if constexpr (TAPE) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e, ROLLOUT_RANDOM)) + (size_t)le * TAPE_K * 8;
-    if constexpr (DESCENT || PIBT) trow = reinterpret_cast<int32_t *>(qsm + rollout_lds_bytes(e, ROLLOUT_RANDOM)) + (size_t)le * 8;
+    if constexpr (TAPE) trow = reinterpret_cast<int32_t *>(qsm + base_sz) + (size_t)le * TAPE_K * 8;
+    if constexpr (DESCENT || PIBT) trow = reinterpret_cast<int32_t *>(qsm + base_sz) + (size_t)le * 8;
     const uint32_t mreg = obs_map_word(e, b0, nenv, (int)(threadIdx.x & 63));
     EnvRegs rs{};
     if (le < nenv) env_regs_load<8>(e, b0 + le, rs, lpath);
@@ -49,9 +62,14 @@
             psince = static_cast<const RO &>(ro).pibt_since[ag];
         }
     }
+    [[maybe_unused]] PerfAcc pacc;          // PERF: the record to continue from, among the prologue's loads
+    if constexpr (PERF) {
+        if (le < nenv) pacc = perf_acc_load(ro_perf(ro) + (b0 + __builtin_amdgcn_readfirstlane(le)), ro_accumulate(ro));
+    }
     // every prologue load has landed before the loop: otherwise the compiler keeps a
     // register's load "pending" at the loop header and waits vmcnt(0) -- i.e. behind
     // all of the previous step's stores -- where the loop uses it
+    if constexpr (PERF) __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0): the record's loads are scalar
     __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0), expcnt/lgkmcnt untouched
     // the lane's skip set, one bit per store of its env's slice, from the slice's address.  It is
     // the same at every step where the unit divides the slot stride (every slot of the env keeps
@@ -64,6 +82,14 @@
         if (le < nenv && !band_moves)
             band_mask = obs_band_skip_mask(e, MAPF_BAND_UNIT, (size_t)(ro.obs + (size_t)(b0 + le) * e.N * e.C * e.F * e.F),
                                            (int)(threadIdx.x & 63));
+    }
+    if constexpr (PERF) {
+        // the env's map rows in LDS, once (the observing forms copy them in obs_wave_init at every step):
+        // the wave's searches read them.  Lane k holds word k: rowsz <= 64 (regmap_fits, which
+        // rollout_fusable requires; obs_wave_init's rule)
+        if (le < nenv && (int)(threadIdx.x & 63) < L.rowsz) L.mapc[(size_t)le * L.rowsz + (threadIdx.x & 63)] = mreg;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
     }
     RSTAMP_BEGIN();
     // (a scalar condition: pace_wait's s_sleep ignores EXEC)
@@ -130,7 +156,7 @@
                     const size_t ai = (size_t)(b0 + le) * E.N + i;
                     const int a = descent_action(E, E.bfs + ai * bfs_cells(E.H, E.W), rs.pi, rs.clock, i);
                     as_lds(trow)[i] = a;
-                    R.actions[s * BN + ai] = a;
+                    if (!PERF || R.actions) R.actions[s * BN + ai] = a;      // PERF: no actions asked for, none stored
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -160,13 +186,13 @@
                 const int a = pibt_solve_wave<8>(E.N, lane, head ? rs.pi : NO_CELL, cand, age);
                 if (head) {
                     as_lds(trow)[i] = a;
-                    R.actions[s * BN + ai] = a;
+                    if (!PERF || R.actions) R.actions[s * BN + ai] = a;
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
-        StepOut o = R.out;
+        StepOut o = PERF ? StepOut{} : R.out;
         if (o.status) o.status += s * BN;
         if (o.reward) o.reward += s * BN;
         if (o.shadow_goals) o.shadow_goals += s * E.B;
@@ -177,10 +203,17 @@
         if (o.constraints) o.constraints += s * BN;
         if (o.reward_total) o.reward_total += s * BN;
         PairsDeferred dfr;
-        step_pairs_env<8, true, true, true, TAPE || DESCENT || PIBT>(
-            E, TAPE ? trow + (size_t)(t & (TAPE_K - 1)) * 8 : (DESCENT || PIBT ? trow : R.actions + s * BN), o,
+        [[maybe_unused]] StepVals pv;
+        step_pairs_env<8, !PERF, true, true, TAPE || DESCENT || PIBT, PERF>(
+            E, TAPE ? trow + (size_t)(t & (TAPE_K - 1)) * 8 : (DESCENT || PIBT ? trow : (PERF && !R.actions ? nullptr : R.actions + s * BN)), o,
             TAPE || DESCENT || PIBT ? 1u : 3u, 0,
-            blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs);
+            blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs, PERF ? &pv : nullptr);
+        if constexpr (PERF) {
+            if (le < nenv) {
+                perf_acc_step<8>(pacc, pv, E.N, (int)(threadIdx.x & 63));
+                step_pairs_search_inline(E, dfr, slds, L.mapc + (size_t)le * L.rowsz, rs);
+            }
+        } else
         if (le < nenv) {
             const ObsGroup g = obs_wave_init(E, L, le, mreg);
             if (BAND == OBS_BAND && band_moves)
@@ -209,5 +242,8 @@
             static_cast<const RO &>(ro).pibt_seen[(size_t)(b0 + le) * e.N + (lane >> 3)] = pseen;
             static_cast<const RO &>(ro).pibt_since[(size_t)(b0 + le) * e.N + (lane >> 3)] = psince;
         }
+    }
+    if constexpr (PERF) {
+        if (le < nenv) perf_acc_store(pacc, ro_perf(ro) + (b0 + le), (int)(threadIdx.x & 63));
     }
     if (le < nenv) RSTAMP_END(b0 + le);

@@ -8,6 +8,7 @@
 
 #include "mapf.h"
 #include "mapf_common.h"
+#include "mapf_perf.h"
 
 namespace mapf {
 
@@ -148,6 +149,16 @@ int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOu
                            uint32_t *pibt_seen, uint32_t *pibt_since, uint32_t *shadow = nullptr, int valid = 0);
 bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy,
                              bool sparse = false, const float *obs = nullptr);
+// mapf_rollout_perf's launches: the kernels' perf forms (",perf" in the plan's text), which write the
+// record perf [B] and no observation or step output.  actions / slots: the caller's [T][B][N] with
+// slots = 1, or a [B][N] scratch with slots = 0 (the tape: always the former).
+int launch_rollout_perf(const DevEnv &e, int T, int32_t *actions, int slots, mapf_perf *perf, int accumulate,
+                        const mapf_tuning &tu, hipStream_t s, int policy, uint32_t *pibt_seen, uint32_t *pibt_since);
+bool describe_rollout_perf(const DevEnv &e, const mapf_tuning &tu, char *buf, size_t n, int policy);
+int launch_rollout_wide_perf(const DevEnv &e, int T, int32_t *actions, int slots, mapf_perf *perf, int accumulate,
+                             const mapf_tuning &tu, hipStream_t s, int policy, uint32_t *pibt_seen,
+                             uint32_t *pibt_since);
+void describe_rollout_wide_perf(const DevEnv &e, const mapf_tuning &tu, char *buf, size_t n, int policy);
 // the same for up to 64 agents / per-env maps / the BFS channel: one wave per env
 // (mapf_rollout_wide.hip); used where the pair-lane rollout does not apply.  Returns MAPF_OK or
 // MAPF_ESTATE (a captured launch found no free argument slot, ArgRing).
@@ -234,6 +245,7 @@ void launch_normalize_stats(const float *ret, const float *v, const float *cret,
                             float *adv, float *cadv, int M, float lam, float lam1, int mix, const float *lamd,
                             hipStream_t s);
 void launch_episode_sum(const float *x, int T, int B, int N, float *out, hipStream_t s);
+void launch_perf_accumulate(const StepOut &o, int T, int B, int N, mapf_perf *perf, int accumulate, hipStream_t s);
 void launch_sample(const float *ps, int stride, int32_t *a32, int64_t *a64, int M, uint64_t seed, uint32_t step,
                    hipStream_t s);
 // minibatch rows and their gather (mapf_minibatch.hip).  GatherArgs: the arrays of a mapf_gather_spec

@@ -13,11 +13,14 @@
 //  moments_kernel /  the same statistics over a minibatch split across ranks: sums (then
 //  normalize_stats_  sums of squares about the global mean) to be all-reduced, then the
 //  kernel            normalisation with the global mean and unbiased variance.
+//  perf_accumulate_kernel  all eight OneEpPerformance numbers of every env from [T]-slot step outputs
+//                    (mapf_perf_accumulate; the arithmetic is mapf_perf.h's, shared with the host)
 //  episode_sum_kernel  OneEpPerformance.episodeReward / episodeCostReward (runner.py:95-96):
 //                    each step's np.sum of the env's N float32 values (numpy's pairwise
 //                    order), accumulated in float32 over the T steps.
 #include "mapf_common.h"
 #include "mapf_kernels.h"
+#include "mapf_perf.h"
 
 namespace mapf {
 
@@ -143,29 +146,6 @@ __global__ __launch_bounds__(256) void normalize_stats_kernel(const float *__res
     cadv[k] = c;
 }
 
-// np.sum over a float32 [1, N] array (numpy's pairwise_sum, N <= 128: sequential below 8
-// elements, else 8 strided accumulators combined ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the
-// remainder in order; the reduction's identity 0 added first)
-__device__ inline float np_sum_f32(const float *a, int n) {
-    float res;
-    if (n < 8) {
-        res = 0.f;
-        for (int i = 0; i < n; ++i) res = __fadd_rn(res, a[i]);
-    } else {
-        float r[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = a[j];
-        int i = 8;
-        for (; i < n - (n % 8); i += 8)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] = __fadd_rn(r[j], a[i + j]);
-        res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])),
-                        __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
-        for (; i < n; ++i) res = __fadd_rn(res, a[i]);
-    }
-    return __fadd_rn(0.f, res);
-}
-
 // x [T][B][N]: out[b] = sum over t (float32, in order) of np_sum_f32(x[t][b][:]) -- the python
 // accumulator starts at int 0, and 0 + np.float32 stays np.float32 (NEP 50)
 __global__ __launch_bounds__(256) void episode_sum_kernel(const float *__restrict__ x, int T, int B, int N,
@@ -175,6 +155,26 @@ __global__ __launch_bounds__(256) void episode_sum_kernel(const float *__restric
     float acc = 0.f;
     for (int t = 0; t < T; ++t) acc = __fadd_rn(acc, np_sum_f32(x + ((size_t)t * B + b) * N, N));
     out[b] = acc;
+}
+
+// mapf_perf_accumulate: one lane per env walks its T steps in order (perf_add_step, mapf_perf.h)
+__global__ __launch_bounds__(256) void perf_accumulate_kernel(StepOut o, int T, int B, int N, mapf_perf *__restrict__ perf,
+                                                              int accumulate) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    mapf_perf p{};
+    if (accumulate) p = perf[b];
+    for (int t = 0; t < T; ++t) {
+        const size_t k = ((size_t)t * B + b) * N;
+        perf_add_step(p, N, o.status ? o.status + k : nullptr, o.reward_total ? o.reward_total + k : nullptr,
+                      o.cost ? o.cost + k : nullptr, o.goals_reached ? o.goals_reached + k : nullptr,
+                      o.shadow_goals ? o.shadow_goals[(size_t)t * B + b] : -1, o.constraints ? o.constraints + k : nullptr);
+    }
+    perf[b] = p;
+}
+
+void launch_perf_accumulate(const StepOut &o, int T, int B, int N, mapf_perf *perf, int accumulate, hipStream_t s) {
+    hipLaunchKernelGGL(perf_accumulate_kernel, dim3((B + 255) / 256), dim3(256), 0, s, o, T, B, N, perf, accumulate);
 }
 
 void launch_moments(const float *ret, const float *v, const float *cret, const float *cv, int M, const double *mean,

@@ -663,6 +663,101 @@ static int launch_wide_t(const DevEnv &e, int steps, const WideOutPibt &ro, cons
     return MAPF_OK;
 }
 
+// ---- the perf form (mapf_rollout_perf): the stepping role alone ------------------------------------
+// One wave = one workgroup = one env for the whole launch, whatever the slot forms' tuning says: there
+// is no observation, so no observer waves, no snapshot ring, no pacing and no priority (they manage the
+// observation's store drain).  Per step: step_group<.., PERF> (the policy's pick inside it, as in the
+// observing forms), the record (perf_acc_step, mapf_perf.h), the BFS maps of the agents whose goal
+// changed, the human's next path.  The state ends as rollout_wide_body leaves it: the same step, the
+// same searches in the same order, step_regs_store and the PIBT age pair at the end.
+// LDS, the form's own: map rows | cost table | one scratch area, the larger of the search's BFS image and
+// the step's neighbour grid (the step is done with the grid before a search begins) -- no nibble table, no
+// bit-stream, no occupancy, no snapshot.  ro.grid = 0 (mapf_tuning.wide_grid 0): the agent loop, no grid.
+template <class T, int RW>
+__host__ __device__ inline size_t wide_perf_scratch_bytes(const DevEnv &e, int grid) {
+    const size_t s = srch::wave_lds<T, RW>(e.H, e.W), g = grid ? wide_grid_bytes(e) : 0;
+    return wide_a16(s > g ? s : g);
+}
+template <class T, int RW>
+__host__ __device__ inline size_t wide_perf_lds_bytes(const DevEnv &e, int grid) {
+    return wide_a16((size_t)e.Hp * e.WW * 4) + wide_cost_bytes(e) + wide_perf_scratch_bytes<T, RW>(e, grid);
+}
+struct WidePerfOut : WideOutPibt {
+    mapf_perf *perf;
+    int accumulate;
+};
+
+template <class T, int RW, int POL>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void rollout_wide_perf_kernel(DevEnv e, int T_steps,
+                                                                                                      WidePerfOut ro) {
+    constexpr bool TAPE = POL == ROLLOUT_TAPE, PIBT = POL == ROLLOUT_PIBT;
+    constexpr bool PICKS = POL == ROLLOUT_DESCENT || PIBT;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int nb = (int)gridDim.x;
+    const int b = (ro.xcd_remap && (nb & 7) == 0) ? ((int)blockIdx.x & 7) * (nb >> 3) + ((int)blockIdx.x >> 3)
+                                                  : (int)blockIdx.x;
+    if (b >= e.B) return;
+    const int lane = lane_id();
+    ObsLds L{};
+    L.rowsz = e.Hp * e.WW;
+    L.mapc = reinterpret_cast<uint32_t *>(smem);
+    char *cp = smem + wide_a16((size_t)L.rowsz * 4);
+    float *lcost = wide_cost_bytes(e) ? reinterpret_cast<float *>(cp) : nullptr;
+    char *scratch = cp + wide_cost_bytes(e);
+    uint8_t *grid = ro.grid ? reinterpret_cast<uint8_t *>(scratch) : nullptr;
+    const uint32_t *mb = env_map(e, b);
+    for (int q = lane; q < L.rowsz; q += 64) L.mapc[q] = mb[q];
+    if (lcost)
+        for (int q = lane; q <= e.R * e.R; q += 64) lcost[q] = e.cost_lut[q];
+    wide_sync();
+    StepRegs rs;
+    step_regs_load(e, b, lane, rs);
+    if constexpr (PIBT) {
+        const size_t ag = (size_t)b * e.N + (size_t)min(lane, e.N - 1);
+        rs.pseen = ro.pibt_seen[ag];
+        rs.psince = ro.pibt_since[ag];
+    }
+    PerfAcc pacc = perf_acc_load(ro.perf + b, ro.accumulate);
+    __builtin_amdgcn_s_waitcnt(0x0F70);     // vmcnt(0): the prologue's loads (as rollout_wide_body)
+    const StepSrc src{L.mapc, lcost, grid};
+    const WaveGroup g;
+    const size_t BN = (size_t)e.B * e.N;
+    // this lane's element of the caller's [T][B][N] actions, lane-held; none asked for: null, nothing stored
+    int32_t *lact = ro.actions ? ro.actions + (size_t)b * e.N + (size_t)min(lane, e.N - 1) : nullptr;
+    {
+        uint64_t v = (uint64_t)lact;
+        asm volatile("" : "+v"(v));
+        lact = reinterpret_cast<int32_t *>(v);
+    }
+    const StepOut none{};
+    for (int t = 0; t < T_steps; ++t) {
+        StepInline inl;
+        StepVals pv;
+        step_group<WaveGroup, true, true, PICKS ? POL : ROLLOUT_RANDOM, true>(e, lact ? lact + (size_t)t * BN : nullptr, none, TAPE || PICKS ? 1u : 3u, 0, b, g,
+                                                                              &inl, src, rs, 0u, &pv);
+        perf_acc_step<1>(pacc, pv, e.N, lane);
+        for (uint64_t m = inl.bmask; m; m &= m - 1ull) {      // agent.bfsMap of the agents whose goal changed
+            const int l = ctz64(m);
+            const uint32_t gl = (uint32_t)__builtin_amdgcn_readlane((int)inl.goal, l);
+            srch::search_one<T, RW>(e, false, b, (uint32_t)b * (uint32_t)e.N + (uint32_t)l, gl, NO_CELL, 0, scratch, L.mapc);
+        }
+        if (inl.replan) {                                     // the human's next path, into the other buffer
+            const int len = srch::search_one<T, RW>(e, true, b, 0u, inl.rstart, inl.rgoal, inl.rbuf, scratch, L.mapc);
+            if (inl.rbuf) rs.hl1 = len;
+            else rs.hl0 = len;
+        }
+        wide_sync();
+    }
+    step_regs_store(e, b, lane, rs);
+    if constexpr (PIBT) {
+        if (lane < e.N) {
+            ro.pibt_seen[(size_t)b * e.N + lane] = rs.pseen;
+            ro.pibt_since[(size_t)b * e.N + lane] = rs.psince;
+        }
+    }
+    perf_acc_store(pacc, ro.perf + b, lane);
+}
+
 template <class T> constexpr const char *row_name() {
     return std::is_same<T, uint32_t>::value ? "u32" : (std::is_same<T, uint64_t>::value ? "u64" : "Row2");
 }
@@ -711,6 +806,53 @@ void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, ch
                       (int)decltype(rw)::value, p.nt ? "true" : "false", p.bits ? ",bits" : "",
                       rollout_policy_tag(policy), p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
                       p.r.grid, p.r.overlap, p.r.slack, p.r.fair, p.r.prio, p.r.bfsobs, p.r.pair, p.r.xcd_remap);
+        return 0;
+    });
+}
+
+struct WidePerfPlan {
+    int grid_mode = 0, remap = 1;
+    size_t lds = 0;
+};
+template <class T, int RW>
+static WidePerfPlan plan_wide_perf_t(const DevEnv &e, const mapf_tuning &tu) {
+    WidePerfPlan p;
+    // the grid wherever the request stays within a workgroup's 64 KiB (it shares the search's area)
+    p.grid_mode = tu.wide_grid != 0 && wide_perf_lds_bytes<T, RW>(e, 2) <= 64 * 1024 ? 2 : 0;
+    p.remap = tu.xcd_remap != 0;
+    p.lds = wide_perf_lds_bytes<T, RW>(e, p.grid_mode);
+    return p;
+}
+
+int launch_rollout_wide_perf(const DevEnv &e, int T, int32_t *actions, int slots, mapf_perf *perf, int accumulate,
+                             const mapf_tuning &tu, hipStream_t s, int policy, uint32_t *pibt_seen,
+                             uint32_t *pibt_since) {
+    return with_row_type(e, [&](auto t, auto rw) {
+        using R = decltype(t);
+        constexpr int RWV = decltype(rw)::value;
+        const WidePerfPlan p = plan_wide_perf_t<R, RWV>(e, tu);
+        WidePerfOut ro{};
+        ro.actions = actions;
+        ro.slots = slots;
+        ro.xcd_remap = p.remap;
+        ro.grid = p.grid_mode;
+        ro.pibt_seen = pibt_seen;
+        ro.pibt_since = pibt_since;
+        ro.perf = perf;
+        ro.accumulate = accumulate;
+        return with_policy(policy, [&](auto pol) -> int {
+            hipLaunchKernelGGL((rollout_wide_perf_kernel<R, RWV, decltype(pol)::value>), dim3(e.B), dim3(64), p.lds, s, e, T, ro);
+            return MAPF_OK;
+        });
+    });
+}
+
+void describe_rollout_wide_perf(const DevEnv &e, const mapf_tuning &tu, char *buf, size_t n, int policy) {
+    with_row_type(e, [&](auto t, auto rw) {
+        const WidePerfPlan p = plan_wide_perf_t<decltype(t), decltype(rw)::value>(e, tu);
+        std::snprintf(buf, n, "rollout_wide_kernel<%s,%d%s,perf> grid=%d block=64 lds=%zu wpe=1 epw=1 grid_mode=%d remap=%d",
+                      row_name<decltype(t)>(), (int)decltype(rw)::value, rollout_policy_tag(policy), e.B, p.lds,
+                      p.grid_mode, p.remap);
         return 0;
     });
 }

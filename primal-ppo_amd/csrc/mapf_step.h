@@ -147,11 +147,11 @@ struct StepSrc {
 // the wave picks with the PIBT solve (mapf_pibt.h) from the same five cells per lane, the env's
 // human cells and the age pair in rg, and stores the picks likewise.  Any other POL: the actions
 // come from `flags` bit 1 or the caller.
-template <class Grp, bool REGS = false, bool LANEPTR = false, int POL = ROLLOUT_RANDOM>
+template <class Grp, bool REGS = false, bool LANEPTR = false, int POL = ROLLOUT_RANDOM, bool PERF = false>
 __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e, int32_t *__restrict__ actions,
                                                                 const StepOut &out, uint32_t flags, int parity, int b,
                                                                 const Grp &g, StepInline *inl, StepSrc src,
-                                                                StepRegs &rg, uint32_t have = 0) {
+                                                                StepRegs &rg, uint32_t have = 0, StepVals *pv = nullptr) {
     constexpr bool DESCENT = POL == ROLLOUT_DESCENT, PIBT = POL == ROLLOUT_PIBT;
     static_assert(!PIBT || (REGS && std::is_same<Grp, WaveGroup>::value), "the PIBT solve runs on a whole wave");
     const int N = e.N;
@@ -239,7 +239,7 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         if (act) {
             a = descent_action(e, e.bfs + ai * bfs_cells(e.H, e.W), pp, clock, i);
-            actions[oi] = a;
+            if (!PERF || actions) actions[oi] = a;      // PERF: a caller that takes no actions passes none
         }
     } else if constexpr (PIBT) {
         // The map cells load where descent's do, under the same visibility rule (the caller
@@ -260,12 +260,12 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
             pibt_candidates(e, e.bfs + ai * bfs_cells(e.H, e.W), pp, sm, rg.hp, rg.hn, clock, i, cand, [&](int j) { return pibt_rl(hf, j); });
         }
         a = pibt_solve_wave(N, i, pp, cand, age);     // every lane: pp is NO_CELL past N
-        if (act) actions[oi] = a;
+        if (act && (!PERF || actions)) actions[oi] = a;
     } else
     if (flags & 2u) {          // random policy fused in: same stream as random_actions_kernel
         if (act) {
             a = random_action(philox(env_id, P_ACT | ((uint32_t)(i >> 3) << 8), clock, 0u, e.seed), i);
-            actions[oi] = a;
+            if (!PERF || actions) actions[oi] = a;
         }
     } else if (act) {
         a = actions[oi];
@@ -450,6 +450,13 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
         }
     }
     if (i == 0 && has(2, out.shadow_goals)) out.shadow_goals[ob] = popc64(shadow_mask);
+    if constexpr (PERF) {      // the stores' values for the wave's record (mapf_perf.h)
+        if (act) {
+            pv->st = st;
+            pv->cost = cin ? (REGS && src.cost ? as_lds(src.cost)[cd2] : e.cost_lut[cd2]) : 0.f;
+        }
+        pv->nshadow = popc64(shadow_mask);
+    }
     if (inl) inl->replan = false;
     if (!(flags & 1u)) return;
 
@@ -664,6 +671,11 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
         if (has(6, out.goals_reached)) out.goals_reached[oi] = reached ? 1.f : 0.f;
         if (has(7, out.constraints)) out.constraints[oi] = cv;
         if (has(8, out.reward_total)) out.reward_total[oi] = reached ? rw + e.goal_reward : rw;   // runner.py:89-91
+        if constexpr (PERF) {
+            pv->reached = reached;
+            pv->cv = cv == 1.f;
+            pv->rtot = reached ? rw + e.goal_reward : rw;
+        }
     }
     STAMP(6);
     STAMP_END();

@@ -161,10 +161,13 @@ __device__ inline void step_pairs_finish(const DevEnv &e, const PairsDeferred &d
 // RES (with INLINE): the env state lives in *rs (EnvRegs) instead of HBM.
 // LDSACT (the tape rollout, caller's actions): `actions` is this env's row of N actions in LDS
 // (index = agent), so the step loop reads no global memory.
-template <int NP, bool FEED, bool INLINE = false, bool RES = false, bool LDSACT = false>
+// PERF (mapf_rollout_perf's kernels): the values the output stores take are also left in *pv, on the
+// agents' head lanes (zeros elsewhere), for the wave's record (mapf_perf.h).
+template <int NP, bool FEED, bool INLINE = false, bool RES = false, bool LDSACT = false, bool PERF = false>
 __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restrict__ actions, const StepOut &out,
                                                uint32_t flags, int slot, int gt, const ObsLds &ob, int b0,
-                                               RegMap rm, PairsDeferred &dfr, EnvRegs *rs = nullptr) {
+                                               RegMap rm, PairsDeferred &dfr, EnvRegs *rs = nullptr,
+                                               StepVals *pv = nullptr) {
     using namespace pairs;
     constexpr int L = NP * NP;
     constexpr uint32_t ROW = (1u << NP) - 1u;
@@ -226,7 +229,7 @@ __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restr
         const u32x4 o = philox(env_id, P_ACT, clock, 0u, e.seed);
         a_i = random_action(o, i);
         a_j = random_action(o, j);
-        if (vi && head) actions[ai] = a_i;
+        if (vi && head && (!PERF || actions)) actions[ai] = a_i;      // PERF: a caller that takes no actions passes none
     } else {
         if constexpr (LDSACT) {
             const auto row = as_lds(actions);
@@ -345,6 +348,10 @@ __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restr
         }
     }
     if (li == 0 && out.shadow_goals) out.shadow_goals[b] = __popc(shadow);
+    if constexpr (PERF) {
+        if (vi && head) { pv->st = st; pv->cost = cost; }
+        pv->nshadow = __popc(shadow);
+    }
     STAMP(2);
     if (!(flags & 1u)) return;
 
@@ -581,6 +588,11 @@ __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restr
         if (out.goals_reached) out.goals_reached[ai] = reached ? 1.f : 0.f;
         if (out.constraints) out.constraints[ai] = cv;
         if (out.reward_total) out.reward_total[ai] = reached ? rw + e.goal_reward : rw;
+        if constexpr (PERF) {
+            pv->reached = reached;
+            pv->cv = cv == 1.f;
+            pv->rtot = reached ? rw + e.goal_reward : rw;
+        }
     }
     STAMP(6);
     if constexpr (FEED) {

@@ -46,6 +46,13 @@ class State(ctypes.Structure):
     _fields_ = [(n, P) for n in ("pos", "goal", "last_action", "seq_cursor", "human", "human_path", "clock")]
 
 
+class Perf(ctypes.Structure):
+    """include/mapf.h: mapf_perf (OneEpPerformance of one env; the fields in episodes.METRIC_KEYS' order)."""
+    _fields_ = [("episode_reward", F32), ("episode_cost_reward", F32), ("human_collide", I32),
+                ("static_collide", I32), ("agent_collide", I32), ("total_goals", I32), ("shadow_goals", I32),
+                ("constraint_violations", I32)]
+
+
 GATHER_MAX = 16
 
 
@@ -137,6 +144,11 @@ SIGNATURES = {
     "mapf_normalize_advantages_stats": (ctypes.c_int, [P, P, P, P, P, P, P, I32, ctypes.c_double, I32, P]),
     "mapf_normalize_advantages_stats_dlam": (ctypes.c_int, [P, P, P, P, P, P, P, I32, P, I32, P]),
     "mapf_episode_sum": (ctypes.c_int, [P, I32, I32, I32, P, P]),
+    # OneEpPerformance records (mapf.h: mapf_perf)
+    "mapf_perf_accumulate": (ctypes.c_int, [ctypes.POINTER(StepOut), I32, I32, I32, P, I32, P]),
+    "mapf_perf_add_host": (ctypes.c_int, [ctypes.POINTER(Perf), I32, P, P, P, P, I32, P]),
+    "mapf_rollout_perf": (ctypes.c_int, [P, I32, I32, P, P, I32, P]),
+    "mapf_rollout_perf_plan": (ctypes.c_int, [P, I32, ctypes.c_char_p, I32]),
     # policy acting forward epilogues (csrc/mapf_policy.hip)
     "mapf_nhwc_bias_relu": (ctypes.c_int, [P, P, I64, I32, P]),
     "mapf_nhwc_bias_relu_pool2": (ctypes.c_int, [P, P, P, I32, I32, I32, I32, P]),

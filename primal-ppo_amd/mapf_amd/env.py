@@ -545,6 +545,50 @@ class BatchedMapfGym:
                                                   _ptr(obs), _ptr(vec), _ptr(shadow), int(valid), _stream(self.device)))
         return out, obs, vec
 
+    def rollout_perf(self, T=None, policy="random", *, tape=None, actions=None, perf=None, accumulate=False):
+        """mapf_rollout_perf (mapf.h): T committed steps under `policy` (rollout's names; T / tape as there) in
+        one launch that writes only the episode metrics -- no observation, no vec, no step output.  Returns
+        perf, int32 [B, 8] on the device (perf_dict names the columns; the two float columns hold float32
+        bits), newly allocated if None.  accumulate: continue from what `perf` holds (the float sums go on
+        in order: any chunking of an episode gives the bits of one launch).  actions: None, or int32
+        [T, B, N] receiving the drawn / chosen actions (not used under "tape").  The handle ends exactly as
+        after rollout(T, policy, ...)."""
+        _policy_symbols(policy)
+        if policy == "tape":
+            n = self._check_tape(tape)
+            if T is not None and int(T) != n:
+                raise ValueError(f"T = {T} but the tape holds {n} steps")
+            T, actions = n, tape
+        elif tape is not None:
+            raise ValueError(f"tape= goes with policy='tape', not {policy!r}")
+        else:
+            T = int(T)
+            if T < 0:
+                raise ValueError("T must be >= 0")
+            if actions is not None:
+                _check(actions, torch.int32, T * self.B * self.N, self.device, "actions")
+        if perf is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the perf to continue from")
+            perf = torch.zeros(self.B, 8, dtype=torch.int32, device=self.device)
+        else:
+            _check(perf, torch.int32, self.B * 8, self.device, "perf")
+        if T == 0:
+            return perf
+        _lib.check(_lib.lib().mapf_rollout_perf(self.h, SPARSE_POLICY[policy], T, _ptr(actions), _ptr(perf),
+                                                1 if accumulate else 0, _stream(self.device)))
+        return perf
+
+    def rollout_perf_plan(self, policy="random"):
+        """The form a rollout_perf launch takes, as text (mapf_rollout_perf_plan): the kernels' names with
+        ",perf" inside the angle brackets, or "<pick>+step+perf_accumulate" for the per-step route."""
+        _policy_symbols(policy)
+        buf = ctypes.create_string_buffer(512)
+        kind = _lib.lib().mapf_rollout_perf_plan(self.h, SPARSE_POLICY[policy], buf, 512)
+        if kind < 0:
+            _lib.check(kind)
+        return buf.value.decode()
+
     def rollout_sparse_plan(self, obs, policy="random"):
         """The form a mapf_rollout_sparse launch into `obs` takes, as text (mapf_rollout_sparse_plan):
         "rollout_random_kernel<true,4,sparse64> ..." where the sparse form applies, else the band form's."""
@@ -998,6 +1042,50 @@ def episode_sum(x):
     out = torch.empty(B, dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().mapf_episode_sum(_ptr(x), T, B, N, _ptr(out), _stream(x.device)))
     return out
+
+
+# the step outputs mapf_perf_accumulate reads (the others stay NULL)
+PERF_INPUTS = ("status", "reward_total", "cost", "goals_reached", "shadow_goals", "constraints")
+
+
+def perf_accumulate(out, perf=None, accumulate=False):
+    """mapf_perf_accumulate (mapf.h): the episode metrics of every env from step outputs that already
+    exist.  out: a dict of [T, B, N] (shadow_goals [T, B]) or one step's [B, N] ([B]) device tensors as the
+    rollouts fill them; a missing key leaves its metrics at their previous value (or zero).  Returns perf,
+    int32 [B, 8] (perf_dict), newly allocated if None; accumulate continues from what it holds."""
+    ref = next((out[k] for k in PERF_INPUTS if k != "shadow_goals" and out.get(k) is not None), None)
+    if ref is None:
+        raise ValueError(f"out: none of {PERF_INPUTS} with an agent axis present")
+    if ref.dim() not in (2, 3):
+        raise ValueError(f"out: expected [T, B, N] or [B, N] tensors, got {tuple(ref.shape)}")
+    T = ref.shape[0] if ref.dim() == 3 else 1
+    B, N = ref.shape[-2], ref.shape[-1]
+    so = _lib.StepOut()
+    for k in PERF_INPUTS:
+        t = out.get(k)
+        if t is None:
+            continue
+        dtype = torch.int8 if k == "status" else (torch.int32 if k == "shadow_goals" else torch.float32)
+        _check(t, dtype, T * B * (1 if k == "shadow_goals" else N), ref.device, k)
+        setattr(so, k, t.data_ptr())
+    if perf is None:
+        if accumulate:
+            raise ValueError("accumulate=True needs the perf to continue from")
+        perf = torch.zeros(B, 8, dtype=torch.int32, device=ref.device)
+    else:
+        _check(perf, torch.int32, B * 8, ref.device, "perf")
+    _lib.check(_lib.lib().mapf_perf_accumulate(ctypes.byref(so), T, B, N, _ptr(perf), 1 if accumulate else 0,
+                                               _stream(ref.device)))
+    return perf
+
+
+def perf_dict(perf):
+    """{METRIC_KEYS[i]: tensor [B]} of a perf tensor int32 [B, 8]: the two float metrics are the same bits
+    viewed as float32 (reinterpreted, not converted), the six counts int32."""
+    from .episodes import METRIC_KEYS
+    if perf.dtype != torch.int32 or perf.dim() != 2 or perf.shape[1] != 8:
+        raise ValueError(f"perf: expected int32 [B, 8], got {perf.dtype} {tuple(perf.shape)}")
+    return {k: (perf[:, i].contiguous().view(torch.float32) if i < 2 else perf[:, i]) for i, k in enumerate(METRIC_KEYS)}
 
 
 def sample_actions(ps, seed, step, out32=None, out64=None):

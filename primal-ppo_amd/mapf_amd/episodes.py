@@ -294,6 +294,45 @@ def replay_fixed_episodes(infos, tapes, device=None, num_channel=6, fov=9, use_d
     return res
 
 
+def evaluate_fixed_episodes_device(infos, policy, *, tapes=None, human_weight=None, human_horizon=None, device=None,
+                                   num_channel=6, fov=9, use_da=False, use_hp=False, human_movement_type=0,
+                                   max_steps=256, k_predict=5, fix_choice=1):
+    """evaluate_fixed_episodes for a policy the rollout kernels run themselves: one rollout_perf launch
+    per map-shape group, which steps the whole episode on the device and writes only the eight
+    OneEpPerformance numbers of every env (mapf_rollout_perf) -- no observation is computed or stored.
+    policy: "descent" | "pibt" (max_steps steps; human_weight / human_horizon as pibt_policy's) or
+    "tape" (tapes[(H, W)] = int32 [T, len(group), N], as replay_fixed_episodes takes them).
+    Same env arguments, same {metric: float64 numpy [E]}.  Numerically: the six integer metrics equal
+    evaluate_fixed_episodes' exactly; the two float metrics are the reference's own float32 running sums
+    (`perf.episodeReward += np.sum(rewards)`: numpy's pairwise float32 sum over the agents, accumulated
+    in float32 over the steps), converted to float64 at the end, whereas evaluate_fixed_episodes and
+    replay_fixed_episodes sum in float64 -- they agree up to float32 rounding, not bit for bit."""
+    from .env import perf_dict
+    if policy not in ("descent", "pibt", "tape"):
+        raise ValueError(f"policy: expected 'descent', 'pibt' or 'tape', got {policy!r}")
+    if policy == "tape" and tapes is None:
+        raise ValueError("policy='tape' needs tapes=")
+    device = torch.device("cuda") if device is None else torch.device(device)
+    E = infos["numEpisodes"]
+    res = {k: np.zeros(E, np.float64) for k in METRIC_KEYS}
+    for (H, W), idx in sorted(_groups_by_shape(infos).items()):
+        env = _group_env(infos, idx, H, W, device, num_channel, fov, use_da, use_hp, human_movement_type, k_predict,
+                         fix_choice, keep_bfs=policy != "tape")
+        if policy == "pibt":
+            if human_weight is not None:
+                env.set_pibt_human_weight(human_weight)
+            if human_horizon is not None:
+                env.set_pibt_human_horizon(human_horizon)
+        if policy == "tape":
+            perf = env.rollout_perf(policy="tape", tape=tapes[(H, W)])
+        else:
+            perf = env.rollout_perf(max_steps, policy)
+        for key, col in perf_dict(perf).items():
+            res[key][idx] = col.cpu().numpy().astype(np.float64)
+        env.close()
+    return res
+
+
 def make_network_policy(network, greedy=False, seed=0):
     """Model.evaluate (model.py:43-60): softmax policy, argmax when greedy, else a
     per-agent categorical draw (Philox inverse CDF in place of np.random.choice)."""
