@@ -149,6 +149,18 @@ static void apply_tuning(DevEnv &d, const mapf_tuning &t, int obs_envs) {
     d.force_agent_lanes = t.agent_lanes;
 }
 
+// DevEnv::constr_d2: the largest d2 with (R - sqrt(d2)) / R >= 0.01 in fp64 (monotone in d2, mapf_gym.py:633)
+static int constr_d2_of(int radius) {
+    const double R = (double)radius;
+    int best = -1;
+    for (int k = 0; k <= radius * radius; ++k) {
+        double v = R - std::sqrt((double)k);
+        if (!(v > 0.0)) v = 0.0;
+        if (v / R >= 0.01) best = k;
+    }
+    return best;
+}
+
 extern "C" {
 
 void mapf_tuning_default(mapf_tuning *t) {
@@ -252,12 +264,11 @@ int mapf_create(const mapf_config *cfg, int device, mapf_env **out) {
     // fp64 lookup table, computed exactly like the reference (numpy sqrt)
     const double R = (double)c.penalty_radius;
     std::vector<float> cost_lut(d.R * d.R + 1);
-    d.constr_d2 = -1;
+    d.constr_d2 = constr_d2_of(c.penalty_radius);
     for (int k = 0; k <= d.R * d.R; ++k) {
         double v = R - std::sqrt((double)k);      // np.linalg.norm -> sqrt (mapf_gym.py:519)
         if (!(v > 0.0)) v = 0.0;
         cost_lut[k] = (float)(v / R);
-        if (v / R >= 0.01) d.constr_d2 = k;       // monotone in k (mapf_gym.py:633)
     }
 
     const size_t BN = (size_t)d.B * d.N;
@@ -335,50 +346,73 @@ int mapf_destroy(mapf_env *e) {
 
 int mapf_path_capacity(const mapf_env *e) { return e ? e->d.Lmax : 0; }
 int mapf_step_observe_fused(const mapf_env *e) { return e && step_observe_fusable(e->d) ? 1 : 0; }
-static bool rollout_random_fused(const mapf_env *e) {
-    return e && (rollout_random_fusable(e->d) || rollout_wide_fusable(e->d));
+static int check_policy(int policy) {
+    if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
+    return MAPF_OK;
 }
-int mapf_rollout_random_fused(const mapf_env *e) {
-    if (!e) return 0;
-    return rollout_random_fusable(e->d) ? 1 : (rollout_wide_fusable(e->d) ? 2 : 0);
-}
-// the pair-lane kernel where it takes the launch (a tape or descent: where their LDS rows fit too), else
-// the wide kernel, else the per-step form, as rollout_impl
-static int rollout_plan_impl(const mapf_env *e, int policy, int32_t slots, char *buf, int32_t n) {
-    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
-    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
-    if (rollout_random_fusable(e->d) && describe_rollout_random(e->d, slots, e->tune, buf, (size_t)n, policy)) return 1;
-    if (rollout_wide_fusable(e->d)) {
-        describe_rollout_wide(e->d, slots & (MAPF_SLOTS | MAPF_SLOTS_OBS_BITS), e->tune, buf, (size_t)n, policy);
-        return 2;
-    }
-    std::snprintf(buf, (size_t)n, "%s%s",
-                  policy == ROLLOUT_PIBT ? "pibt_actions+step_observe"
-                                         : (policy == ROLLOUT_DESCENT ? "descent_actions+step_observe" : "step_observe"),
-                  (slots & MAPF_SLOTS_OBS_BITS) ? "_bits" : "");
-    return 0;
-}
-int mapf_rollout_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
-    return rollout_plan_impl(e, ROLLOUT_RANDOM, slots, buf, n);
-}
-int mapf_rollout_actions_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
-    return rollout_plan_impl(e, ROLLOUT_TAPE, slots, buf, n);
-}
-int mapf_rollout_descent_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
-    return rollout_plan_impl(e, ROLLOUT_DESCENT, slots, buf, n);
+// descent and PIBT pick from the agents' tiled BFS maps
+static bool needs_bfs(int policy) { return policy == ROLLOUT_DESCENT || policy == ROLLOUT_PIBT; }
+
+// what a *_plan call knows of the rollout call it describes
+static RolloutReq plan_req(RolloutForm form, int policy, int slots, const float *obs = nullptr) {
+    RolloutReq q{};
+    q.form = form;
+    q.policy = policy;
+    q.slots = slots;
+    q.obs = const_cast<float *>(obs);
+    return q;
 }
 
-int mapf_rollout_pibt_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
-    const int kind = rollout_plan_impl(e, ROLLOUT_PIBT, slots, buf, n);
-    if (kind >= 0 && e->d.pibt_w != 0) {    // the weight is a run-time value of the same kernel: a trailing word
-        const size_t len = std::strlen(buf);
-        if (e->pibt_horizon > 1)
-            std::snprintf(buf + len, (size_t)n - len, " human_weight=%d human_horizon=%d", pibt_w_weight(e->d.pibt_w),
-                          e->pibt_horizon);
-        else
-            std::snprintf(buf + len, (size_t)n - len, " human_weight=%d", pibt_w_weight(e->d.pibt_w));
+int mapf_rollout_random_fused(const mapf_env *e) { return e ? rollout_route(e->d, plan_req(ROLLOUT_OBSERVE, ROLLOUT_RANDOM, 0)) : 0; }
+
+// the PIBT weight / horizon after a plan's text: run-time values of the same kernel, so trailing words
+static void pibt_plan_suffix(const mapf_env *e, char *buf, int32_t n) {
+    if (e->d.pibt_w == 0) return;
+    const size_t len = std::strlen(buf);
+    if (e->pibt_horizon > 1)
+        std::snprintf(buf + len, (size_t)n - len, " human_weight=%d human_horizon=%d", pibt_w_weight(e->d.pibt_w),
+                      e->pibt_horizon);
+    else
+        std::snprintf(buf + len, (size_t)n - len, " human_weight=%d", pibt_w_weight(e->d.pibt_w));
+}
+
+// Every *_plan call: the request's route as the kind, and as text the kernel's form there or the per-step
+// launches -- the switch rollout_run makes
+static int rollout_plan(const mapf_env *e, const RolloutReq &q, char *buf, int32_t n) {
+    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
+    if (int rc = check_policy(q.policy)) return rc;
+    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
+    const bool perf = q.form == ROLLOUT_PERF;
+    const int route = rollout_route(e->d, q);
+    switch (route) {
+        case ROUTE_PAIRS: (perf ? describe_rollout_perf : describe_rollout_random)(e->d, q, e->tune, buf, (size_t)n); break;
+        case ROUTE_WIDE: (perf ? describe_rollout_wide_perf : describe_rollout_wide)(e->d, q, e->tune, buf, (size_t)n); break;
+        default:
+            std::snprintf(buf, (size_t)n, "%sstep%s",
+                          q.policy == ROLLOUT_PIBT ? "pibt_actions+" : (q.policy == ROLLOUT_DESCENT ? "descent_actions+" : ""),
+                          perf ? "+perf_accumulate" : ((q.slots & MAPF_SLOTS_OBS_BITS) ? "_observe_bits" : "_observe"));
     }
-    return kind;
+    if (q.policy == ROLLOUT_PIBT && q.form != ROLLOUT_SPARSE) pibt_plan_suffix(e, buf, n);   // (the sparse plan carries none)
+    return route;
+}
+int mapf_rollout_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
+    return rollout_plan(e, plan_req(ROLLOUT_OBSERVE, ROLLOUT_RANDOM, slots), buf, n);
+}
+int mapf_rollout_actions_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
+    return rollout_plan(e, plan_req(ROLLOUT_OBSERVE, ROLLOUT_TAPE, slots), buf, n);
+}
+int mapf_rollout_descent_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
+    return rollout_plan(e, plan_req(ROLLOUT_OBSERVE, ROLLOUT_DESCENT, slots), buf, n);
+}
+int mapf_rollout_pibt_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
+    return rollout_plan(e, plan_req(ROLLOUT_OBSERVE, ROLLOUT_PIBT, slots), buf, n);
+}
+// (a shadow that describes every slot: the band-clean launch where the sparse form does not apply)
+int mapf_rollout_sparse_plan(const mapf_env *e, int32_t policy, const float *obs, char *buf, int32_t n) {
+    return rollout_plan(e, plan_req(ROLLOUT_SPARSE, policy, MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN, obs), buf, n);
+}
+int mapf_rollout_perf_plan(const mapf_env *e, int32_t policy, char *buf, int32_t n) {
+    return rollout_plan(e, plan_req(ROLLOUT_PERF, policy, 0), buf, n);
 }
 
 int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent) {
@@ -387,18 +421,6 @@ int mapf_descent_pick(uint32_t descent_mask, uint32_t clock, int32_t agent) {
 
 int mapf_pibt_key(int32_t dist, int32_t action, uint32_t clock, int32_t agent) {
     return pibt_key((int)dist, (int)action, clock, (int)agent);
-}
-
-// the largest d2 with (R - sqrt(d2)) / R >= 0.01 in fp64: mapf_create's rule for DevEnv::constr_d2
-static int constr_d2_of(int radius) {
-    const double R = (double)radius;
-    int best = -1;
-    for (int k = 0; k <= radius * radius; ++k) {
-        double v = R - std::sqrt((double)k);
-        if (!(v > 0.0)) v = 0.0;
-        if (v / R >= 0.01) best = k;
-    }
-    return best;
 }
 
 int mapf_pibt_human_level(int32_t penalty_radius, int32_t d2) {
@@ -951,8 +973,100 @@ static mapf_step_out step_out_slot(const mapf_step_out &out, size_t k, const Dev
     return ot;
 }
 
-// mapf_rollout_random / _actions / _descent / _pibt (`name`, for the error text).  policy (ROLLOUT_*) says
-// where the actions come from; `actions` is the caller's tape with ROLLOUT_TAPE (read only), else out.
+// what every call that runs a policy checks after its own arguments (`name`, for the error text)
+static int policy_ready(const mapf_env *e, int policy, const char *name) {
+    if (needs_bfs(policy) && !e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
+    if (!e->ready) return fail(MAPF_ESTATE, std::string(name) + " before mapf_reset");
+    return MAPF_OK;
+}
+
+// the policy's pick into act [B][N]: descent's or PIBT's launch; nothing for the random policy (the step
+// draws) and the tape
+static int policy_pick(mapf_env *e, int policy, int32_t *act, hipStream_t s) {
+    if (!needs_bfs(policy)) return MAPF_OK;
+    if (int rc = flush_search(e, s)) return rc;      // the maps of the last step's new goals
+    if (policy == ROLLOUT_DESCENT) launch_descent_actions(e->d, act, s);
+    else launch_pibt_actions(e->d, act, e->pibt_seen, e->pibt_since, s);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+static int policy_actions(mapf_env *e, int policy, const char *name, int32_t *actions, void *stream) {
+    if (!e || !actions) return fail(MAPF_EINVAL, "null argument");
+    if (int rc = policy_ready(e, policy, name)) return rc;
+    HIPCHK(hipSetDevice(e->device));
+    return policy_pick(e, policy, actions, (hipStream_t)stream);
+}
+int mapf_descent_actions(mapf_env *e, int32_t *actions, void *stream) {
+    return policy_actions(e, ROLLOUT_DESCENT, "mapf_descent_actions", actions, stream);
+}
+int mapf_pibt_actions(mapf_env *e, int32_t *actions, void *stream) {
+    return policy_actions(e, ROLLOUT_PIBT, "mapf_pibt_actions", actions, stream);
+}
+
+int mapf_pibt_human_cells(mapf_env *e, uint32_t *cells, void *stream) {
+    if (!e || !cells) return fail(MAPF_EINVAL, "null argument");
+    if (!e->ready) return fail(MAPF_ESTATE, "mapf_pibt_human_cells before mapf_reset");
+    HIPCHK(hipSetDevice(e->device));
+    // the current path only: the path that follows may still be searched beside the step (join_deferred)
+    launch_pibt_human_cells(e->d, cells, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+// ROUTE_STEPS: T x (the policy's pick, a committed step), same results as the one-launch kernels.  An
+// observing request's step is step_observe into slot t (or in place; the tape plays row t whatever `slots`
+// says).  A perf request's is a step into the handle's step scratch and the record's accumulate over it.
+// out: the caller's outputs as q.out holds them.
+static int rollout_steps(mapf_env *e, const RolloutReq &q, const mapf_step_out *out, void *stream) {
+    const bool perf = q.form == ROLLOUT_PERF, bits = (q.slots & MAPF_SLOTS_OBS_BITS) != 0;
+    // with MAPF_SLOTS_OBS_BITS `obs` is the packed buffer (uint32 behind the float pointer): a slot is
+    // B * N * WPA words, and step_observe is told so
+    const size_t BN = (size_t)e->d.B * e->d.N;
+    const size_t obs_t = bits ? BN * (size_t)obs_bits_words(e->d.C, e->d.F) : BN * e->d.C * e->d.F * e->d.F;
+    if (perf && !e->perf_step.status) return fail(MAPF_ESTATE, "no step scratch on this handle");
+    const uint32_t draw = q.policy == ROLLOUT_RANDOM ? 2u : 0u;
+    for (int32_t t = 0; t < q.T; ++t) {
+        const size_t k = (q.slots & 1) ? (size_t)t : 0;
+        int32_t *act = q.actions ? q.actions + (q.policy == ROLLOUT_TAPE ? (size_t)t : k) * BN : e->perf_act;
+        if (int rc = policy_pick(e, q.policy, act, (hipStream_t)stream)) return rc;
+        if (perf) {
+            if (int rc = step_impl(e, act, &e->perf_step, MAPF_STEP_COMMIT | draw, stream)) return rc;
+            launch_perf_accumulate(step_out_of(&e->perf_step), 1, e->d.B, e->d.N, q.perf, t == 0 ? q.accumulate : 1,
+                                   (hipStream_t)stream);
+        } else {
+            mapf_step_out ot{};
+            if (out) ot = step_out_slot(*out, k, e->d);
+            if (int rc = step_observe_impl(e, act, out ? &ot : nullptr, draw, q.obs + k * obs_t, q.vec + k * BN * 4, stream, bits))
+                return rc;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+// A checked request on its route (rollout_plan's switch): one launch, or rollout_steps
+static int rollout_run(mapf_env *e, RolloutReq &q, const mapf_step_out *out, void *stream) {
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (q.T == 0) return MAPF_OK;
+    q.pibt_seen = e->pibt_seen;
+    q.pibt_since = e->pibt_since;
+    const bool perf = q.form == ROLLOUT_PERF;
+    const int route = rollout_route(e->d, q);
+    if (route == ROUTE_STEPS) return rollout_steps(e, q, out, stream);
+    if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
+    const int rc = route == ROUTE_PAIRS ? (perf ? launch_rollout_perf : launch_rollout_random)(e->d, q, e->tune, e->args, s)
+                                        : (perf ? launch_rollout_wide_perf : launch_rollout_wide)(e->d, q, e->tune, e->args, s);
+    if (rc == MAPF_ESTATE)
+        return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
+                                 "(16 per handle, ArgRing; mapf_release_captures frees them)");
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+// mapf_rollout_random / _actions / _descent / _pibt / _sparse (`name`, for the error text).  policy (ROLLOUT_*)
+// says where the actions come from; `actions` is the caller's tape with ROLLOUT_TAPE (read only), else out.
 // shadow / valid: mapf_rollout_sparse's (NULL: every other entry point)
 static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, int32_t slots, int32_t *actions,
                         const mapf_step_out *out, float *obs, float *vec, void *stream, uint32_t *shadow = nullptr,
@@ -960,59 +1074,25 @@ static int rollout_impl(mapf_env *e, int policy, const char *name, int32_t T, in
     if (!e || !actions || !obs || !vec) return fail(MAPF_EINVAL, "null argument");
     if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
     if (slots < 0 || slots > (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN | MAPF_SLOTS_OBS_BITS)) return fail(MAPF_EINVAL, "slots: unknown bits");
-    if ((policy == ROLLOUT_DESCENT || policy == ROLLOUT_PIBT) && !e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
-    if (!e->ready) return fail(MAPF_ESTATE, std::string(name) + " before mapf_reset");
-    // with MAPF_SLOTS_OBS_BITS `obs` is the packed buffer (uint32 behind the float pointer): a slot is
-    // B * N * WPA words, and every launch below is told so
-    const bool bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
-    const size_t BN = (size_t)e->d.B * e->d.N;
-    const size_t obs_t = bits ? BN * (size_t)obs_bits_words(e->d.C, e->d.F) : BN * e->d.C * e->d.F * e->d.F;
+    if (int rc = policy_ready(e, policy, name)) return rc;
     if (policy == ROLLOUT_TAPE && out && out->actions_fixed && T > 0) {      // the tape is read while actions_fixed is written
+        const size_t BN = (size_t)e->d.B * e->d.N;
         const uintptr_t a0 = (uintptr_t)actions, a1 = a0 + (size_t)T * BN * 4;
         const uintptr_t f0 = (uintptr_t)out->actions_fixed, f1 = f0 + ((slots & 1) ? (size_t)T : 1) * BN * 4;
         if (a0 < f1 && f0 < a1) return fail(MAPF_EINVAL, "actions_in overlaps out->actions_fixed");
     }
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (T == 0) return MAPF_OK;
-    if (rollout_random_fused(e)) {
-        if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
-        // the wide kernels take what the pair-lane one does not (a tape or descent whose LDS rows pass its
-        // LDS included); they store everything (MAPF_SLOTS_BAND_CLEAN ignored)
-        const StepOut o = step_out_of(out);
-        int rc = launch_rollout_random(e->d, T, actions, o, obs, vec, slots, e->tune, e->args, s, policy, e->pibt_seen,
-                                       e->pibt_since, shadow, valid);
-        if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
-            rc = launch_rollout_wide(e->d, T, actions, o, obs, vec, slots & (MAPF_SLOTS | MAPF_SLOTS_OBS_BITS), e->tune,
-                                     e->args, s, policy, e->pibt_seen, e->pibt_since);
-        if (rc == MAPF_ESTATE)
-            return fail(MAPF_ESTATE, "every argument slot for captured persistent launches of this handle is taken "
-                                     "(16 per handle, ArgRing; mapf_release_captures frees them)");
-        if (rc == MAPF_OK) {
-            HIPCHK(hipGetLastError());
-            return MAPF_OK;
-        }
-        // Still ROLLOUT_NOT_COVERED: pair-lane fusable, but the tape's or descent's rows pass its LDS and
-        // the wide kernel does not apply.  Never a random launch: its pair-lane kernel declines exactly
-        // where !rollout_random_fusable, and rollout_random_fused then means the wide one applies.
-    }
-    // not covered by a one-launch kernel: T step_observe launches (descent: each after its
-    // descent_actions), same results.  The tape plays row t whatever `slots` says.
-    for (int32_t t = 0; t < T; ++t) {
-        const size_t k = (slots & 1) ? (size_t)t : 0;
-        mapf_step_out ot{};
-        if (out) ot = step_out_slot(*out, k, e->d);
-        int32_t *act = actions + (policy == ROLLOUT_TAPE ? (size_t)t : k) * BN;
-        if (policy == ROLLOUT_DESCENT) {
-            if (int rc = mapf_descent_actions(e, act, stream)) return rc;
-        } else if (policy == ROLLOUT_PIBT) {
-            if (int rc = mapf_pibt_actions(e, act, stream)) return rc;
-        }
-        if (int rc = step_observe_impl(e, act, out ? &ot : nullptr, policy == ROLLOUT_RANDOM ? 2u : 0u, obs + k * obs_t,
-                                       vec + k * BN * 4, stream, bits))
-            return rc;
-    }
-    return MAPF_OK;
+    RolloutReq q{};
+    q.form = shadow ? ROLLOUT_SPARSE : ROLLOUT_OBSERVE;
+    q.policy = policy;
+    q.T = T;
+    q.slots = slots;
+    q.actions = actions;
+    q.out = step_out_of(out);
+    q.obs = obs;
+    q.vec = vec;
+    q.shadow = shadow;
+    q.valid = valid;
+    return rollout_run(e, q, out, stream);
 }
 
 int mapf_rollout_random(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
@@ -1027,41 +1107,9 @@ int mapf_rollout_actions(mapf_env *e, int32_t T, int32_t slots, const int32_t *a
                         vec, stream);
 }
 
-int mapf_descent_actions(mapf_env *e, int32_t *actions, void *stream) {
-    if (!e || !actions) return fail(MAPF_EINVAL, "null argument");
-    if (!e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
-    if (!e->ready) return fail(MAPF_ESTATE, "mapf_descent_actions before mapf_reset");
-    HIPCHK(hipSetDevice(e->device));
-    if (int rc = flush_search(e, (hipStream_t)stream)) return rc;      // the maps of the last step's new goals
-    launch_descent_actions(e->d, actions, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return MAPF_OK;
-}
-
 int mapf_rollout_descent(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
                          float *obs, float *vec, void *stream) {
     return rollout_impl(e, ROLLOUT_DESCENT, "mapf_rollout_descent", T, slots, actions_out, out, obs, vec, stream);
-}
-
-int mapf_pibt_actions(mapf_env *e, int32_t *actions, void *stream) {
-    if (!e || !actions) return fail(MAPF_EINVAL, "null argument");
-    if (!e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
-    if (!e->ready) return fail(MAPF_ESTATE, "mapf_pibt_actions before mapf_reset");
-    HIPCHK(hipSetDevice(e->device));
-    if (int rc = flush_search(e, (hipStream_t)stream)) return rc;      // the maps of the last step's new goals
-    launch_pibt_actions(e->d, actions, e->pibt_seen, e->pibt_since, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return MAPF_OK;
-}
-
-int mapf_pibt_human_cells(mapf_env *e, uint32_t *cells, void *stream) {
-    if (!e || !cells) return fail(MAPF_EINVAL, "null argument");
-    if (!e->ready) return fail(MAPF_ESTATE, "mapf_pibt_human_cells before mapf_reset");
-    HIPCHK(hipSetDevice(e->device));
-    // the current path only: the path that follows may still be searched beside the step (join_deferred)
-    launch_pibt_human_cells(e->d, cells, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return MAPF_OK;
 }
 
 int mapf_rollout_pibt(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_out, const mapf_step_out *out,
@@ -1071,7 +1119,7 @@ int mapf_rollout_pibt(mapf_env *e, int32_t T, int32_t slots, int32_t *actions_ou
 
 int mapf_rollout_sparse(mapf_env *e, int32_t policy, int32_t T, int32_t *actions, const mapf_step_out *out, float *obs,
                         float *vec, uint32_t *shadow, int32_t valid, void *stream) {
-    if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
+    if (int rc = check_policy(policy)) return rc;
     if (!shadow) return fail(MAPF_EINVAL, "null argument");
     if (valid < 0) return fail(MAPF_EINVAL, "valid must be >= 0");
     if ((uintptr_t)shadow & 63) return fail(MAPF_EINVAL, "shadow must be 64-byte aligned");
@@ -1081,88 +1129,22 @@ int mapf_rollout_sparse(mapf_env *e, int32_t policy, int32_t T, int32_t *actions
     return rollout_impl(e, policy, "mapf_rollout_sparse", T, slots, actions, out, obs, vec, stream, shadow, valid);
 }
 
-// the PIBT weight / horizon words after a plan's text (mapf_rollout_pibt_plan's)
-static void pibt_plan_suffix(const mapf_env *e, char *buf, int32_t n) {
-    if (e->d.pibt_w == 0) return;
-    const size_t len = std::strlen(buf);
-    if (e->pibt_horizon > 1)
-        std::snprintf(buf + len, (size_t)n - len, " human_weight=%d human_horizon=%d", pibt_w_weight(e->d.pibt_w),
-                      e->pibt_horizon);
-    else
-        std::snprintf(buf + len, (size_t)n - len, " human_weight=%d", pibt_w_weight(e->d.pibt_w));
-}
-
-int mapf_rollout_perf_plan(const mapf_env *e, int32_t policy, char *buf, int32_t n) {
-    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
-    if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
-    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
-    int kind = 0;
-    if (rollout_random_fusable(e->d) && describe_rollout_perf(e->d, e->tune, buf, (size_t)n, policy)) {
-        kind = 1;
-    } else if (rollout_wide_fusable(e->d)) {
-        describe_rollout_wide_perf(e->d, e->tune, buf, (size_t)n, policy);
-        kind = 2;
-    } else {
-        std::snprintf(buf, (size_t)n, "%sstep+perf_accumulate",
-                      policy == ROLLOUT_PIBT ? "pibt_actions+" : (policy == ROLLOUT_DESCENT ? "descent_actions+" : ""));
-    }
-    if (policy == ROLLOUT_PIBT) pibt_plan_suffix(e, buf, n);
-    return kind;
-}
-
 int mapf_rollout_perf(mapf_env *e, int32_t policy, int32_t T, int32_t *actions, mapf_perf *perf, int32_t accumulate,
                       void *stream) {
     if (!e || !perf) return fail(MAPF_EINVAL, "null argument");
-    if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
+    if (int rc = check_policy(policy)) return rc;
     if (policy == ROLLOUT_TAPE && !actions) return fail(MAPF_EINVAL, "the tape policy needs actions");
     if (T < 0) return fail(MAPF_EINVAL, "T must be >= 0");
-    if ((policy == ROLLOUT_DESCENT || policy == ROLLOUT_PIBT) && !e->d.keep_bfs) return fail(MAPF_ESTATE, "keep_bfs is off");
-    if (!e->ready) return fail(MAPF_ESTATE, "mapf_rollout_perf before mapf_reset");
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (T == 0) return MAPF_OK;
-    accumulate = accumulate != 0;
-    // the kernels' picks go to the caller's [T][B][N]; with none they are stored nowhere
-    int32_t *act = actions;
-    const int slots = actions ? 1 : 0;
-    if (rollout_random_fused(e)) {
-        if (int rc = flush_search(e, s)) return rc;     // the kernel searches inline from here on
-        int rc = launch_rollout_perf(e->d, T, act, slots, perf, accumulate, e->tune, s, policy, e->pibt_seen, e->pibt_since);
-        if (rc == ROLLOUT_NOT_COVERED && rollout_wide_fusable(e->d))
-            rc = launch_rollout_wide_perf(e->d, T, act, slots, perf, accumulate, e->tune, s, policy, e->pibt_seen,
-                                          e->pibt_since);
-        if (rc == MAPF_OK) {
-            HIPCHK(hipGetLastError());
-            return MAPF_OK;
-        }
-    }
-    // no one-launch kernel: T x (the policy's pick, a committed step into the handle's step scratch, the
-    // record's accumulate over that one step), same results
-    if (!e->perf_step.status) return fail(MAPF_ESTATE, "no step scratch on this handle");
-    const size_t BN = (size_t)e->d.B * e->d.N;
-    const StepOut so = step_out_of(&e->perf_step);
-    for (int32_t t = 0; t < T; ++t) {
-        int32_t *a = actions ? actions + (size_t)t * BN : e->perf_act;
-        if (policy == ROLLOUT_DESCENT) {
-            if (int rc = mapf_descent_actions(e, a, stream)) return rc;
-        } else if (policy == ROLLOUT_PIBT) {
-            if (int rc = mapf_pibt_actions(e, a, stream)) return rc;
-        }
-        if (int rc = step_impl(e, a, &e->perf_step, MAPF_STEP_COMMIT | (policy == ROLLOUT_RANDOM ? 2u : 0u), stream)) return rc;
-        launch_perf_accumulate(so, 1, e->d.B, e->d.N, perf, t == 0 ? accumulate : 1, s);
-    }
-    HIPCHK(hipGetLastError());
-    return MAPF_OK;
-}
-
-int mapf_rollout_sparse_plan(const mapf_env *e, int32_t policy, const float *obs, char *buf, int32_t n) {
-    if (!e || !buf || n < 1) return fail(MAPF_EINVAL, "null argument");
-    if (policy < ROLLOUT_RANDOM || policy > ROLLOUT_PIBT) return fail(MAPF_EINVAL, "policy must be 0..3");
-    if (hipSetDevice(e->device) != hipSuccess) return fail(MAPF_EDEVICE, "hipSetDevice failed");
-    if (rollout_random_fusable(e->d) &&
-        describe_rollout_random(e->d, MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN, e->tune, buf, (size_t)n, policy, true, obs))
-        return 1;
-    return rollout_plan_impl(e, policy, MAPF_SLOTS, buf, n);
+    if (int rc = policy_ready(e, policy, "mapf_rollout_perf")) return rc;
+    RolloutReq q{};
+    q.form = ROLLOUT_PERF;
+    q.policy = policy;
+    q.T = T;
+    q.slots = actions ? 1 : 0;      // the kernels' picks go to the caller's [T][B][N]; with none they are stored nowhere
+    q.actions = actions;
+    q.perf = perf;
+    q.accumulate = accumulate != 0;
+    return rollout_run(e, q, nullptr, stream);
 }
 
 int mapf_obs_sparse_applies(const mapf_config *cfg, uint64_t obs_address) {

@@ -315,6 +315,13 @@ constexpr auto rollout_kernel_fn() {
 
 bool rollout_random_fusable(const DevEnv &e) { return rollout_fusable(e) && rollout_lds_bytes(e, ROLLOUT_RANDOM) <= 64 * 1024; }
 
+// a policy's LDS rows past the pair-lane kernel's 64 KiB go to the wide kernel (a tape, descent, PIBT)
+int rollout_route(const DevEnv &e, const RolloutReq &q) {
+    const size_t lds = q.form == ROLLOUT_PERF ? rollout_perf_lds_bytes(e, q.policy) : rollout_lds_bytes(e, q.policy);
+    if (rollout_random_fusable(e) && lds <= 64 * 1024) return ROUTE_PAIRS;
+    return rollout_wide_fusable(e) ? ROUTE_WIDE : ROUTE_STEPS;
+}
+
 // The pair-lane rollout's launch form for this handle's tuning (mapf.h: mapf_tuning).
 struct RolloutPlan {
     int subs = 1;        // 4-env quarters per workgroup (4: the 16 waves of a CU in one workgroup)
@@ -324,21 +331,23 @@ struct RolloutPlan {
     bool tape_ungrouped = false;   // tape / descent: their LDS rows did not fit the grouped form's LDS
 };
 
-// policy ROLLOUT_TAPE / ROLLOUT_DESCENT / ROLLOUT_PIBT: the caller's-actions, descent and PIBT forms (their LDS rows; past
-// 64 KiB the wide kernel takes over)
-static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, RolloutPlan &p, int policy,
-                                bool sparse = false) {
-    if (!rollout_random_fusable(e) || rollout_lds_bytes(e, policy) > 64 * 1024) return false;
-    const int grid = (e.B + 3) / 4;
-    // Persistent waves: every CU should hold the same number of workgroups, or the
-    // CUs holding more set the pace of every step.  The LDS request caps the
-    // workgroups per CU at ceil(grid / CUs) (160 KiB of LDS per CU).
-    const int ncu = device_cu_count();
-    int occ = (grid + ncu - 1) / ncu;
-    if (tu.roll_occ >= 1 && tu.roll_occ <= 16) occ = tu.roll_occ;
-    size_t lds = rollout_lds_bytes(e, policy);
+// Persistent waves: every CU should hold the same number of workgroups, or the
+// CUs holding more set the pace of every step.  The LDS request caps the
+// workgroups per CU at occ = ceil(grid / CUs) (160 KiB of LDS per CU): a four-env workgroup's
+// `lds` bytes, raised to the CU's even share
+static size_t rollout_cu_share(const DevEnv &e, const mapf_tuning &tu, size_t lds, int &occ) {
+    const int grid = (e.B + 3) / 4, ncu = device_cu_count();
+    occ = tu.roll_occ >= 1 && tu.roll_occ <= 16 ? tu.roll_occ : (grid + ncu - 1) / ncu;
     const size_t cap = ((size_t)160 * 1024 / (size_t)occ) & ~(size_t)255;
-    if (occ >= 3 && cap > lds && cap <= 64 * 1024) lds = cap;
+    return occ >= 3 && cap > lds && cap <= 64 * 1024 ? cap : lds;
+}
+
+// ROUTE_PAIRS requests (the policy's LDS rows fit)
+static RolloutPlan plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, int policy, bool sparse) {
+    RolloutPlan p;
+    const int grid = (e.B + 3) / 4;
+    int occ;
+    const size_t lds = rollout_cu_share(e, tu, rollout_lds_bytes(e, policy), occ);
     // Slot buffers at four workgroups per CU (c2): one workgroup of all 16 waves instead,
     // each wave paced within `slack` steps of the slowest (RolloutOut::slack).  Unpaced,
     // each SIMD's four waves ran at 12.3 / 14.4 / 16.3 / 18.3 us per step by wave slot
@@ -365,7 +374,7 @@ static bool plan_rollout_random(const DevEnv &e, int slots, const mapf_tuning &t
     p.fair = fair;
     p.slack = fair > 0 ? -1 : tu.roll_slack;
     p.remap = tu.xcd_remap != 0;
-    return true;
+    return p;
 }
 
 // MAPF_SLOTS_BAND_CLEAN takes effect: slot buffers, a config-static zero band, one mask bit per store
@@ -380,22 +389,26 @@ static bool rollout_sparse_form(const DevEnv &e, int slots, const float *obs) {
     return (slots & MAPF_SLOTS) && !(slots & MAPF_SLOTS_OBS_BITS) && obs_sparse_applies(e.N, e.C, e.F, (size_t)(uintptr_t)obs);
 }
 
-bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy,
-                             bool sparse, const float *obs) {
-    const bool bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
-    sparse = sparse && rollout_sparse_form(e, slots, obs);
-    if (!sparse && obs) slots |= MAPF_SLOTS_BAND_CLEAN;          // a sparse call where the form does not apply
-    const bool band = !bits && !sparse && rollout_band_form(e, slots);      // packed zeros cost nothing to write
-    slots &= 1;
-    RolloutPlan p;
-    if (!plan_rollout_random(e, slots, tu, p, policy, sparse)) {
-        std::snprintf(buf, n, "none");
-        return false;
-    }
+// what the pair-lane kernel stores of a request's observations: packed (",bits"), sparse, or all but the zero band
+struct RolloutStores {
+    bool bits, sparse, band;
+};
+static RolloutStores rollout_stores(const DevEnv &e, const RolloutReq &q) {
+    RolloutStores f;
+    f.bits = (q.slots & MAPF_SLOTS_OBS_BITS) != 0;
+    f.sparse = q.form == ROLLOUT_SPARSE && rollout_sparse_form(e, q.slots, q.obs);
+    f.band = !f.bits && !f.sparse && rollout_band_form(e, q.slots);      // packed zeros cost nothing to write
+    return f;
+}
+
+void describe_rollout_random(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n) {
+    const RolloutStores f = rollout_stores(e, q);
+    const int slots = q.slots & 1, policy = q.policy;
+    const RolloutPlan p = plan_rollout_random(e, slots, tu, policy, f.sparse);
     char band_tag[16] = "";
-    if (band) std::snprintf(band_tag, sizeof band_tag, ",band%d", MAPF_BAND_UNIT);
-    if (sparse) std::snprintf(band_tag, sizeof band_tag, ",sparse%d", OBS_SPARSE_PIECE * 4);
-    if (bits) std::snprintf(band_tag, sizeof band_tag, ",bits");
+    if (f.band) std::snprintf(band_tag, sizeof band_tag, ",band%d", MAPF_BAND_UNIT);
+    if (f.sparse) std::snprintf(band_tag, sizeof band_tag, ",sparse%d", OBS_SPARSE_PIECE * 4);
+    if (f.bits) std::snprintf(band_tag, sizeof band_tag, ",bits");
     const int k = std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
                                 slots ? "true" : "false", p.subs, band_tag, rollout_policy_tag(policy), p.grid, 256 * p.subs,
                                 p.lds, p.subs > 1 ? p.fair : 0, p.subs > 1 ? p.slack : -1, p.remap);
@@ -406,116 +419,87 @@ bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, 
             std::snprintf(buf + k, n - (size_t)k, " fetch=load%s",
                           p.tape_ungrouped ? (policy == ROLLOUT_PIBT ? " ungrouped=pibt_lds" : " ungrouped=descent_lds") : "");
     }
-    return true;
 }
 
-// slots: the MAPF_SLOTS_* bits of mapf_rollout_random
-int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                          int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy,
-                          uint32_t *pibt_seen, uint32_t *pibt_since, uint32_t *shadow, int valid) {
-    const bool bits = (slots & MAPF_SLOTS_OBS_BITS) != 0;
-    const bool sparse = shadow && rollout_sparse_form(e, slots, obs);
-    const bool band = !bits && !sparse && rollout_band_form(e, slots) && ((uintptr_t)obs & 15) == 0;     // whole float4s
-    slots &= 1;
-    RolloutPlan p;
-    if (!plan_rollout_random(e, slots, tu, p, policy, sparse)) return ROLLOUT_NOT_COVERED;
-    const RolloutOut ro0{actions, out, obs, vec, slots, p.remap, p.sub_lds, p.slack, p.fair};
-    (void)ring;
-    return with_policy(policy, [&](auto pol) -> int {
+#if MAPF_ARGS_PTR
+template <class A>
+A kernel_args_of(void (*)(const A *, int));      // the argument block a kernel reads (RolloutArgs*); never defined
+#endif
+
+int launch_rollout_random(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, ArgRing &ring, hipStream_t s) {
+    const RolloutStores f = rollout_stores(e, q);
+    const bool band = f.band && ((uintptr_t)q.obs & 15) == 0;     // whole float4s
+    const int slots = q.slots & 1;
+    const RolloutPlan p = plan_rollout_random(e, slots, tu, q.policy, f.sparse);
+    const RolloutOut ro0{q.actions, q.out, q.obs, q.vec, slots, p.remap, p.sub_lds, p.slack, p.fair};
+    auto launch = [&](auto kern, const auto &ro) -> int {
+        const dim3 gd(p.grid), bd(256 * p.subs);
+#if MAPF_ARGS_PTR
+        using RA = decltype(kernel_args_of(kern));
+        const RA *args = push_args(ring, RA{e, ro}, s);
+        if (!args) return MAPF_ESTATE;      // a capture found no free argument slot: nothing launched
+        hipLaunchKernelGGL(kern, gd, bd, p.lds, s, args, q.T);
+#else
+        (void)ring;
+        hipLaunchKernelGGL(kern, gd, bd, p.lds, s, e, q.T, ro);
+#endif
+        return MAPF_OK;
+    };
+    return with_policy(q.policy, [&](auto pol) -> int {
         constexpr int POL = decltype(pol)::value;
         using RO = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibt, RolloutOut>;
         RO ro{};
         static_cast<RolloutOut &>(ro) = ro0;
         if constexpr (POL == ROLLOUT_PIBT) {
-            ro.pibt_seen = pibt_seen;
-            ro.pibt_since = pibt_since;
+            ro.pibt_seen = q.pibt_seen;
+            ro.pibt_since = q.pibt_since;
         }
-        auto launch = [&](auto kern) -> int {
-            const dim3 gd(p.grid), bd(256 * p.subs);
-#if MAPF_ARGS_PTR
-            using RA = std::conditional_t<POL == ROLLOUT_PIBT, RolloutArgsPibt, RolloutArgs>;
-            const RA *args = push_args(ring, RA{e, ro}, s);
-            if (!args) return MAPF_ESTATE;      // a capture found no free argument slot: nothing launched
-            hipLaunchKernelGGL(kern, gd, bd, p.lds, s, args, T);
-#else
-            hipLaunchKernelGGL(kern, gd, bd, p.lds, s, e, T, ro);
-#endif
-            return MAPF_OK;
-        };
-        if (sparse) {
-            using ROS = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse>;
-            ROS rs{};
+        if (f.sparse) {
+            std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse> rs{};
             static_cast<RO &>(rs) = ro;
-            rs.shadow = shadow;
-            rs.valid = valid;
-            const dim3 gd(p.grid), bd(256 * p.subs);
-            auto kern = p.subs == 4 ? &rollout_sparse_kernel<4, POL> : &rollout_sparse_kernel<1, POL>;
-#if MAPF_ARGS_PTR
-            const RolloutArgsOf<ROS> *args = push_args(ring, RolloutArgsOf<ROS>{e, rs}, s);
-            if (!args) return MAPF_ESTATE;
-            hipLaunchKernelGGL(kern, gd, bd, p.lds, s, args, T);
-#else
-            hipLaunchKernelGGL(kern, gd, bd, p.lds, s, e, T, rs);
-#endif
-            return MAPF_OK;
+            rs.shadow = q.shadow;
+            rs.valid = q.valid;
+            return p.subs == 4 ? launch(&rollout_sparse_kernel<4, POL>, rs) : launch(&rollout_sparse_kernel<1, POL>, rs);
         }
-        if (bits)      // one instantiation for slots and in place (ro.slots is a run-time field)
-            return p.subs == 4 ? launch(rollout_kernel_fn<OBS_BITS, 4, false, POL>()) : launch(rollout_kernel_fn<OBS_BITS, 1, false, POL>());
+        if (f.bits)      // one instantiation for slots and in place (ro.slots is a run-time field)
+            return p.subs == 4 ? launch(rollout_kernel_fn<OBS_BITS, 4, false, POL>(), ro) : launch(rollout_kernel_fn<OBS_BITS, 1, false, POL>(), ro);
         if (band)
-            return p.subs == 4 ? launch(rollout_kernel_fn<true, 4, true, POL>()) : launch(rollout_kernel_fn<true, 1, true, POL>());
+            return p.subs == 4 ? launch(rollout_kernel_fn<true, 4, true, POL>(), ro) : launch(rollout_kernel_fn<true, 1, true, POL>(), ro);
         if (p.subs == 4)
-            return slots ? launch(rollout_kernel_fn<true, 4, false, POL>()) : launch(rollout_kernel_fn<false, 4, false, POL>());
-        return slots ? launch(rollout_kernel_fn<true, 1, false, POL>()) : launch(rollout_kernel_fn<false, 1, false, POL>());
+            return slots ? launch(rollout_kernel_fn<true, 4, false, POL>(), ro) : launch(rollout_kernel_fn<false, 4, false, POL>(), ro);
+        return slots ? launch(rollout_kernel_fn<true, 1, false, POL>(), ro) : launch(rollout_kernel_fn<false, 1, false, POL>(), ro);
     });
 }
 
-// mapf_rollout_perf on the pair-lane kernel: the slot form's LDS layout (the searches and the picks' rows
-// sit behind the observation's areas), requested as plan_rollout_random does for its ungrouped form
-static bool plan_rollout_perf(const DevEnv &e, const mapf_tuning &tu, RolloutPlan &p, int policy) {
-    if (!rollout_random_fusable(e) || rollout_perf_lds_bytes(e, policy) > 64 * 1024) return false;
-    const int grid = (e.B + 3) / 4;
-    const int ncu = device_cu_count();
-    int occ = (grid + ncu - 1) / ncu;
-    if (tu.roll_occ >= 1 && tu.roll_occ <= 16) occ = tu.roll_occ;
-    // the form's own request: map rows, search scratch, path copies, rows (c2: 4 workgroups of 4 waves per CU,
-    // the registers' 4 waves per SIMD, which this request leaves room for); raised to the CU's even share so
-    // that no CU takes more workgroups than ceil(grid / CUs)
-    size_t lds = rollout_perf_lds_bytes(e, policy);
-    const size_t cap = ((size_t)160 * 1024 / (size_t)occ) & ~(size_t)255;
-    if (occ >= 3 && cap > lds && cap <= 64 * 1024) lds = cap;
-    p.subs = 1;
-    p.grid = grid;
-    p.lds = lds;
+// ROLLOUT_PERF requests on the pair-lane kernel, never grouped.  The form's own request: map rows, search
+// scratch, path copies, rows (c2: 4 workgroups of 4 waves per CU, the registers' 4 waves per SIMD, which this
+// request leaves room for), raised like the observing forms'
+static RolloutPlan plan_rollout_perf(const DevEnv &e, const mapf_tuning &tu, int policy) {
+    RolloutPlan p;
+    int occ;
+    p.grid = (e.B + 3) / 4;
+    p.lds = rollout_cu_share(e, tu, rollout_perf_lds_bytes(e, policy), occ);
     p.sub_lds = (int)((rollout_perf_lds_bytes(e, policy) + 15) & ~(size_t)15);
-    p.fair = 0;
-    p.slack = -1;
     p.remap = tu.xcd_remap != 0;
-    return true;
+    return p;
 }
 
-bool describe_rollout_perf(const DevEnv &e, const mapf_tuning &tu, char *buf, size_t n, int policy) {
-    RolloutPlan p;
-    if (!plan_rollout_perf(e, tu, p, policy)) {
-        std::snprintf(buf, n, "none");
-        return false;
-    }
-    std::snprintf(buf, n, "rollout_random_kernel<1%s,perf> grid=%d block=256 lds=%zu remap=%d", rollout_policy_tag(policy),
+void describe_rollout_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n) {
+    const RolloutPlan p = plan_rollout_perf(e, tu, q.policy);
+    std::snprintf(buf, n, "rollout_random_kernel<1%s,perf> grid=%d block=256 lds=%zu remap=%d", rollout_policy_tag(q.policy),
                   p.grid, p.lds, p.remap);
-    return true;
 }
 
-int launch_rollout_perf(const DevEnv &e, int T, int32_t *actions, int slots, mapf_perf *perf, int accumulate,
-                        const mapf_tuning &tu, hipStream_t s, int policy, uint32_t *pibt_seen, uint32_t *pibt_since) {
-    RolloutPlan p;
-    if (!plan_rollout_perf(e, tu, p, policy)) return ROLLOUT_NOT_COVERED;
+int launch_rollout_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, ArgRing &, hipStream_t s) {
+    const RolloutPlan p = plan_rollout_perf(e, tu, q.policy);
     RolloutOutPerf ro{};
-    static_cast<RolloutOut &>(ro) = RolloutOut{actions, StepOut{}, nullptr, nullptr, slots, p.remap, p.sub_lds, -1, 0};
-    ro.pibt_seen = pibt_seen;
-    ro.pibt_since = pibt_since;
-    ro.perf = perf;
-    ro.accumulate = accumulate;
-    return with_policy(policy, [&](auto pol) -> int {
-        hipLaunchKernelGGL(rollout_perf_kernel<decltype(pol)::value>, dim3(p.grid), dim3(256), p.lds, s, e, T, ro);
+    static_cast<RolloutOut &>(ro) = RolloutOut{q.actions, StepOut{}, nullptr, nullptr, q.slots, p.remap, p.sub_lds, -1, 0};
+    ro.pibt_seen = q.pibt_seen;
+    ro.pibt_since = q.pibt_since;
+    ro.perf = q.perf;
+    ro.accumulate = q.accumulate;
+    return with_policy(q.policy, [&](auto pol) -> int {
+        hipLaunchKernelGGL(rollout_perf_kernel<decltype(pol)::value>, dim3(p.grid), dim3(256), p.lds, s, e, q.T, ro);
         return MAPF_OK;
     });
 }

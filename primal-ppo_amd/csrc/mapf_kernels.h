@@ -101,33 +101,12 @@ void launch_bfs_fixup(const DevEnv &e, int parity, float *obs, hipStream_t s);
 bool step_observe_fusable(const DevEnv &e);
 void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t flags, int slot,
                          float *obs, float *vec, int nsearch, int sslot, hipStream_t s, bool bits = false);
-// T committed random-policy steps + observations in one launch (mapf_fused.hip): MAPF_OK;
-// ROLLOUT_NOT_COVERED (nothing launched) if the configuration is not covered; MAPF_ESTATE
-// (nothing launched) if a captured launch found no free argument slot (ArgRing)
-// (the kernel's form from the handle's tuning, mapf.h: mapf_tuning); describe_* write the
-// form launch_* would take as text (mapf_rollout_plan).  launch_/describe_rollout_random take
-// mapf_rollout_random's `slots` bits (MAPF_SLOTS | MAPF_SLOTS_BAND_CLEAN | MAPF_SLOTS_OBS_BITS), the
-// wide ones MAPF_SLOTS | MAPF_SLOTS_OBS_BITS.  With MAPF_SLOTS_OBS_BITS `obs` is the packed uint32
-// buffer, the kernels' OBS_BITS instantiations write it, and the plan's text carries ",bits".
-// policy: where the actions come from, the kernels' POL template parameter.
-//   ROLLOUT_RANDOM (mapf_rollout_random): the in-kernel Philox draw, written to `actions`.
-//   ROLLOUT_TAPE (mapf_rollout_actions): `actions` is the caller's [T][B][N] tape, read only, played
-//     instead of the draw; the plan's text carries ",tape".
-//   ROLLOUT_DESCENT (mapf_rollout_descent): every action is picked from the agents' tiled BFS maps
-//     (keep_bfs) and written to `actions` like the draw; the plan's text carries ",descent" (and
-//     bfsobs=0 in the wide three-wave form).
-//   ROLLOUT_PIBT (mapf_rollout_pibt): the stepping wave picks every action with the PIBT solve
-//     (mapf_pibt.h) from the tiled BFS maps and the handle's age arrays, written to `actions` like
-//     the draw; the plan's text carries ",pibt" (and bfsobs=0 in the wide three-wave form).  Its
-//     kernels take the age arrays in argument types of their own and are therefore symbols of their
-//     own over the shared bodies: rollout_random_pibt_kernel, rollout_wide_pibt_kernel,
-//     rollout_wide3_pibt_kernel.
-// describe_rollout_random returns false (text "none") where the pair-lane kernel does not take the
-// launch -- with a tape or descent that includes a fusable configuration whose LDS rows do not fit.
-// shadow / valid (mapf_rollout_sparse): the caller's piece masks, uint32 [slots][B][16], and the leading
-// slots they describe; the pair-lane kernel's sparse form where rollout_sparse_form, else the launch
-// is the MAPF_SLOTS_BAND_CLEAN one (the caller ors the bit in); the plan's text carries ",sparse64".
-constexpr int ROLLOUT_NOT_COVERED = 1;
+// T committed steps in one launch: the pair-lane kernel (mapf_fused.hip) or, for up to 64 agents / per-env
+// maps / the BFS channel, one wave per env (mapf_rollout_wide.hip).
+// policy: where the actions come from, the kernels' POL template parameter and the mark inside the angle
+// brackets of the plan text (with descent and PIBT also bfsobs=0 in the wide three-wave form).  The PIBT
+// kernels take the handle's age arrays in argument types of their own and are therefore symbols of their
+// own over the shared bodies: rollout_random_pibt_kernel, rollout_wide_pibt_kernel, rollout_wide3_pibt_kernel.
 constexpr int ROLLOUT_RANDOM = 0, ROLLOUT_TAPE = 1, ROLLOUT_DESCENT = 2, ROLLOUT_PIBT = 3;
 // f(std::integral_constant<int, policy>{}): the runtime policy as a template argument
 template <class F>
@@ -137,36 +116,48 @@ inline auto with_policy(int policy, F f) {
     if (policy == ROLLOUT_TAPE) return f(std::integral_constant<int, ROLLOUT_TAPE>{});
     return f(std::integral_constant<int, ROLLOUT_RANDOM>{});
 }
-// the policy's mark inside the angle brackets of the plan text
 inline const char *rollout_policy_tag(int policy) {
     return policy == ROLLOUT_PIBT ? ",pibt" : (policy == ROLLOUT_DESCENT ? ",descent" : (policy == ROLLOUT_TAPE ? ",tape" : ""));
 }
-// pibt_seen / pibt_since (here and in launch_rollout_wide): the handle's age arrays [B][N], read and
-// written back by ROLLOUT_PIBT launches only
+// One rollout call as its entry point received it; a *_plan call fills what it has (form, policy, slots, obs).
+enum RolloutForm { ROLLOUT_OBSERVE, ROLLOUT_SPARSE, ROLLOUT_PERF };
+struct RolloutReq {
+    RolloutForm form;    // _SPARSE: mapf_rollout_sparse, text ",sparse64" (the pair-lane kernel where
+                         // rollout_sparse_form, else as _OBSERVE); _PERF: mapf_rollout_perf, text ",perf"
+    int policy;          // ROLLOUT_*
+    int T;
+    int slots;           // MAPF_SLOTS_* bits (_SPARSE: MAPF_SLOTS, and MAPF_SLOTS_BAND_CLEAN where the shadow
+                         // describes every slot; _PERF: 1 with the caller's actions, else 0).  The wide kernels
+                         // ignore MAPF_SLOTS_BAND_CLEAN; with MAPF_SLOTS_OBS_BITS the text carries ",bits"
+    int32_t *actions;    // ROLLOUT_TAPE: the caller's [T][B][N] tape, read only; else where the picks go
+                         // (_PERF: may be null, the picks are stored nowhere)
+    StepOut out;         // _PERF: unused, as obs and vec
+    float *obs, *vec;    // MAPF_SLOTS_OBS_BITS: obs is the packed uint32 buffer
+    uint32_t *shadow;    // _SPARSE: the caller's piece masks, uint32 [slots][B][16], and the leading
+    int valid;           //   slots they describe
+    mapf_perf *perf;     // _PERF: the record [B], and whether the launch continues it
+    int accumulate;
+    uint32_t *pibt_seen, *pibt_since;   // the handle's age arrays [B][N], read and written back under ROLLOUT_PIBT only
+};
+// Where a request runs: ROUTE_PAIRS where the pair-lane kernel applies (rollout_random_fusable) and the
+// policy's LDS rows fit its 64 KiB, else ROUTE_WIDE where rollout_wide_fusable, else ROUTE_STEPS (per-step
+// launches).  The values are the kinds the *_plan calls return.  Launch and plan entries both switch on it;
+// a launch_* or describe_* called on another route than its own is a programming error.
+constexpr int ROUTE_STEPS = 0, ROUTE_PAIRS = 1, ROUTE_WIDE = 2;
 bool rollout_random_fusable(const DevEnv &e);
-int launch_rollout_random(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                           int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy,
-                           uint32_t *pibt_seen, uint32_t *pibt_since, uint32_t *shadow = nullptr, int valid = 0);
-bool describe_rollout_random(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy,
-                             bool sparse = false, const float *obs = nullptr);
-// mapf_rollout_perf's launches: the kernels' perf forms (",perf" in the plan's text), which write the
-// record perf [B] and no observation or step output.  actions / slots: the caller's [T][B][N] with
-// slots = 1, or a [B][N] scratch with slots = 0 (the tape: always the former).
-int launch_rollout_perf(const DevEnv &e, int T, int32_t *actions, int slots, mapf_perf *perf, int accumulate,
-                        const mapf_tuning &tu, hipStream_t s, int policy, uint32_t *pibt_seen, uint32_t *pibt_since);
-bool describe_rollout_perf(const DevEnv &e, const mapf_tuning &tu, char *buf, size_t n, int policy);
-int launch_rollout_wide_perf(const DevEnv &e, int T, int32_t *actions, int slots, mapf_perf *perf, int accumulate,
-                             const mapf_tuning &tu, hipStream_t s, int policy, uint32_t *pibt_seen,
-                             uint32_t *pibt_since);
-void describe_rollout_wide_perf(const DevEnv &e, const mapf_tuning &tu, char *buf, size_t n, int policy);
-// the same for up to 64 agents / per-env maps / the BFS channel: one wave per env
-// (mapf_rollout_wide.hip); used where the pair-lane rollout does not apply.  Returns MAPF_OK or
-// MAPF_ESTATE (a captured launch found no free argument slot, ArgRing).
 bool rollout_wide_fusable(const DevEnv &e);
-int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                        int slots, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s, int policy,
-                        uint32_t *pibt_seen, uint32_t *pibt_since);
-void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy);
+int rollout_route(const DevEnv &e, const RolloutReq &q);
+// launch_*: MAPF_OK, or MAPF_ESTATE (nothing launched) if a captured launch found no free argument slot
+// (ArgRing).  describe_*: the kernel's form from the handle's tuning (mapf.h: mapf_tuning) as text, the
+// one launch_* would take.  *_perf: the kernels' perf forms, for ROLLOUT_PERF requests.
+int launch_rollout_random(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s);
+int launch_rollout_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s);
+int launch_rollout_wide(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s);
+int launch_rollout_wide_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, struct ArgRing &ring, hipStream_t s);
+void describe_rollout_random(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n);
+void describe_rollout_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n);
+void describe_rollout_wide(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n);
+void describe_rollout_wide_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n);
 
 // Device-resident kernel argument blocks.  A persistent kernel whose arguments (DevEnv + its
 // output pointers, ~0.5 KiB) do not fit in the SGPR file kept them live from the kernarg

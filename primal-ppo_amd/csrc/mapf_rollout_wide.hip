@@ -516,6 +516,14 @@ constexpr auto wide3_kernel_fn() {
     if constexpr (POL == ROLLOUT_PIBT) return &rollout_wide3_pibt_kernel<T, RW, ST>;
     else return &rollout_wide3_kernel<T, RW, ST, POL>;
 }
+// ... of a policy and a plan's store form (bits, else nt): the three-wave kernel (WPE3) or the other
+template <class T, int RW, int POL, bool WPE3>
+static auto wide_kernel_of(bool bits, bool nt) {
+    if constexpr (WPE3)
+        return bits ? wide3_kernel_fn<T, RW, OBS_BITS, POL>() : (nt ? wide3_kernel_fn<T, RW, true, POL>() : wide3_kernel_fn<T, RW, false, POL>());
+    else
+        return bits ? wide_kernel_fn<T, RW, OBS_BITS, POL>() : (nt ? wide_kernel_fn<T, RW, true, POL>() : wide_kernel_fn<T, RW, false, POL>());
+}
 
 // The three-wave form is not built for 128-bit rows spread over two lanes (maps wider than 64 cells):
 // capped at 168 VGPRs (three waves per SIMD), <Row2,2> spilled 136-188 B per lane to scratch
@@ -555,12 +563,9 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     p.nt = tu.wide_nt >= 0 ? tu.wide_nt != 0 : (slots || (size_t)e.B * e.N * e.C * e.F * e.F * 4 > ((size_t)128 << 20));
     if (p.bits) p.nt = false;
     // (the packed kernels' own register counts decide their form, as each policy's do)
-    const void *kern = p.bits ? reinterpret_cast<const void *>(wide_kernel_fn<T, RW, OBS_BITS, POL>()) : p.nt ? reinterpret_cast<const void *>(wide_kernel_fn<T, RW, true, POL>())
-                            : reinterpret_cast<const void *>(wide_kernel_fn<T, RW, false, POL>());
+    const void *kern = reinterpret_cast<const void *>(wide_kernel_of<T, RW, POL, false>(p.bits, p.nt));
     const void *kern3 = nullptr;
-    if constexpr (wide3_form<T, RW>())
-        kern3 = p.bits ? reinterpret_cast<const void *>(wide3_kernel_fn<T, RW, OBS_BITS, POL>()) : p.nt ? reinterpret_cast<const void *>(wide3_kernel_fn<T, RW, true, POL>())
-                     : reinterpret_cast<const void *>(wide3_kernel_fn<T, RW, false, POL>());
+    if constexpr (wide3_form<T, RW>()) kern3 = reinterpret_cast<const void *>(wide_kernel_of<T, RW, POL, true>(p.bits, p.nt));
     // two waves per env where every env's pair fits at once: the VGPR budget of a SIMD
     // (512 per lane) over the waves it must hold, 4 SIMDs per CU
     const int fit = 512 / ((kernel_vgprs(kern) + 7) & ~7);
@@ -627,38 +632,34 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
 }
 
 template <class T, int RW, int POL>
-static int launch_wide_t(const DevEnv &e, int steps, const WideOutPibt &ro, const mapf_tuning &tu, ArgRing &ring,
-                         hipStream_t s) {
-    const WidePlan p = plan_wide_t<T, RW, POL>(e, ro.slots, tu);     // ro.slots: MAPF_SLOTS | MAPF_SLOTS_OBS_BITS
+static int launch_wide_t(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, ArgRing &ring, hipStream_t s) {
+    const WidePlan p = plan_wide_t<T, RW, POL>(e, q.slots, tu);
     wide_out_t<POL> r{};
     static_cast<WideOut &>(r) = p.r;
     if constexpr (POL == ROLLOUT_PIBT) {
-        r.pibt_seen = ro.pibt_seen;
-        r.pibt_since = ro.pibt_since;
+        r.pibt_seen = q.pibt_seen;
+        r.pibt_since = q.pibt_since;
     }
-    r.actions = ro.actions;
-    r.out = ro.out;
-    r.obs = ro.obs;
-    r.vec = ro.vec;
+    r.actions = q.actions;
+    r.out = q.out;
+    r.obs = q.obs;
+    r.vec = q.vec;
     if constexpr (wide3_form<T, RW>()) {
         if (r.wpe == 3) {
             const wide_args_t<POL> *args = push_args(ring, wide_args_t<POL>{e, r}, s);
             if (!args) return MAPF_ESTATE;
-            auto kern3 = p.bits ? wide3_kernel_fn<T, RW, OBS_BITS, POL>()
-                                : (p.nt ? wide3_kernel_fn<T, RW, true, POL>() : wide3_kernel_fn<T, RW, false, POL>());
-            hipLaunchKernelGGL(kern3, dim3(p.grid), dim3(p.block), p.lds, s, args, steps);
+            hipLaunchKernelGGL((wide_kernel_of<T, RW, POL, true>(p.bits, p.nt)), dim3(p.grid), dim3(p.block), p.lds, s, args, q.T);
             return MAPF_OK;
         }
     }
-    auto kern = p.bits ? wide_kernel_fn<T, RW, OBS_BITS, POL>()
-                       : (p.nt ? wide_kernel_fn<T, RW, true, POL>() : wide_kernel_fn<T, RW, false, POL>());
+    auto kern = wide_kernel_of<T, RW, POL, false>(p.bits, p.nt);
 #if MAPF_ARGS_PTR
     const wide_args_t<POL> *args = push_args(ring, wide_args_t<POL>{e, r}, s);
     if (!args) return MAPF_ESTATE;
-    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, s, args, steps);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, s, args, q.T);
 #else
     (void)ring;
-    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, s, e, steps, r);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, s, e, q.T, r);
 #endif
     return MAPF_OK;
 }
@@ -777,29 +778,20 @@ bool rollout_wide_fusable(const DevEnv &e) {
     return with_row_type(e, [&](auto t, auto rw) { return wide_fits<decltype(t), decltype(rw)::value>(e); });
 }
 
-int launch_rollout_wide(const DevEnv &e, int T, int32_t *actions, const StepOut &out, float *obs, float *vec,
-                        int slots, const mapf_tuning &tu, ArgRing &ring, hipStream_t s, int policy,
-                        uint32_t *pibt_seen, uint32_t *pibt_since) {
-    WideOutPibt ro{};
-    ro.pibt_seen = pibt_seen;
-    ro.pibt_since = pibt_since;
-    ro.actions = actions;
-    ro.out = out;
-    ro.obs = obs;
-    ro.vec = vec;
-    ro.slots = slots;
+int launch_rollout_wide(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, ArgRing &ring, hipStream_t s) {
     return with_row_type(e, [&](auto t, auto rw) {
         using R = decltype(t);
         constexpr int RWV = decltype(rw)::value;
-        return with_policy(policy, [&](auto pol) { return launch_wide_t<R, RWV, decltype(pol)::value>(e, T, ro, tu, ring, s); });
+        return with_policy(q.policy, [&](auto pol) { return launch_wide_t<R, RWV, decltype(pol)::value>(e, q, tu, ring, s); });
     });
 }
 
-void describe_rollout_wide(const DevEnv &e, int slots, const mapf_tuning &tu, char *buf, size_t n, int policy) {
+void describe_rollout_wide(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n) {
+    const int policy = q.policy;
     with_row_type(e, [&](auto t, auto rw) {
         using R = decltype(t);
         constexpr int RWV = decltype(rw)::value;
-        const WidePlan p = with_policy(policy, [&](auto pol) { return plan_wide_t<R, RWV, decltype(pol)::value>(e, slots, tu); });
+        const WidePlan p = with_policy(policy, [&](auto pol) { return plan_wide_t<R, RWV, decltype(pol)::value>(e, q.slots, tu); });
         std::snprintf(buf, n, "%s<%s,%d,%s%s%s> grid=%d block=%d lds=%zu wpe=%d epw=%d grid_mode=%d overlap=%d slack=%d "
                               "fair=%d prio=%d bfsobs=%d pair=%d remap=%d",
                       p.r.wpe == 3 ? "rollout_wide3_kernel" : "rollout_wide_kernel", row_name<decltype(t)>(),
@@ -824,34 +816,32 @@ static WidePerfPlan plan_wide_perf_t(const DevEnv &e, const mapf_tuning &tu) {
     return p;
 }
 
-int launch_rollout_wide_perf(const DevEnv &e, int T, int32_t *actions, int slots, mapf_perf *perf, int accumulate,
-                             const mapf_tuning &tu, hipStream_t s, int policy, uint32_t *pibt_seen,
-                             uint32_t *pibt_since) {
+int launch_rollout_wide_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, ArgRing &, hipStream_t s) {
     return with_row_type(e, [&](auto t, auto rw) {
         using R = decltype(t);
         constexpr int RWV = decltype(rw)::value;
         const WidePerfPlan p = plan_wide_perf_t<R, RWV>(e, tu);
         WidePerfOut ro{};
-        ro.actions = actions;
-        ro.slots = slots;
+        ro.actions = q.actions;
+        ro.slots = q.slots;
         ro.xcd_remap = p.remap;
         ro.grid = p.grid_mode;
-        ro.pibt_seen = pibt_seen;
-        ro.pibt_since = pibt_since;
-        ro.perf = perf;
-        ro.accumulate = accumulate;
-        return with_policy(policy, [&](auto pol) -> int {
-            hipLaunchKernelGGL((rollout_wide_perf_kernel<R, RWV, decltype(pol)::value>), dim3(e.B), dim3(64), p.lds, s, e, T, ro);
+        ro.pibt_seen = q.pibt_seen;
+        ro.pibt_since = q.pibt_since;
+        ro.perf = q.perf;
+        ro.accumulate = q.accumulate;
+        return with_policy(q.policy, [&](auto pol) -> int {
+            hipLaunchKernelGGL((rollout_wide_perf_kernel<R, RWV, decltype(pol)::value>), dim3(e.B), dim3(64), p.lds, s, e, q.T, ro);
             return MAPF_OK;
         });
     });
 }
 
-void describe_rollout_wide_perf(const DevEnv &e, const mapf_tuning &tu, char *buf, size_t n, int policy) {
+void describe_rollout_wide_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n) {
     with_row_type(e, [&](auto t, auto rw) {
         const WidePerfPlan p = plan_wide_perf_t<decltype(t), decltype(rw)::value>(e, tu);
         std::snprintf(buf, n, "rollout_wide_kernel<%s,%d%s,perf> grid=%d block=64 lds=%zu wpe=1 epw=1 grid_mode=%d remap=%d",
-                      row_name<decltype(t)>(), (int)decltype(rw)::value, rollout_policy_tag(policy), e.B, p.lds,
+                      row_name<decltype(t)>(), (int)decltype(rw)::value, rollout_policy_tag(q.policy), e.B, p.lds,
                       p.grid_mode, p.remap);
         return 0;
     });
