@@ -521,6 +521,49 @@ int mapf_rollout_pibt(mapf_env *env, int32_t T, int32_t slots, int32_t *actions_
  * " human_horizon=<K>" where K > 1; with w = 0 nothing is added. */
 int mapf_rollout_pibt_plan(const mapf_env *env, int32_t slots, char *buf, int32_t n);
 
+/* Action noise on the picked policies' rollouts (noise injection into a supervisor's trajectories, as in
+ * DART, Laskey et al.): the policy's pick stays the LABEL, and with probability eps a uniform random
+ * action is PLAYED in its place, so the trajectory drifts into states the planner alone never visits
+ * while every label remains the planner's.  Per handle one integer noise_q16 in 0..65536, eps in
+ * 1/65536 units, 0 by default.  It applies to the descent and the PIBT policy only (mapf_rollout_descent,
+ * mapf_rollout_pibt, and mapf_rollout_sparse / mapf_rollout_perf under those policies); the random and
+ * the tape policy ignore it: same results, same plan text.  For env b, agent i at clock t (steps since
+ * reset, the clock the pick sees), label = the policy's pick:
+ *   e      = philox(env_offset + b, P_NOISE | (i >> 3) << 8, t, 0; key = the handle's seed), P_NOISE = 12;
+ *   u      = 16-bit half-word i & 7 of e: word (i & 7) >> 1, shifted right by ((i & 7) & 1) * 16 (the
+ *            extraction of the random policy's action);
+ *   noisy  = u < noise_q16: never at 0, always at 65536, with probability exactly noise_q16 / 65536;
+ *   played = noisy ? the random policy's action for that agent and clock (what mapf_random_actions
+ *            gives: draw P_ACT | (i >> 3) << 8) : label.
+ * actions_out of the rollout calls receives `label`; the step is taken with `played`;
+ * out->actions_fixed is, as always, what was executed after fixActions.  The PIBT ages are updated by
+ * the pick as without noise (they depend on goals and clocks only).  With noise_q16 == 0 no draw is
+ * made and every byte of every output and of the handle's state is as without the setting; with 65536
+ * a descent or PIBT rollout equals the random policy's in everything but actions_out.  The draws are
+ * counter-based on the env clock: any chunking of T, a captured launch replayed and T per-step calls
+ * (pick, mapf_noise_actions, step) give the same bytes.
+ *
+ * mapf_set_action_noise: MAPF_EINVAL on a null env or a value outside 0..65536, and nothing changes
+ * then.  No device call; the value is an argument of the next launch.  A captured launch keeps the value
+ * it was captured with (its argument block is stored at capture).  Resets and mapf_set_state do not
+ * touch it.  While the value is above 0 the descent and PIBT rollouts run instantiations of their own --
+ * a launch without noise runs the kernels of a build without the feature, register for register -- and
+ * their *_plan texts say so: ",noise" before the closing angle bracket, e.g.
+ * "rollout_random_kernel<true,4,pibt,noise>", "rollout_wide_kernel<u64,1,descent,perf,noise>", and
+ * " noise=<q16>" at the end, after the PIBT words (the per-step route: "pibt_actions+step_observe
+ * noise=<q16>", the noise launch between the two).  At 0 nothing is added. */
+int mapf_set_action_noise(mapf_env *env, int32_t noise_q16);
+/* The handle's noise_q16, or MAPF_EINVAL on a null env. */
+int mapf_get_action_noise(const mapf_env *env);
+/* The rule for the current state (clock) of every env: labels DEVICE int32 [B][N] in, played DEVICE
+ * int32 [B][N] out; played may be labels.  One small launch, capturable; at noise 0 it copies.  Labels
+ * are not validated (a step refuses bad actions as ever).  MAPF_ESTATE before mapf_reset. */
+int mapf_noise_actions(mapf_env *env, const int32_t *labels, int32_t *played, void *stream);
+/* `played` of the rule on the host, no device call (the function the kernels run).  MAPF_EINVAL for an
+ * agent outside 0..63, a label outside 0..4 or noise_q16 outside 0..65536. */
+int mapf_action_noise_pick(uint64_t seed, uint32_t env_id, int32_t agent, uint32_t clock, int32_t noise_q16,
+                           int32_t label);
+
 /* Copy agent.bfsMap for every agent: DEVICE int16 [B][N][H][W] (requires keep_bfs). */
 int mapf_bfs(mapf_env *env, int16_t *dist, void *stream);
 

@@ -81,6 +81,9 @@ struct mapf_env {
     // and those store no action the caller did not ask for.
     int32_t *perf_act = nullptr;
     mapf_step_out perf_step{};
+    // mapf_set_action_noise's per-step route: the [B][N] row of played actions the step runs from (the
+    // policy's pick, the label, stays in the caller's row, or in perf_act where the caller takes none)
+    int32_t *noise_act = nullptr;
     int pibt_horizon = 1;     // the PIBT policy's human horizon K (mapf_set_pibt_human_horizon); in d.pibt_w while the weight is above 0
     template <class T>
     int alloc(T *&p, size_t n) {
@@ -296,6 +299,7 @@ int mapf_create(const mapf_config *cfg, int device, mapf_env **out) {
     rc |= e->alloc(cl, cost_lut.size());
     rc |= e->alloc(e->args.base, (ARG_SLOTS + ARG_CAPTURE_SLOTS) * ARG_SLOT_BYTES);
     rc |= e->alloc(e->pibt_seen, BN); rc |= e->alloc(e->pibt_since, BN);
+    rc |= e->alloc(e->noise_act, BN);
     if (!rollout_wide_fusable(d)) {
         mapf_step_out &ps = e->perf_step;
         rc |= e->alloc(e->perf_act, BN);
@@ -393,6 +397,10 @@ static int rollout_plan(const mapf_env *e, const RolloutReq &q, char *buf, int32
                           perf ? "+perf_accumulate" : ((q.slots & MAPF_SLOTS_OBS_BITS) ? "_observe_bits" : "_observe"));
     }
     if (q.policy == ROLLOUT_PIBT && q.form != ROLLOUT_SPARSE) pibt_plan_suffix(e, buf, n);   // (the sparse plan carries none)
+    if (needs_bfs(q.policy) && e->d.noise_q16 > 0) {       // the threshold of the ",noise" instantiation: after the PIBT words
+        const size_t len = std::strlen(buf);
+        std::snprintf(buf + len, (size_t)n - len, " noise=%d", e->d.noise_q16);
+    }
     return route;
 }
 int mapf_rollout_plan(const mapf_env *e, int32_t slots, char *buf, int32_t n) {
@@ -427,6 +435,27 @@ int mapf_pibt_human_level(int32_t penalty_radius, int32_t d2) {
     if (penalty_radius < 1 || penalty_radius > 64) return fail(MAPF_EINVAL, "penalty_radius must be in 1..64");
     if (d2 < 0) return fail(MAPF_EINVAL, "d2 must be >= 0");
     return pibt_human_level((int)penalty_radius, constr_d2_of((int)penalty_radius), (int)d2);
+}
+
+int mapf_set_action_noise(mapf_env *e, int32_t noise_q16) {
+    if (!e) return fail(MAPF_EINVAL, "null argument");
+    if (noise_q16 < 0 || noise_q16 > 65536) return fail(MAPF_EINVAL, "the action noise must be in 0..65536");
+    e->d.noise_q16 = (int)noise_q16;      // a kernel argument of the next launch: no device call
+    return MAPF_OK;
+}
+
+int mapf_get_action_noise(const mapf_env *e) {
+    if (!e) return fail(MAPF_EINVAL, "null argument");
+    return e->d.noise_q16;
+}
+
+int mapf_action_noise_pick(uint64_t seed, uint32_t env_id, int32_t agent, uint32_t clock, int32_t noise_q16,
+                           int32_t label) {
+    if (agent < 0 || agent > 63) return fail(MAPF_EINVAL, "agent must be in 0..63");
+    if (label < 0 || label >= NA) return fail(MAPF_EINVAL, "label must be in 0..4");
+    if (noise_q16 < 0 || noise_q16 > 65536) return fail(MAPF_EINVAL, "the action noise must be in 0..65536");
+    if (noise_q16 == 0) return label;     // the kernels' branch: no draw
+    return action_noise_pick(seed, env_id, (int)agent, clock, (int)noise_q16, (int)label);
 }
 
 int mapf_set_pibt_human_weight(mapf_env *e, int32_t weight) {
@@ -1014,7 +1043,8 @@ int mapf_pibt_human_cells(mapf_env *e, uint32_t *cells, void *stream) {
     return MAPF_OK;
 }
 
-// ROUTE_STEPS: T x (the policy's pick, a committed step), same results as the one-launch kernels.  An
+// ROUTE_STEPS: T x (the policy's pick, with action noise mapf_noise_actions' launch into the handle's row, a
+// committed step), same results as the one-launch kernels.  An
 // observing request's step is step_observe into slot t (or in place; the tape plays row t whatever `slots`
 // says).  A perf request's is a step into the handle's step scratch and the record's accumulate over it.
 // out: the caller's outputs as q.out holds them.
@@ -1030,6 +1060,10 @@ static int rollout_steps(mapf_env *e, const RolloutReq &q, const mapf_step_out *
         const size_t k = (q.slots & 1) ? (size_t)t : 0;
         int32_t *act = q.actions ? q.actions + (q.policy == ROLLOUT_TAPE ? (size_t)t : k) * BN : e->perf_act;
         if (int rc = policy_pick(e, q.policy, act, (hipStream_t)stream)) return rc;
+        if (needs_bfs(q.policy) && e->d.noise_q16 != 0) {      // the label stays in the row picked into; the step plays the scratch row
+            launch_noise_actions(e->d, act, e->noise_act, (hipStream_t)stream);
+            act = e->noise_act;
+        }
         if (perf) {
             if (int rc = step_impl(e, act, &e->perf_step, MAPF_STEP_COMMIT | draw, stream)) return rc;
             launch_perf_accumulate(step_out_of(&e->perf_step), 1, e->d.B, e->d.N, q.perf, t == 0 ? q.accumulate : 1,
@@ -1172,6 +1206,15 @@ int mapf_random_actions(mapf_env *e, int32_t *actions, void *stream) {
     if (!e->ready) return fail(MAPF_ESTATE, "mapf_random_actions before mapf_reset");
     HIPCHK(hipSetDevice(e->device));
     launch_random_actions(e->d, actions, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+int mapf_noise_actions(mapf_env *e, const int32_t *labels, int32_t *played, void *stream) {
+    if (!e || !labels || !played) return fail(MAPF_EINVAL, "null argument");
+    if (!e->ready) return fail(MAPF_ESTATE, "mapf_noise_actions before mapf_reset");
+    HIPCHK(hipSetDevice(e->device));
+    launch_noise_actions(e->d, labels, played, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return MAPF_OK;
 }

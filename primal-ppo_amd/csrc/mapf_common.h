@@ -35,7 +35,7 @@ __host__ __device__ constexpr int opp(int a) { return a == 0 ? 0 : (a == 1 ? 3 :
 
 // Philox purposes (shared spec with oracle/mapf_oracle.c).
 enum : uint32_t { P_ENTRANCE = 1, P_HGOAL0 = 2, P_START = 3, P_GOAL0 = 4, P_GOAL = 5,
-                  P_HGOAL = 6, P_FIX = 7, P_ACT = 8, P_SAMPLE = 9, P_MAPGEN = 10, P_SHUFFLE = 11 };
+                  P_HGOAL = 6, P_FIX = 7, P_ACT = 8, P_SAMPLE = 9, P_MAPGEN = 10, P_SHUFFLE = 11, P_NOISE = 12 };
 
 // counters[] slots
 enum : int { C_BAD_ACTION = 0, C_FIX_BOUND = 1, C_EMPTY_VIABLE = 2, C_FREECELL = 3,
@@ -78,6 +78,9 @@ struct DevEnv {
     const uint8_t *smask;     // [nmaps][H*W]: static-invalid action mask of each cell (getInvalidActions[0])
     int search_blocks;        // workgroups of the observe launch that run search work
     int band_blocks;          // workgroups of the fused launch that write the zero band (0 = none)
+    int noise_q16;            // action noise of the picked policies (mapf_set_action_noise): eps in 1/65536 units,
+                              // 0 = off.  Last, so no other field moves.  The host picks the rollout kernels'
+                              // ROLLOUT_NOISE instantiations from it; the kernels read it as the threshold
 };
 
 static_assert(offsetof(DevEnv, pibt_w) == 116 && offsetof(DevEnv, seed) == 120, "pibt_w fills the hole before seed");
@@ -168,6 +171,53 @@ __host__ __device__ inline int random_action(const u32x4 &o, int i) {
     const uint32_t w = (k >> 1) == 0 ? o.x : (k >> 1) == 1 ? o.y : (k >> 1) == 2 ? o.z : o.w;
     return (int)((((w >> ((k & 1) * 16)) & 0xFFFFu) * (uint32_t)NA) >> 16);
 }
+
+// Action noise on a picked policy's rollouts (include/mapf.h: mapf_set_action_noise has the
+// specification): the label stays the policy's pick, the action played is, with probability
+// noise_q16 / 65536, the uniform random policy's for that agent and clock.  One Philox draw of purpose
+// P_NOISE serves the 8 agents of a draw group as P_ACT's does, agent i taking half-word i & 7; the random
+// action's draw is made only where an agent of the group is noisy.  A launch without noise makes no draw:
+// the rollout kernels with noise are instantiations of their own (mapf_kernels.h: ROLLOUT_NOISE), and
+// noise_actions_kernel branches on the kernel argument.  noise_draw, noise_hit and random_action are the
+// functions every kernel and the host export run.
+__host__ __device__ inline uint32_t philox_half(const u32x4 &o, int i) {      // random_action's half-word
+    const int k = i & 7;
+    const uint32_t w = (k >> 1) == 0 ? o.x : (k >> 1) == 1 ? o.y : (k >> 1) == 2 ? o.z : o.w;
+    return (w >> ((k & 1) * 16)) & 0xFFFFu;
+}
+// the draw of purpose `purpose` (P_NOISE: explore, P_ACT: the random policy's actions) for draw group `group`
+__host__ __device__ inline u32x4 noise_draw(uint64_t seed, uint32_t env_id, uint32_t purpose, int group, uint32_t clock) {
+    return philox_hd(env_id, purpose | ((uint32_t)group << 8), clock, 0u, seed);
+}
+__host__ __device__ inline bool noise_hit(const u32x4 &explore, int agent, int noise_q16) {
+    return philox_half(explore, agent) < (uint32_t)noise_q16;
+}
+// one agent, sequentially (mapf_action_noise_pick, noise_actions_kernel)
+__host__ __device__ inline int action_noise_pick(uint64_t seed, uint32_t env_id, int agent, uint32_t clock,
+                                                 int noise_q16, int label) {
+    if (!noise_hit(noise_draw(seed, env_id, P_NOISE, agent >> 3, clock), agent, noise_q16)) return label;
+    return random_action(noise_draw(seed, env_id, P_ACT, agent >> 3, clock), agent);
+}
+#if defined(__HIPCC__)
+// One env's agents on the lanes of a wave (the persistent rollout kernels): `on` = this lane holds agent
+// `agent` (< N) and its label a; returns what the lane plays.  Env and clock are the wave's, so the draws
+// are wave-uniform: made scalar (readfirstlane), they run on the scalar unit, group by group -- a few
+// VGPRs for the half-word's select, where ten rounds of per-lane Philox held ten at the kernels' fullest
+// point.  Any `on` lane may ask; every lane of the wave that is active runs the loop.
+__device__ inline int noise_play_wave(uint64_t seed, uint32_t env_id, uint32_t clock, int noise_q16, int N, bool on,
+                                      int agent, int a) {
+    const uint32_t env_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)env_id);
+    const uint32_t clock_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)clock);
+    for (int g = 0; g * 8 < N; ++g) {
+        const bool hit = on && (agent >> 3) == g && noise_hit(noise_draw(seed, env_s, P_NOISE, g, clock_s), agent, noise_q16);
+        if (__ballot(hit)) {                 // a scalar branch: the second draw only for a group with a noisy agent
+            const int r = random_action(noise_draw(seed, env_s, P_ACT, g, clock_s), agent);
+            a = hit ? r : a;
+        }
+    }
+    return a;
+}
+#endif
 
 // LDS-typed pointers.  A pointer the compiler cannot prove to be LDS is generic and its
 // accesses compile to flat_* instructions, which also count in vmcnt: a flat read of LDS

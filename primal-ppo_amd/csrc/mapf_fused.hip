@@ -261,13 +261,14 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
 #else
     DevEnv e, int T, RolloutOut ro) {
 #endif
-    using RO = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibt, RolloutOut>;     // RolloutOut: never PIBT here
+    using RO = std::conditional_t<rollout_pol(POL) == ROLLOUT_PIBT, RolloutOutPibt, RolloutOut>;     // RolloutOut: never PIBT here
     constexpr bool PERF = false;
 #include "mapf_fused_rollout.inc"
 }
 // the PIBT form: the same loop, a kernel of its own because its arguments differ (RolloutOutPibt);
 // the plan text names it by the form it shares, rollout_random_kernel<..,pibt>
-template <int ST, int SUBS, int BAND>
+// NOISY: the form with action noise (ROLLOUT_PIBT | ROLLOUT_NOISE), a symbol of its own
+template <int ST, int SUBS, int BAND, bool NOISY = false>
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_random_pibt_kernel(
 #if MAPF_ARGS_PTR
     const RolloutArgsPibt *__restrict__ args, int T) {
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
 #else
     DevEnv e, int T, RolloutOutPibt ro) {
 #endif
-    constexpr int POL = ROLLOUT_PIBT;
+    constexpr int POL = ROLLOUT_PIBT | (NOISY ? ROLLOUT_NOISE : 0);
     using RO = RolloutOutPibt;
     constexpr bool PERF = false;
 #include "mapf_fused_rollout.inc"
@@ -285,13 +286,13 @@ __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4)))
 template <int SUBS, int POL>
 __global__ __launch_bounds__(256 * SUBS) __attribute__((amdgpu_waves_per_eu(4))) void rollout_sparse_kernel(
 #if MAPF_ARGS_PTR
-    const RolloutArgsOf<std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse>> *__restrict__ args, int T) {
+    const RolloutArgsOf<std::conditional_t<rollout_pol(POL) == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse>> *__restrict__ args, int T) {
     const DevEnv &e = args->e;
     const auto &ro = args->ro;
 #else
-    DevEnv e, int T, std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse> ro) {
+    DevEnv e, int T, std::conditional_t<rollout_pol(POL) == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse> ro) {
 #endif
-    using RO = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse>;
+    using RO = std::conditional_t<rollout_pol(POL) == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse>;
     constexpr int ST = OBS_NT, BAND = OBS_SPARSE;
     constexpr bool PERF = false;
 #include "mapf_fused_rollout.inc"
@@ -309,7 +310,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void r
 }
 template <int ST, int SUBS, int BAND, int POL>
 constexpr auto rollout_kernel_fn() {
-    if constexpr (POL == ROLLOUT_PIBT) return &rollout_random_pibt_kernel<ST, SUBS, BAND>;
+    if constexpr (rollout_pol(POL) == ROLLOUT_PIBT) return &rollout_random_pibt_kernel<ST, SUBS, BAND, rollout_pol_noise(POL)>;
     else return &rollout_random_kernel<ST, SUBS, BAND, POL>;
 }
 
@@ -409,8 +410,9 @@ void describe_rollout_random(const DevEnv &e, const RolloutReq &q, const mapf_tu
     if (f.band) std::snprintf(band_tag, sizeof band_tag, ",band%d", MAPF_BAND_UNIT);
     if (f.sparse) std::snprintf(band_tag, sizeof band_tag, ",sparse%d", OBS_SPARSE_PIECE * 4);
     if (f.bits) std::snprintf(band_tag, sizeof band_tag, ",bits");
-    const int k = std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
-                                slots ? "true" : "false", p.subs, band_tag, rollout_policy_tag(policy), p.grid, 256 * p.subs,
+    const int k = std::snprintf(buf, n, "rollout_random_kernel<%s,%d%s%s%s> grid=%d block=%d lds=%zu fair=%d slack=%d remap=%d",
+                                slots ? "true" : "false", p.subs, band_tag, rollout_policy_tag(policy),
+                                rollout_noise_tag(rollout_noisy(e, policy)), p.grid, 256 * p.subs,
                                 p.lds, p.subs > 1 ? p.fair : 0, p.subs > 1 ? p.slack : -1, p.remap);
     if (k > 0 && (size_t)k < n) {
         if (policy == ROLLOUT_TAPE)
@@ -447,15 +449,15 @@ int launch_rollout_random(const DevEnv &e, const RolloutReq &q, const mapf_tunin
     };
     return with_policy(q.policy, [&](auto pol) -> int {
         constexpr int POL = decltype(pol)::value;
-        using RO = std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibt, RolloutOut>;
+        using RO = std::conditional_t<rollout_pol(POL) == ROLLOUT_PIBT, RolloutOutPibt, RolloutOut>;
         RO ro{};
         static_cast<RolloutOut &>(ro) = ro0;
-        if constexpr (POL == ROLLOUT_PIBT) {
+        if constexpr (rollout_pol(POL) == ROLLOUT_PIBT) {
             ro.pibt_seen = q.pibt_seen;
             ro.pibt_since = q.pibt_since;
         }
         if (f.sparse) {
-            std::conditional_t<POL == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse> rs{};
+            std::conditional_t<rollout_pol(POL) == ROLLOUT_PIBT, RolloutOutPibtSparse, RolloutOutSparse> rs{};
             static_cast<RO &>(rs) = ro;
             rs.shadow = q.shadow;
             rs.valid = q.valid;
@@ -468,7 +470,7 @@ int launch_rollout_random(const DevEnv &e, const RolloutReq &q, const mapf_tunin
         if (p.subs == 4)
             return slots ? launch(rollout_kernel_fn<true, 4, false, POL>(), ro) : launch(rollout_kernel_fn<false, 4, false, POL>(), ro);
         return slots ? launch(rollout_kernel_fn<true, 1, false, POL>(), ro) : launch(rollout_kernel_fn<false, 1, false, POL>(), ro);
-    });
+    }, rollout_noisy(e, q.policy));
 }
 
 // ROLLOUT_PERF requests on the pair-lane kernel, never grouped.  The form's own request: map rows, search
@@ -486,8 +488,8 @@ static RolloutPlan plan_rollout_perf(const DevEnv &e, const mapf_tuning &tu, int
 
 void describe_rollout_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n) {
     const RolloutPlan p = plan_rollout_perf(e, tu, q.policy);
-    std::snprintf(buf, n, "rollout_random_kernel<1%s,perf> grid=%d block=256 lds=%zu remap=%d", rollout_policy_tag(q.policy),
-                  p.grid, p.lds, p.remap);
+    std::snprintf(buf, n, "rollout_random_kernel<1%s,perf%s> grid=%d block=256 lds=%zu remap=%d", rollout_policy_tag(q.policy),
+                  rollout_noise_tag(rollout_noisy(e, q.policy)), p.grid, p.lds, p.remap);
 }
 
 int launch_rollout_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, ArgRing &, hipStream_t s) {
@@ -501,7 +503,7 @@ int launch_rollout_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning 
     return with_policy(q.policy, [&](auto pol) -> int {
         hipLaunchKernelGGL(rollout_perf_kernel<decltype(pol)::value>, dim3(p.grid), dim3(256), p.lds, s, e, q.T, ro);
         return MAPF_OK;
-    });
+    }, rollout_noisy(e, q.policy));
 }
 
 bool step_observe_fusable(const DevEnv &e) {

@@ -7,7 +7,8 @@
 // the wave's record (PerfAcc, mapf_perf.h), which is stored once after the loop.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int E = 4;                     // envs per workgroup, one per wave
-    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT, PIBT = POL == ROLLOUT_PIBT;
+    constexpr bool TAPE = rollout_pol(POL) == ROLLOUT_TAPE, DESCENT = rollout_pol(POL) == ROLLOUT_DESCENT, PIBT = rollout_pol(POL) == ROLLOUT_PIBT;
+    constexpr bool NOISE = rollout_pol_noise(POL);      // DESCENT / PIBT with action noise: an instantiation of its own
     // XCD-aware env order: workgroups are dealt round-robin over the 8 XCDs, so workgroup w
     // takes env block (w % 8) * (grid / 8) + w / 8 -- each XCD owns one contiguous range of
     // envs, and the output lines that several envs share (status: 16 envs per 128-B line)
@@ -152,12 +153,18 @@
                 int lane = (int)(threadIdx.x & 63);
                 asm volatile("" : "+v"(lane));          // addresses stay out of the loop's invariants (as the tape's)
                 const int i = lane >> 3;
-                if ((lane & 7) == 0 && i < E.N) {
+                const bool head = (lane & 7) == 0 && i < E.N;
+                int a = 0;
+                if (head) {
                     const size_t ai = (size_t)(b0 + le) * E.N + i;
-                    const int a = descent_action(E, E.bfs + ai * bfs_cells(E.H, E.W), rs.pi, rs.clock, i);
-                    as_lds(trow)[i] = a;
+                    a = descent_action(E, E.bfs + ai * bfs_cells(E.H, E.W), rs.pi, rs.clock, i);
                     if (!PERF || R.actions) R.actions[s * BN + ai] = a;      // PERF: no actions asked for, none stored
                 }
+                // action noise: the label is stored, the step reads `played` from the row (N <= 8: one draw
+                // group, env and clock the wave's)
+                if constexpr (NOISE)
+                    a = noise_play_wave(E.seed, E.env_offset + (uint32_t)(b0 + le), rs.clock, E.noise_q16, E.N, head, i, a);
+                if (head) as_lds(trow)[i] = a;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -183,11 +190,11 @@
                             (int)human_ahead(as_lds(rs.lp), rs.hs, rs.hcur ? rs.hlen1 : rs.hlen0, j));
                     });
                 }
-                const int a = pibt_solve_wave<8>(E.N, lane, head ? rs.pi : NO_CELL, cand, age);
-                if (head) {
-                    as_lds(trow)[i] = a;
-                    if (!PERF || R.actions) R.actions[s * BN + ai] = a;
-                }
+                int a = pibt_solve_wave<8>(E.N, lane, head ? rs.pi : NO_CELL, cand, age);
+                if (head && (!PERF || R.actions)) R.actions[s * BN + ai] = a;
+                if constexpr (NOISE)         // as descent's
+                    a = noise_play_wave(E.seed, E.env_offset + (uint32_t)(b0 + le), rs.clock, E.noise_q16, E.N, head, i, a);
+                if (head) as_lds(trow)[i] = a;
             }
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();

@@ -67,6 +67,8 @@ void launch_step(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t
 bool launch_step_pairs(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t flags, int slot,
                        hipStream_t s);   // N <= 8: one lane per agent pair; false if N > 8
 void launch_random_actions(const DevEnv &e, int32_t *actions, hipStream_t s);
+// action noise over a row of labels [B][N] at the envs' clocks (mapf_noise_actions); played may be labels
+void launch_noise_actions(const DevEnv &e, const int32_t *labels, int32_t *played, hipStream_t s);
 // the descent policy's actions from the state and the tiled BFS maps (keep_bfs; mapf_descent_actions)
 void launch_descent_actions(const DevEnv &e, int32_t *actions, hipStream_t s);
 // the PIBT policy's actions from the state, the tiled BFS maps and the handle's age arrays seen /
@@ -108,9 +110,24 @@ void launch_step_observe(const DevEnv &e, int32_t *actions, const StepOut &out, 
 // kernels take the handle's age arrays in argument types of their own and are therefore symbols of their
 // own over the shared bodies: rollout_random_pibt_kernel, rollout_wide_pibt_kernel, rollout_wide3_pibt_kernel.
 constexpr int ROLLOUT_RANDOM = 0, ROLLOUT_TAPE = 1, ROLLOUT_DESCENT = 2, ROLLOUT_PIBT = 3;
+// Action noise (mapf_set_action_noise) is a bit of the kernels' POL alone, never of a caller's policy:
+// ROLLOUT_DESCENT / ROLLOUT_PIBT | ROLLOUT_NOISE are instantiations of their own, launched while the
+// handle's noise_q16 is above 0, so the kernels of a launch without noise are the kernels of a build
+// without the feature, register for register (DESIGN.md 9p has both placements' resource tables).  The
+// PIBT kernels, symbols of their own, take it as a trailing bool.  The plan text carries ",noise" before
+// the closing bracket.
+constexpr int ROLLOUT_NOISE = 4;
+constexpr int rollout_pol(int POL) { return POL & 3; }
+constexpr bool rollout_pol_noise(int POL) { return (POL & ROLLOUT_NOISE) != 0; }
+inline bool rollout_noisy(const DevEnv &e, int policy) {
+    return e.noise_q16 != 0 && (policy == ROLLOUT_DESCENT || policy == ROLLOUT_PIBT);
+}
+inline const char *rollout_noise_tag(bool noisy) { return noisy ? ",noise" : ""; }
 // f(std::integral_constant<int, policy>{}): the runtime policy as a template argument
 template <class F>
-inline auto with_policy(int policy, F f) {
+inline auto with_policy(int policy, F f, bool noisy = false) {       // noisy: rollout_noisy() of the launch
+    if (noisy && policy == ROLLOUT_PIBT) return f(std::integral_constant<int, ROLLOUT_PIBT | ROLLOUT_NOISE>{});
+    if (noisy && policy == ROLLOUT_DESCENT) return f(std::integral_constant<int, ROLLOUT_DESCENT | ROLLOUT_NOISE>{});
     if (policy == ROLLOUT_PIBT) return f(std::integral_constant<int, ROLLOUT_PIBT>{});
     if (policy == ROLLOUT_DESCENT) return f(std::integral_constant<int, ROLLOUT_DESCENT>{});
     if (policy == ROLLOUT_TAPE) return f(std::integral_constant<int, ROLLOUT_TAPE>{});

@@ -69,8 +69,8 @@ struct WideArgsPibt {
     DevEnv e;
     WideOutPibt ro;
 };
-template <int POL> using wide_out_t = std::conditional_t<POL == ROLLOUT_PIBT, WideOutPibt, WideOut>;
-template <int POL> using wide_args_t = std::conditional_t<POL == ROLLOUT_PIBT, WideArgsPibt, WideArgs>;
+template <int POL> using wide_out_t = std::conditional_t<rollout_pol(POL) == ROLLOUT_PIBT, WideOutPibt, WideOut>;
+template <int POL> using wide_args_t = std::conditional_t<rollout_pol(POL) == ROLLOUT_PIBT, WideArgsPibt, WideArgs>;
 
 __host__ __device__ inline size_t wide_a16(size_t x) { return (x + 15) & ~(size_t)15; }
 
@@ -215,7 +215,7 @@ __device__ inline void wide_plain_barrier() {
 // -- the three-wave in-place form's last-step re-store included -- is the packed one.
 template <class T, int RW, int ST, int POL>     // POL: ROLLOUT_RANDOM / ROLLOUT_TAPE / ROLLOUT_DESCENT / ROLLOUT_PIBT
 __device__ __attribute__((always_inline)) inline void rollout_wide_body(const DevEnv &e, int T_steps, const wide_out_t<POL> &ro) {
-    constexpr bool TAPE = POL == ROLLOUT_TAPE, DESCENT = POL == ROLLOUT_DESCENT, PIBT = POL == ROLLOUT_PIBT;
+    constexpr bool TAPE = rollout_pol(POL) == ROLLOUT_TAPE, DESCENT = rollout_pol(POL) == ROLLOUT_DESCENT, PIBT = rollout_pol(POL) == ROLLOUT_PIBT;
     constexpr bool PICKS = DESCENT || PIBT;          // the stepping wave picks from the BFS maps
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // XCD-aware env order (as the pair-lane rollout): workgroups are dealt round-robin
@@ -495,25 +495,26 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void r
 // The PIBT forms of the two kernels: the same body with ROLLOUT_PIBT, kernels of their own because
 // their arguments differ (WideOutPibt).  The plan text names them by the form they share,
 // rollout_wide_kernel<..,pibt> / rollout_wide3_kernel<..,pibt>.
-template <class T, int RW, int ST>
+// NOISE: the form with action noise (ROLLOUT_PIBT | ROLLOUT_NOISE), a symbol of its own.
+template <class T, int RW, int ST, bool NOISE = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2))) void rollout_wide_pibt_kernel(WIDE_PIBT_PARAMS) {
     WIDE_BIND
-    rollout_wide_body<T, RW, ST, ROLLOUT_PIBT>(e, T_steps, ro);
+    rollout_wide_body<T, RW, ST, ROLLOUT_PIBT | (NOISE ? ROLLOUT_NOISE : 0)>(e, T_steps, ro);
 }
-template <class T, int RW, int ST>
+template <class T, int RW, int ST, bool NOISE = false>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void rollout_wide3_pibt_kernel(
     const WideArgsPibt *__restrict__ args, int T_steps) {
-    rollout_wide_body<T, RW, ST, ROLLOUT_PIBT>(args->e, T_steps, args->ro);
+    rollout_wide_body<T, RW, ST, ROLLOUT_PIBT | (NOISE ? ROLLOUT_NOISE : 0)>(args->e, T_steps, args->ro);
 }
 // the kernel of a policy and store form
 template <class T, int RW, int ST, int POL>
 constexpr auto wide_kernel_fn() {
-    if constexpr (POL == ROLLOUT_PIBT) return &rollout_wide_pibt_kernel<T, RW, ST>;
+    if constexpr (rollout_pol(POL) == ROLLOUT_PIBT) return &rollout_wide_pibt_kernel<T, RW, ST, rollout_pol_noise(POL)>;
     else return &rollout_wide_kernel<T, RW, ST, POL>;
 }
 template <class T, int RW, int ST, int POL>
 constexpr auto wide3_kernel_fn() {
-    if constexpr (POL == ROLLOUT_PIBT) return &rollout_wide3_pibt_kernel<T, RW, ST>;
+    if constexpr (rollout_pol(POL) == ROLLOUT_PIBT) return &rollout_wide3_pibt_kernel<T, RW, ST, rollout_pol_noise(POL)>;
     else return &rollout_wide3_kernel<T, RW, ST, POL>;
 }
 // ... of a policy and a plan's store form (bits, else nt): the three-wave kernel (WPE3) or the other
@@ -576,7 +577,7 @@ static WidePlan plan_wide_t(const DevEnv &e, int slots, const mapf_tuning &tu) {
     r.slots = slots;
     r.xcd_remap = tu.xcd_remap != 0;
     r.prio = tu.wide_prio;
-    r.bfsobs = POL == ROLLOUT_DESCENT || POL == ROLLOUT_PIBT ? 0 : tu.wide_bfsobs;   // descent, PIBT: the stepping wave reads the maps it rebuilt
+    r.bfsobs = rollout_pol(POL) == ROLLOUT_DESCENT || rollout_pol(POL) == ROLLOUT_PIBT ? 0 : tu.wide_bfsobs;   // descent, PIBT: the stepping wave reads the maps it rebuilt
     r.grid = 0;
     if (!pipe && wide_grid_bytes(e) <= wide_scratch_bytes<T, RW>(e)) r.grid = 2;
     else if (wide_lds_bytes<T, RW>(e, 1) <= (occ > 1 ? cap : (size_t)64 * 1024)) r.grid = 1;
@@ -636,7 +637,7 @@ static int launch_wide_t(const DevEnv &e, const RolloutReq &q, const mapf_tuning
     const WidePlan p = plan_wide_t<T, RW, POL>(e, q.slots, tu);
     wide_out_t<POL> r{};
     static_cast<WideOut &>(r) = p.r;
-    if constexpr (POL == ROLLOUT_PIBT) {
+    if constexpr (rollout_pol(POL) == ROLLOUT_PIBT) {
         r.pibt_seen = q.pibt_seen;
         r.pibt_since = q.pibt_since;
     }
@@ -691,8 +692,8 @@ struct WidePerfOut : WideOutPibt {
 template <class T, int RW, int POL>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void rollout_wide_perf_kernel(DevEnv e, int T_steps,
                                                                                                       WidePerfOut ro) {
-    constexpr bool TAPE = POL == ROLLOUT_TAPE, PIBT = POL == ROLLOUT_PIBT;
-    constexpr bool PICKS = POL == ROLLOUT_DESCENT || PIBT;
+    constexpr bool TAPE = rollout_pol(POL) == ROLLOUT_TAPE, PIBT = rollout_pol(POL) == ROLLOUT_PIBT;
+    constexpr bool PICKS = rollout_pol(POL) == ROLLOUT_DESCENT || PIBT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nb = (int)gridDim.x;
     const int b = (ro.xcd_remap && (nb & 7) == 0) ? ((int)blockIdx.x & 7) * (nb >> 3) + ((int)blockIdx.x >> 3)
@@ -782,7 +783,8 @@ int launch_rollout_wide(const DevEnv &e, const RolloutReq &q, const mapf_tuning 
     return with_row_type(e, [&](auto t, auto rw) {
         using R = decltype(t);
         constexpr int RWV = decltype(rw)::value;
-        return with_policy(q.policy, [&](auto pol) { return launch_wide_t<R, RWV, decltype(pol)::value>(e, q, tu, ring, s); });
+        return with_policy(q.policy, [&](auto pol) { return launch_wide_t<R, RWV, decltype(pol)::value>(e, q, tu, ring, s); },
+                           rollout_noisy(e, q.policy));
     });
 }
 
@@ -791,12 +793,13 @@ void describe_rollout_wide(const DevEnv &e, const RolloutReq &q, const mapf_tuni
     with_row_type(e, [&](auto t, auto rw) {
         using R = decltype(t);
         constexpr int RWV = decltype(rw)::value;
-        const WidePlan p = with_policy(policy, [&](auto pol) { return plan_wide_t<R, RWV, decltype(pol)::value>(e, q.slots, tu); });
-        std::snprintf(buf, n, "%s<%s,%d,%s%s%s> grid=%d block=%d lds=%zu wpe=%d epw=%d grid_mode=%d overlap=%d slack=%d "
+        const WidePlan p = with_policy(policy, [&](auto pol) { return plan_wide_t<R, RWV, decltype(pol)::value>(e, q.slots, tu); },
+                                       rollout_noisy(e, policy));
+        std::snprintf(buf, n, "%s<%s,%d,%s%s%s%s> grid=%d block=%d lds=%zu wpe=%d epw=%d grid_mode=%d overlap=%d slack=%d "
                               "fair=%d prio=%d bfsobs=%d pair=%d remap=%d",
                       p.r.wpe == 3 ? "rollout_wide3_kernel" : "rollout_wide_kernel", row_name<decltype(t)>(),
                       (int)decltype(rw)::value, p.nt ? "true" : "false", p.bits ? ",bits" : "",
-                      rollout_policy_tag(policy), p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
+                      rollout_policy_tag(policy), rollout_noise_tag(rollout_noisy(e, policy)), p.grid, p.block, p.lds, p.r.wpe, p.r.epw,
                       p.r.grid, p.r.overlap, p.r.slack, p.r.fair, p.r.prio, p.r.bfsobs, p.r.pair, p.r.xcd_remap);
         return 0;
     });
@@ -833,15 +836,16 @@ int launch_rollout_wide_perf(const DevEnv &e, const RolloutReq &q, const mapf_tu
         return with_policy(q.policy, [&](auto pol) -> int {
             hipLaunchKernelGGL((rollout_wide_perf_kernel<R, RWV, decltype(pol)::value>), dim3(e.B), dim3(64), p.lds, s, e, q.T, ro);
             return MAPF_OK;
-        });
+        }, rollout_noisy(e, q.policy));
     });
 }
 
 void describe_rollout_wide_perf(const DevEnv &e, const RolloutReq &q, const mapf_tuning &tu, char *buf, size_t n) {
     with_row_type(e, [&](auto t, auto rw) {
         const WidePerfPlan p = plan_wide_perf_t<decltype(t), decltype(rw)::value>(e, tu);
-        std::snprintf(buf, n, "rollout_wide_kernel<%s,%d%s,perf> grid=%d block=64 lds=%zu wpe=1 epw=1 grid_mode=%d remap=%d",
-                      row_name<decltype(t)>(), (int)decltype(rw)::value, rollout_policy_tag(q.policy), e.B, p.lds,
+        std::snprintf(buf, n, "rollout_wide_kernel<%s,%d%s,perf%s> grid=%d block=64 lds=%zu wpe=1 epw=1 grid_mode=%d remap=%d",
+                      row_name<decltype(t)>(), (int)decltype(rw)::value, rollout_policy_tag(q.policy),
+                      rollout_noise_tag(rollout_noisy(e, q.policy)), e.B, p.lds,
                       p.grid_mode, p.remap);
         return 0;
     });

@@ -145,14 +145,17 @@ struct StepSrc {
 // action itself (descent_action() over its tiled BFS map) and stores it to `actions`; `flags` bit 1
 // is then not looked at.  POL = ROLLOUT_PIBT (its PIBT launches, REGS and the env the whole wave):
 // the wave picks with the PIBT solve (mapf_pibt.h) from the same five cells per lane, the env's
-// human cells and the age pair in rg, and stores the picks likewise.  Any other POL: the actions
+// human cells and the age pair in rg, and stores the picks likewise.  Either | ROLLOUT_NOISE: the
+// stored pick is the label and the step plays noise_play_wave()'s action.  Any other POL: the actions
 // come from `flags` bit 1 or the caller.
 template <class Grp, bool REGS = false, bool LANEPTR = false, int POL = ROLLOUT_RANDOM, bool PERF = false>
 __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e, int32_t *__restrict__ actions,
                                                                 const StepOut &out, uint32_t flags, int parity, int b,
                                                                 const Grp &g, StepInline *inl, StepSrc src,
                                                                 StepRegs &rg, uint32_t have = 0, StepVals *pv = nullptr) {
-    constexpr bool DESCENT = POL == ROLLOUT_DESCENT, PIBT = POL == ROLLOUT_PIBT;
+    constexpr bool DESCENT = rollout_pol(POL) == ROLLOUT_DESCENT, PIBT = rollout_pol(POL) == ROLLOUT_PIBT;
+    constexpr bool NOISE = rollout_pol_noise(POL);      // the launch's handle has action noise above 0
+    static_assert(!NOISE || (REGS && std::is_same<Grp, WaveGroup>::value), "noise_play_wave's draws are the wave's");
     static_assert(!PIBT || (REGS && std::is_same<Grp, WaveGroup>::value), "the PIBT solve runs on a whole wave");
     const int N = e.N;
     STAMP_BEGIN();
@@ -241,6 +244,9 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
             a = descent_action(e, e.bfs + ai * bfs_cells(e.H, e.W), pp, clock, i);
             if (!PERF || actions) actions[oi] = a;      // PERF: a caller that takes no actions passes none
         }
+        // action noise: the label is stored, the step plays `played` (lane = agent: the draw group i >> 3
+        // differs across lanes); an instantiation of its own, so nothing of it is in a launch without noise
+        if constexpr (NOISE) a = noise_play_wave(e.seed, env_id, clock, e.noise_q16, N, act, i, a);
     } else if constexpr (PIBT) {
         // The map cells load where descent's do, under the same visibility rule (the caller
         // searches the maps it reads: bfsobs = 0).  The static mask comes from the LDS rows, as
@@ -261,6 +267,7 @@ __device__ __attribute__((always_inline)) inline void step_group(const DevEnv &e
         }
         a = pibt_solve_wave(N, i, pp, cand, age);     // every lane: pp is NO_CELL past N
         if (act && (!PERF || actions)) actions[oi] = a;
+        if constexpr (NOISE) a = noise_play_wave(e.seed, env_id, clock, e.noise_q16, N, act, i, a);      // as descent's
     } else
     if (flags & 2u) {          // random policy fused in: same stream as random_actions_kernel
         if (act) {

@@ -28,6 +28,18 @@ __global__ __launch_bounds__(256) void random_actions_kernel(DevEnv e, int32_t *
     actions[t] = (int32_t)random_action(o, i);
 }
 
+// Action noise over a row of labels (action_noise_pick(), mapf_noise_actions), one lane per agent:
+// played[t] from labels[t] at the env's clock; at noise 0 a copy (a scalar branch: no draw).  Not
+// __restrict__: played may be labels, each lane then reads its own element before it writes it.
+__global__ __launch_bounds__(256) void noise_actions_kernel(DevEnv e, const int32_t *labels, int32_t *played) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= e.B * e.N) return;
+    const int b = t / e.N, i = t - b * e.N;
+    int a = labels[t];
+    if (e.noise_q16 != 0) a = action_noise_pick(e.seed, e.env_offset + (uint32_t)b, i, e.clock[b], e.noise_q16, a);
+    played[t] = a;
+}
+
 // The descent policy (descent_action(): every agent one step down its own BFS map), one lane per
 // agent: its cell, the env's clock, then its five map cells.
 __global__ __launch_bounds__(256) void descent_actions_kernel(DevEnv e, int32_t *__restrict__ actions) {
@@ -48,6 +60,11 @@ void launch_step(const DevEnv &e, int32_t *actions, const StepOut &out, uint32_t
 void launch_random_actions(const DevEnv &e, int32_t *actions, hipStream_t s) {
     const int n = e.B * e.N;
     hipLaunchKernelGGL(random_actions_kernel, dim3((n + 255) / 256), dim3(256), 0, s, e, actions);
+}
+
+void launch_noise_actions(const DevEnv &e, const int32_t *labels, int32_t *played, hipStream_t s) {
+    const int n = e.B * e.N;
+    hipLaunchKernelGGL(noise_actions_kernel, dim3((n + 255) / 256), dim3(256), 0, s, e, labels, played);
 }
 
 void launch_descent_actions(const DevEnv &e, int32_t *actions, hipStream_t s) {

@@ -123,6 +123,10 @@ SIGNATURES = {
     "mapf_get_pibt_human_horizon": (ctypes.c_int, [P]),
     "mapf_pibt_human_cells": (ctypes.c_int, [P, P, P]),
     "mapf_pibt_w_word": (ctypes.c_int, [I32, I32, I32, I32, P]),
+    "mapf_set_action_noise": (ctypes.c_int, [P, I32]),
+    "mapf_get_action_noise": (ctypes.c_int, [P]),
+    "mapf_noise_actions": (ctypes.c_int, [P, P, P, P]),
+    "mapf_action_noise_pick": (ctypes.c_int, [ctypes.c_uint64, U32, I32, U32, I32, I32]),
     "mapf_flush": (ctypes.c_int, [P, P]),
     "mapf_release_captures": (ctypes.c_int, [P]),
     "mapf_random_actions": (ctypes.c_int, [P, P, P]),

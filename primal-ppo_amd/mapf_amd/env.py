@@ -62,6 +62,33 @@ def _policy_symbols(policy):
     return ROLLOUT_POLICIES[policy]
 
 
+def noise_q16(eps=None, q16=None):
+    """Action noise as the library takes it (mapf_set_action_noise): eps, a float in [0, 1], gives
+    round(eps * 65536); or q16=, the integer in 0..65536, directly."""
+    if (eps is None) == (q16 is None):
+        raise ValueError("action noise: give eps or q16=, one of them")
+    if q16 is not None:
+        if isinstance(q16, bool) or not isinstance(q16, (int, np.integer)):
+            raise TypeError(f"action noise q16: expected an int in 0..65536, got {type(q16).__name__}")
+        if not 0 <= int(q16) <= 65536:
+            raise ValueError(f"action noise q16 must be in 0..65536, got {int(q16)}")
+        return int(q16)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise TypeError(f"action noise eps: expected a float in [0, 1], got {type(eps).__name__}")
+    if not 0.0 <= float(eps) <= 1.0:        # (NaN fails both)
+        raise ValueError(f"action noise eps must be in [0, 1], got {eps!r}")
+    return int(round(float(eps) * 65536))
+
+
+def _check_noise_policy(policy, noise):
+    """noise= of a rollout call: None, or an eps for the picked policies; returns its q16 (None: leave alone)."""
+    if noise is None:
+        return None
+    if policy not in ("descent", "pibt"):
+        raise ValueError(f"noise= goes with policy 'descent' or 'pibt', not {policy!r}")
+    return noise_q16(noise)
+
+
 # mapf_rollout_sparse's policy argument (include/mapf.h)
 SPARSE_POLICY = {"random": 0, "tape": 1, "descent": 2, "pibt": 3}
 
@@ -415,7 +442,7 @@ class BatchedMapfGym:
         return (self.out if out is None else out), obs, vec
 
     def rollout(self, T=None, policy="random", *, slots=False, actions=None, tape=None, obs=None, vec=None, out=None,
-                band_clean=False, obs_bits=False):
+                band_clean=False, obs_bits=False, noise=None):
         """T x (the policy's actions, step_observe) -- runner.py:64-100, T times -- as ONE launch where
         rollout_fused (each wave owns an env and loops step -> observe -> its search work; the kernel
         is rollout_plan(policy=...)), else per-step launches; identical results.  policy:
@@ -434,8 +461,12 @@ class BatchedMapfGym:
         buffer without it; the launch then need not store it (MAPF_SLOTS_BAND_CLEAN, mapf.h).
         obs_bits: `obs` is the packed observation buffer, int32 [T, B, N, WPA] (slots) or [B, N, WPA]
         (default: this env's own), one bit per cell (MAPF_SLOTS_OBS_BITS; band_clean is then ignored).
+        noise ("descent" / "pibt" only, ValueError otherwise): an eps in [0, 1] set on the handle before
+        the launch (set_action_noise); None leaves the handle's setting alone.  `actions` keeps the
+        policy's picks, the labels; the steps play the noisy actions.
         Returns (out, obs, vec)."""
         symbol = _policy_symbols(policy)[0]
+        q16 = _check_noise_policy(policy, noise)
         if policy == "tape":
             n = self._check_tape(tape)
             if T is not None and int(T) != n:
@@ -449,6 +480,8 @@ class BatchedMapfGym:
                 raise ValueError("T must be >= 0")
         actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
                                                            tape=tape, obs_bits=obs_bits)
+        if q16 is not None:
+            self.set_action_noise(q16=q16)
         if T == 0 and policy != "random":   # nothing to play (an empty tensor has no address to hand over)
             return out, obs, vec
         _sparse_forget(obs)
@@ -545,15 +578,16 @@ class BatchedMapfGym:
                                                   _ptr(obs), _ptr(vec), _ptr(shadow), int(valid), _stream(self.device)))
         return out, obs, vec
 
-    def rollout_perf(self, T=None, policy="random", *, tape=None, actions=None, perf=None, accumulate=False):
+    def rollout_perf(self, T=None, policy="random", *, tape=None, actions=None, perf=None, accumulate=False, noise=None):
         """mapf_rollout_perf (mapf.h): T committed steps under `policy` (rollout's names; T / tape as there) in
         one launch that writes only the episode metrics -- no observation, no vec, no step output.  Returns
         perf, int32 [B, 8] on the device (perf_dict names the columns; the two float columns hold float32
         bits), newly allocated if None.  accumulate: continue from what `perf` holds (the float sums go on
         in order: any chunking of an episode gives the bits of one launch).  actions: None, or int32
-        [T, B, N] receiving the drawn / chosen actions (not used under "tape").  The handle ends exactly as
-        after rollout(T, policy, ...)."""
+        [T, B, N] receiving the drawn / chosen actions (not used under "tape").  noise: as rollout()'s.  The
+        handle ends exactly as after rollout(T, policy, ...)."""
         _policy_symbols(policy)
+        q16 = _check_noise_policy(policy, noise)
         if policy == "tape":
             n = self._check_tape(tape)
             if T is not None and int(T) != n:
@@ -573,6 +607,8 @@ class BatchedMapfGym:
             perf = torch.zeros(self.B, 8, dtype=torch.int32, device=self.device)
         else:
             _check(perf, torch.int32, self.B * 8, self.device, "perf")
+        if q16 is not None:
+            self.set_action_noise(q16=q16)
         if T == 0:
             return perf
         _lib.check(_lib.lib().mapf_rollout_perf(self.h, SPARSE_POLICY[policy], T, _ptr(actions), _ptr(perf),
@@ -619,7 +655,7 @@ class BatchedMapfGym:
         return entry
 
     def rollout_launcher(self, T, slots=False, actions=None, obs=None, vec=None, out=None, actions_in=None,
-                         policy="random", obs_bits=False, sparse=True):
+                         policy="random", obs_bits=False, sparse=True, noise=None):
         """rollout(T, policy, slots=slots, ...) prepared once: the buffers are checked and the C call's
         arguments built now, on the current stream; the returned callable issues the launch with
         no per-call host work beyond one ctypes call (a 20-step rollout is ~350 us on the GPU, the
@@ -650,8 +686,12 @@ class BatchedMapfGym:
         each other.  The band rule holds for every policy.
 
         obs_bits: `obs` is the packed int32 buffer (as rollout()); every call stores every word
-        (the band rule does not apply)."""
+        (the band rule does not apply).
+
+        noise ("descent" / "pibt" only): an eps set on the handle now, once (set_action_noise); the
+        launches read the handle's setting when they are issued, a captured one keeps its capture's."""
         _policy_symbols(policy)
+        q16 = _check_noise_policy("tape" if actions_in is not None else policy, noise)
         if actions_in is not None:
             if policy not in ("random", "tape"):
                 raise ValueError("policy and actions_in are mutually exclusive")
@@ -661,6 +701,8 @@ class BatchedMapfGym:
             raise ValueError("policy='tape' needs its tape: actions_in=...")
         actions, so, out, obs, vec = self._rollout_buffers(T if slots else 1, slots, obs, vec, out, actions=actions,
                                                            tape=actions_in, obs_bits=obs_bits)
+        if q16 is not None:
+            self.set_action_noise(q16=q16)
         args = (self.h, int(T), self._slot_bits(slots, False, obs_bits), _ptr(actions), ctypes.byref(so), _ptr(obs),
                 _ptr(vec), _stream(self.device))
         clean = args[:2] + (self._slot_bits(slots, not obs_bits, obs_bits),) + args[3:]
@@ -731,6 +773,34 @@ class BatchedMapfGym:
         out = self.actions if out is None else out
         _check(out, torch.int32, self.B * self.N, self.device, "actions")
         _lib.check(_lib.lib().mapf_pibt_actions(self.h, _ptr(out), _stream(self.device)))
+        return out
+
+    def set_action_noise(self, eps=None, *, q16=None):
+        """Action noise of the picked policies' rollouts (mapf_set_action_noise; mapf.h has the rule): with
+        probability eps, a float in [0, 1] (or q16=, the integer eps * 65536 in 0..65536), an agent plays
+        the uniform random policy's action in place of the policy's pick, which stays the label the
+        rollout's `actions` receive.  0, the default, is off.  It applies to "descent" and "pibt" rollouts
+        (rollout, rollout_sparse, rollout_perf, launchers) and to noise_actions; "random" and "tape" ignore
+        it.  Takes effect at the next launch; a captured launch keeps the value it was captured with.
+        Resets leave it alone."""
+        q = noise_q16(eps, q16)
+        _lib.check(_lib.lib().mapf_set_action_noise(self.h, q))
+
+    @property
+    def action_noise(self):
+        """The handle's action noise as q16 (mapf_get_action_noise)."""
+        q = _lib.lib().mapf_get_action_noise(self.h)
+        _lib.check(min(q, 0))
+        return q
+
+    def noise_actions(self, labels, out=None):
+        """The actions played for `labels` (int32 [B, N]) under the handle's action noise at the current
+        state's clocks (mapf_noise_actions): int32 [B, N]; out may be labels; a copy at noise 0."""
+        _check(labels, torch.int32, self.B * self.N, self.device, "labels")
+        if out is None:
+            out = torch.empty_like(labels)
+        _check(out, torch.int32, self.B * self.N, self.device, "played")
+        _lib.check(_lib.lib().mapf_noise_actions(self.h, _ptr(labels), _ptr(out), _stream(self.device)))
         return out
 
     def set_pibt_human_weight(self, weight):

@@ -214,6 +214,23 @@ def pibt_policy(human_weight=None, human_horizon=None):
     return policy
 
 
+def noisy_policy(policy, eps):
+    """`policy` (a per-step policy of evaluate_fixed_episodes, e.g. pibt_policy()) under action noise
+    eps in [0, 1]: what it picks is the label, what is played is env.noise_actions(label) -- with
+    probability eps the uniform random policy's action (mapf_set_action_noise; mapf.h has the rule).
+    The noise is set on the env the policy is called with, once per env."""
+    from .env import noise_q16
+    q16 = noise_q16(eps)
+    done = []
+
+    def noisy(obs, vec, env, t):
+        if not done or done[0] is not env:
+            env.set_action_noise(q16=q16)
+            done[:] = [env]
+        return env.noise_actions(policy(obs, vec, env, t))
+    return noisy
+
+
 def evaluate_fixed_episodes(infos, policy, device=None, num_channel=6, fov=9, use_da=False, use_hp=False,
                             human_movement_type=0, max_steps=256, k_predict=5, fix_choice=1, record_actions=False,
                             keep_bfs=False):
@@ -296,12 +313,13 @@ def replay_fixed_episodes(infos, tapes, device=None, num_channel=6, fov=9, use_d
 
 def evaluate_fixed_episodes_device(infos, policy, *, tapes=None, human_weight=None, human_horizon=None, device=None,
                                    num_channel=6, fov=9, use_da=False, use_hp=False, human_movement_type=0,
-                                   max_steps=256, k_predict=5, fix_choice=1):
+                                   max_steps=256, k_predict=5, fix_choice=1, noise=None):
     """evaluate_fixed_episodes for a policy the rollout kernels run themselves: one rollout_perf launch
     per map-shape group, which steps the whole episode on the device and writes only the eight
     OneEpPerformance numbers of every env (mapf_rollout_perf) -- no observation is computed or stored.
     policy: "descent" | "pibt" (max_steps steps; human_weight / human_horizon as pibt_policy's) or
     "tape" (tapes[(H, W)] = int32 [T, len(group), N], as replay_fixed_episodes takes them).
+    noise ("descent" / "pibt" only): action noise eps in [0, 1], as noisy_policy's (env.rollout_perf(noise=)).
     Same env arguments, same {metric: float64 numpy [E]}.  Numerically: the six integer metrics equal
     evaluate_fixed_episodes' exactly; the two float metrics are the reference's own float32 running sums
     (`perf.episodeReward += np.sum(rewards)`: numpy's pairwise float32 sum over the agents, accumulated
@@ -312,6 +330,8 @@ def evaluate_fixed_episodes_device(infos, policy, *, tapes=None, human_weight=No
         raise ValueError(f"policy: expected 'descent', 'pibt' or 'tape', got {policy!r}")
     if policy == "tape" and tapes is None:
         raise ValueError("policy='tape' needs tapes=")
+    if noise is not None and policy == "tape":
+        raise ValueError("noise= goes with policy 'descent' or 'pibt', not 'tape'")
     device = torch.device("cuda") if device is None else torch.device(device)
     E = infos["numEpisodes"]
     res = {k: np.zeros(E, np.float64) for k in METRIC_KEYS}
@@ -326,7 +346,7 @@ def evaluate_fixed_episodes_device(infos, policy, *, tapes=None, human_weight=No
         if policy == "tape":
             perf = env.rollout_perf(policy="tape", tape=tapes[(H, W)])
         else:
-            perf = env.rollout_perf(max_steps, policy)
+            perf = env.rollout_perf(max_steps, policy, noise=noise)
         for key, col in perf_dict(perf).items():
             res[key][idx] = col.cpu().numpy().astype(np.float64)
         env.close()

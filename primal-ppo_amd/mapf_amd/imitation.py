@@ -15,7 +15,7 @@ ob[:T] is a contiguous view, gathered without a copy -- and slot T is the state 
 import torch
 
 from .config import NetParameters, TrainingParameters
-from .env import BatchedMapfGym
+from .env import BatchedMapfGym, noise_q16
 from .runner import DeviceMaps
 
 
@@ -25,23 +25,33 @@ class DemoRunner:
     human_weight (policy="pibt" only, ValueError otherwise): the planner's human weight, set on the env once
     here (env.set_pibt_human_weight); None leaves the env's setting alone.  human_horizon: likewise the
     planner's human horizon (env.set_pibt_human_horizon).
+    noise (policy "pibt" / "descent" only, ValueError for "tape"): action noise eps in [0, 1] on the
+    demonstrations, set on the env once here (env.set_action_noise); None leaves the env's setting alone.
+    With probability eps an agent plays a uniform random action, so the rollouts visit states the expert
+    alone never reaches; expert_actions stay the expert's picks for the states observed (the labels).
     new_maps, seed: as DeviceRunner.  obs_bits: keep the observations packed (`obs_bits` int32
     [T + 1, B, N, WPA]; the default) or as floats (`obs` [T + 1, B, N, C, F, F]).
     Exposes T, env, packed, obs / obs_bits, vec and expert_actions (int32 [T, B, N]): a source of
     Model.imitate_rows and DeviceTrainer.imitate."""
 
     def __init__(self, env: BatchedMapfGym, n_steps=None, policy="pibt", new_maps=None, obs_bits=True, seed=0,
-                 human_weight=None, human_horizon=None):
+                 human_weight=None, human_horizon=None, noise=None):
         if policy not in ("pibt", "descent", "tape"):
             raise ValueError(f"DemoRunner: policy must be 'pibt', 'descent' or 'tape' (an expert), got {policy!r}")
         if human_weight is not None and policy != "pibt":
             raise ValueError(f"human_weight belongs to policy='pibt', not {policy!r}")
         if human_horizon is not None and policy != "pibt":
             raise ValueError(f"human_horizon belongs to policy='pibt', not {policy!r}")
+        if noise is not None:
+            if policy == "tape":
+                raise ValueError("noise= belongs to policy 'pibt' or 'descent', not 'tape'")
+            noise = noise_q16(noise)
         if human_weight is not None:
             env.set_pibt_human_weight(human_weight)
         if human_horizon is not None:
             env.set_pibt_human_horizon(human_horizon)
+        if noise is not None:
+            env.set_action_noise(q16=noise)
         self.env, self.policy = env, policy
         self.T = TrainingParameters.N_STEPS if n_steps is None else int(n_steps)
         if self.T < 1:

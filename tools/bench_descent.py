@@ -11,7 +11,9 @@ then `--pairs` alternated pairs, each launch between two HIP events (the random 
 of its own, the descent launches and the per-step series sharing another), and then `--pairs`
 per-step series: the same policy as T x (descent_actions, step_observe) calls in place, between two
 HIP events over the whole series.  Goal changes per env-step come from goals_reached of the last
-timed launch.  With --baseline-lib the
+timed launch.  --noise EPS sets action noise eps on the descent handle (mapf_set_action_noise; 0, the
+default, is off; the per-step series then plays descent_actions, noise_actions, step_observe; a
+baseline from before action noise runs without).  With --baseline-lib the
 driver (which never opens the GPU) starts fresh child processes in turn, baseline / this build,
 `--rounds` times: the baseline library (the parent commit's build, which has no descent entry
 points) runs its random policy only.  The verdicts printed at the end:
@@ -29,6 +31,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "primal-ppo_amd")]
+NOISE_FNS = ("mapf_set_action_noise", "mapf_get_action_noise", "mapf_noise_actions", "mapf_action_noise_pick")
 DESCENT_FNS = ("mapf_rollout_descent", "mapf_rollout_descent_plan", "mapf_descent_actions", "mapf_descent_pick")
 
 
@@ -43,6 +46,11 @@ def measure(args):
     if not has:                           # a build from before the descent entry points: random policy only
         for n in DESCENT_FNS:
             _lib.SIGNATURES.pop(n)
+    has_noise = all(hasattr(ctypes.CDLL(_lib.LIB_PATH), n) for n in NOISE_FNS)
+    if not has_noise:                     # a build from before action noise: the clean policy
+        for n in NOISE_FNS:
+            _lib.SIGNATURES.pop(n)
+    noise = args.noise if has_noise else 0.0
     from mapf_amd.config import make_config
     from mapf_amd.env import BatchedMapfGym
     p = bench.PRESETS[args.config]
@@ -71,13 +79,16 @@ def measure(args):
     plan = {"random": env.rollout_plan(slots, slots)}
     if has:
         denv = make_env()
+        if noise:
+            denv.set_action_noise(noise)
         launch["descent"] = denv.rollout_launcher(T, policy="descent", **kw)
         plan["descent"] = denv.rollout_descent_plan(slots, slots)
         out0 = {k: v[0] for k, v in out.items()}
 
         def per_step():
             for _ in range(T):
-                denv.step_observe(denv.descent_actions(acts[0]), obs[0], vec[0], out=out0)
+                a = denv.descent_actions(acts[0])
+                denv.step_observe(denv.noise_actions(a, out=a) if noise else a, obs[0], vec[0], out=out0)
         launch["per-step"] = per_step
     times = {k: [] for k in launch}
     goals = {}
@@ -101,7 +112,7 @@ def measure(args):
                 goals[k] = round(float(out["goals_reached"].sum()) / (T * B), 5)
     c = env.counters() + (denv.counters() if has else 0)
     print(json.dumps({"config": args.config, "envs": B, "buffers": "slots" if slots else "in place",
-                      "lib": os.path.basename(_lib.LIB_PATH), "T": T, "us_per_step": times, "plan": plan,
+                      "lib": os.path.basename(_lib.LIB_PATH), "T": T, "noise": noise, "us_per_step": times, "plan": plan,
                       "goal_changes_per_env_step": goals, "counters": [int(x) for x in c[:8]]}), flush=True)
 
 
@@ -115,6 +126,7 @@ def main():
     ap.add_argument("--lib", default=None, help="library to measure (default: the package's)")
     ap.add_argument("--baseline-lib", default=None, help="a baseline build to alternate with (random policy only)")
     ap.add_argument("--inplace", action="store_true", help="the [B]-leading buffers instead of [T]-slot buffers")
+    ap.add_argument("--noise", type=float, default=0.0, help="action noise eps in [0, 1] on the descent policy (default 0: off)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child or not args.baseline_lib:
@@ -124,7 +136,8 @@ def main():
     for r in range(args.rounds):
         for which, lib in (("baseline", args.baseline_lib), ("new", args.lib)):
             cmd = [sys.executable, os.path.abspath(__file__), "--child", "--config", args.config, "--T", str(args.T),
-                   "--pairs", str(args.pairs)] + (["--lib", lib] if lib else []) + (["--inplace"] if args.inplace else []) + ["--envs", str(args.envs)]
+                   "--pairs", str(args.pairs)] + (["--lib", lib] if lib else []) + (["--inplace"] if args.inplace else []) + ["--envs", str(args.envs)] + \
+                ["--noise", str(args.noise)]
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             if res.returncode != 0:
                 sys.stderr.write(res.stderr[-3000:])

@@ -11,6 +11,14 @@
   3. The loss and agreement-with-PIBT curves over --updates captured updates (256 x 8 rows each) on PIBT
      demonstrations: a new rollout (the envs run on) every (T * B) // 256 updates, dropout on, the default
      learning rate.
+  4. --own-steps K (default 0: skipped) steps of DeviceRunner(expert="pibt") with the model part 3 trained: the
+     learner acts, the planner labels the learner's own states, and the share of agent-steps where the policy's
+     most probable action is the label is printed -- the agreement off the demonstrations' distribution.
+
+  python tools/bench_imitation.py --noise 0.1 --skip-timing --own-steps 32   # parts 1, 3, 4 on demonstrations under action noise
+
+--noise EPS puts action noise eps on the demonstrations (DemoRunner(noise=...), mapf_set_action_noise): the rollouts
+play a uniform random action with probability eps, the labels stay the planner's.  Part 4's labels are clean.
 """
 import argparse
 import json
@@ -42,6 +50,9 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--updates", type=int, default=300)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--noise", type=float, default=None, help="action noise eps in [0, 1] on the demonstrations")
+    ap.add_argument("--own-steps", type=int, default=0, help="part 4: steps the learner acts, the planner labelling (0: skip)")
+    ap.add_argument("--skip-timing", action="store_true", help="leave out part 2, the update times")
     args = ap.parse_args()
     import mapf_amd  # noqa: F401
     import torch
@@ -58,11 +69,11 @@ def main():
     env = BatchedMapfGym(make_config(B, S, S, num_agents=N, fov=F, num_channel=C, human_mode="random",
                                      goal_mode="random", fix_choice=1, keep_bfs=True, seed=1234))
     env.reset_seeded(generate_warehouse(S, S))
-    demo = DemoRunner(env, n_steps=T, policy="pibt", obs_bits=True, seed=args.seed)
+    demo = DemoRunner(env, n_steps=T, policy="pibt", obs_bits=True, seed=args.seed, noise=args.noise)
     demo.run()
     ms = timed(demo.run, args.reps)
     perf = demo.performance_per_env()
-    print(json.dumps({"part": "demo", "envs": B, "agents": N, "T": T, "plan": env.rollout_plan(True, False, True, policy="pibt"),
+    print(json.dumps({"part": "demo", "envs": B, "agents": N, "T": T, "noise_q16": env.action_noise, "plan": env.rollout_plan(True, False, True, policy="pibt"),
                       "ms_per_rollout": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3),
                       "us_per_step": round(statistics.median(ms) * 1e3 / T, 2),
                       "agent_steps_per_s": round(B * N * T / (statistics.median(ms) * 1e-3)),
@@ -72,7 +83,7 @@ def main():
     # ---- 2. update times
     torch.manual_seed(args.seed)
     g = torch.Generator(device="cuda").manual_seed(1)
-    for n in (8, 16):
+    for n in (() if args.skip_timing else (8, 16)):
         rows = 256
         series = {}
         for graph in (False, True):
@@ -118,7 +129,22 @@ def main():
                           "loss": round(statistics.mean(x[0] for x in w), 4),
                           "agreement": round(statistics.mean(x[2] for x in w), 4),
                           "expert_prob": round(statistics.mean(x[3] for x in w), 4)}), flush=True)
-    assert not env.counters()[:8].any()
+    assert not env.counters()[:8 if not env.action_noise else 1].any()      # (noise boxes agents in: counters 1, 2 may count)
+
+    # ---- 4. the learner on its own states, labelled by the planner (no noise: the sampler explores)
+    if args.own_steps > 0:
+        from mapf_amd.runner import DeviceRunner
+        own = BatchedMapfGym(make_config(B, S, S, num_agents=N, fov=F, num_channel=C, human_mode="random",
+                                         goal_mode="random", fix_choice=1, keep_bfs=True, seed=4321))
+        own.reset_seeded(generate_warehouse(S, S), seed=11)
+        runner = DeviceRunner(own, model, n_steps=args.own_steps, seed=args.seed, obs_bits=True, expert="pibt")
+        runner.run()
+        agree = (runner.ps.argmax(-1).to(torch.int32) == runner.expert_actions).float().mean()
+        print(json.dumps({"part": "own_states", "steps": args.own_steps, "demo_noise_q16": env.action_noise,
+                          "agreement": round(float(agree), 4),
+                          "goals_per_env_step": round(float(runner.goals.sum()) / (args.own_steps * B), 4),
+                          "agent_collisions_per_env_step": round(float((runner.status == -3).sum()) / (args.own_steps * B), 4)}),
+              flush=True)
 
 
 if __name__ == "__main__":

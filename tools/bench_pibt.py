@@ -6,6 +6,7 @@ one GPU.
   python tools/bench_pibt.py --config c2 --baseline-lib primal-ppo_amd/lib/libmapf_parent.so --rounds 3
   python tools/bench_pibt.py --config c4 --human-weight 2 --skip-per-step      # the planner at human weight 2
   python tools/bench_pibt.py --config c4 --human-weight 2 --human-horizon 3 --skip-per-step      # ... pricing 3 cells ahead
+  python tools/bench_pibt.py --config c2 --noise 0.25 --skip-per-step          # descent and the planner under action noise
 
 Each measurement process builds the preset's env (bench.py's presets and maps), prepares one launcher
 per policy over the same [T]-slot buffers (T = 256, c5: 87), every policy on a handle of its own (so
@@ -14,7 +15,9 @@ rounds random / descent / pibt, each launch between two HIP events, and then `--
 series: PIBT as T x (pibt_actions, step_observe) calls in place, between two HIP events over the whole
 series (--skip-per-step leaves it out).  --human-weight W sets the PIBT handle's human weight
 (mapf_set_pibt_human_weight; 0, the default, is the plain policy) and --human-horizon K its human horizon
-(mapf_set_pibt_human_horizon; 1, the default, prices the human's next cell alone) before its launches.  From the last
+(mapf_set_pibt_human_horizon; 1, the default, prices the human's next cell alone) before its launches.  --noise EPS sets
+action noise eps on the descent and the PIBT handle (mapf_set_action_noise; 0, the default, is off; the per-step series
+then plays pibt_actions, noise_actions, step_observe; "rewritten" below then compares with the labels).  From the last
 timed launch of descent and of PIBT, per env-step: goals reached, agents with status -3 and -2, actions
 fixActions rewrote (actions_fixed != actions), agents counted in `constraints`, and the mean cost reward
 per agent-step.  With --baseline-lib the driver (which never opens the GPU) starts fresh child processes
@@ -39,6 +42,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "primal-ppo_amd")]
 PIBT_FNS = ("mapf_rollout_pibt", "mapf_rollout_pibt_plan", "mapf_pibt_actions", "mapf_pibt_key", "mapf_pibt_host")
 HUMAN_FNS = ("mapf_set_pibt_human_weight", "mapf_get_pibt_human_weight", "mapf_pibt_human_level")
+NOISE_FNS = ("mapf_set_action_noise", "mapf_get_action_noise", "mapf_noise_actions", "mapf_action_noise_pick")
 HORIZON_FNS = ("mapf_set_pibt_human_horizon", "mapf_get_pibt_human_horizon", "mapf_pibt_human_cells", "mapf_pibt_w_word")
 
 
@@ -62,6 +66,11 @@ def measure(args):
     if not has_horizon:                   # a build from before the human horizon: the next cell alone
         for n in HORIZON_FNS:
             _lib.SIGNATURES.pop(n)
+    has_noise = all(hasattr(ctypes.CDLL(_lib.LIB_PATH), n) for n in NOISE_FNS)
+    if not has_noise:                     # a build from before action noise: the clean policies
+        for n in NOISE_FNS:
+            _lib.SIGNATURES.pop(n)
+    noise = args.noise if has_noise else 0.0
     from mapf_amd.config import make_config
     from mapf_amd.env import BatchedMapfGym
     p = bench.PRESETS[args.config]
@@ -82,6 +91,8 @@ def measure(args):
     obs = torch.empty(K, B, N, C, F, F, dtype=torch.float32, device=dev)
     vec = torch.empty(K, B, N, 4, dtype=torch.float32, device=dev)
     envs = {"random": make_env(), "descent": make_env()}
+    if noise:
+        envs["descent"].set_action_noise(noise)
     out = {k: torch.empty((K,) + tuple(v.shape), dtype=v.dtype, device=dev) for k, v in envs["random"].out.items()}
     kw = dict(slots=slots, actions=acts, obs=obs, vec=vec, out=out)
     launch = {"random": envs["random"].rollout_launcher(T, **kw),
@@ -93,13 +104,16 @@ def measure(args):
             penv.set_pibt_human_weight(args.human_weight)
         if has_horizon:
             penv.set_pibt_human_horizon(args.human_horizon)
+        if noise:
+            penv.set_action_noise(noise)
         launch["pibt"] = penv.rollout_launcher(T, policy="pibt", **kw)
         plan["pibt"] = penv.rollout_pibt_plan(slots, slots)
         out0 = {k: v[0] for k, v in out.items()}
 
         def per_step():
             for _ in range(T):
-                penv.step_observe(penv.pibt_actions(acts[0]), obs[0], vec[0], out=out0)
+                a = penv.pibt_actions(acts[0])
+                penv.step_observe(penv.noise_actions(a, out=a) if noise else a, obs[0], vec[0], out=out0)
         if not args.skip_per_step:
             launch["per-step"] = per_step
     times = {k: [] for k in launch}
@@ -132,7 +146,7 @@ def measure(args):
     print(json.dumps({"config": args.config, "envs": B, "buffers": "slots" if slots else "in place",
                       "lib": os.path.basename(_lib.LIB_PATH), "T": T,
                       "human_weight": args.human_weight if has_weight else 0,
-                      "human_horizon": args.human_horizon if has_horizon else 1, "us_per_step": times, "plan": plan,
+                      "human_horizon": args.human_horizon if has_horizon else 1, "noise": noise, "us_per_step": times, "plan": plan,
                       "per_env_step": quality, "counters": [int(x) for x in c[:8]]}), flush=True)
 
 
@@ -147,6 +161,7 @@ def main():
     ap.add_argument("--baseline-lib", default=None, help="a baseline build to alternate with (the policies it has)")
     ap.add_argument("--human-weight", type=int, default=0, help="the PIBT policy's human weight, 0..16 (default 0: off)")
     ap.add_argument("--human-horizon", type=int, default=1, help="the PIBT policy's human horizon, 1..8 (default 1: the next cell alone)")
+    ap.add_argument("--noise", type=float, default=0.0, help="action noise eps in [0, 1] on descent and pibt (default 0: off)")
     ap.add_argument("--skip-per-step", action="store_true", help="leave out the per-step PIBT series")
     ap.add_argument("--inplace", action="store_true", help="the [B]-leading buffers instead of [T]-slot buffers")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -160,7 +175,8 @@ def main():
         for which, lib in (("baseline", args.baseline_lib), ("new", args.lib)):
             cmd = [sys.executable, os.path.abspath(__file__), "--child", "--config", args.config, "--T", str(args.T),
                    "--pairs", str(args.pairs)] + (["--lib", lib] if lib else []) + (["--inplace"] if args.inplace else []) + ["--envs", str(args.envs)] + \
-                ["--human-weight", str(args.human_weight), "--human-horizon", str(args.human_horizon)] + (["--skip-per-step"] if args.skip_per_step else [])
+                ["--human-weight", str(args.human_weight), "--human-horizon", str(args.human_horizon), "--noise", str(args.noise)] + \
+                (["--skip-per-step"] if args.skip_per_step else [])
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             if res.returncode != 0:
                 sys.stderr.write(res.stderr[-3000:])
@@ -182,7 +198,7 @@ def main():
     print(f"  per env-step, last launch (pibt at human weight {new['human_weight']}, horizon {new['human_horizon']}): "
           f"{new['per_env_step']}")
     # the baseline plays the same policy: weight 0, or its own weight W at horizon 1 (a baseline with the weight)
-    same_policy = args.human_weight == 0 or args.human_horizon == 1
+    same_policy = (args.human_weight == 0 or args.human_horizon == 1) and args.noise == 0
     for k in ("random", "descent") + (("pibt",) if "baseline pibt" in stat and same_policy else ()):
         bm, lo, hi = stat["baseline " + k]
         print(f"  (i)  {k} median {stat[k][0]:.3f} inside the baseline's [{lo:.3f}, {hi:.3f}]: "
