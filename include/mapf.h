@@ -753,6 +753,107 @@ typedef struct mapf_gather_spec {
  * 2^31 - 1 workgroups.  No host synchronisation and no allocation: capturable. */
 int mapf_gather_rows(const mapf_gather_spec *spec, void *stream);
 
+/* ---- Grid symmetries: every training row is eight (csrc/mapf_sym.h, csrc/mapf_sym.hip) ----
+ *
+ * The observation is an F x F window centred on the agent (F odd) and every channel is spatially
+ * equivariant, so a row of (observation, vec, action, per-action columns) transformed by one of the
+ * square's eight symmetries is the row the env would have produced on the transformed world.
+ * A symmetry is g in 0..7: bit 2 = mirror the columns first, bits 0..1 = that many counter-clockwise
+ * quarter turns after it.  On an F x F plane x, in numpy:
+ *     np.rot90(np.flip(x, -1) if g & 4 else x, k=g & 3, axes=(-2, -1))
+ * Rows grow downwards; action 1 is (0,+1), 2 is (+1,0), 3 is (0,-1), 4 is (-1,0).  Per generator:
+ *                               quarter turn                      mirror
+ *   cell (r, c)                 (F-1-c, r)                        (r, F-1-c)
+ *   displacement (dr, dc)       (-dc, dr)                         (dr, -dc)
+ *   action                      0 -> 0, 1 -> 4, 2 -> 1,           1 <-> 3
+ *                               3 -> 2, 4 -> 3
+ *   vec (v0, v1, v2, v3)        (0.0f - v1, v0, v2, v3)           (v0, 0.0f - v1, v2, v3)
+ *   columns x[5] (train_valid,  out[action'(a)] = x[a]            out[action'(a)] = x[a]
+ *   ps)
+ * Negation is 0.0f - x, so a zero component stays +0.0 as the env computes it: vec is bit-equal to the
+ * transformed world's.  An action outside 0..4 is copied unchanged.  The functions of csrc/mapf_sym.h
+ * are the rule; the kernels and the host entry points below all run them.
+ *
+ * Host entry points (no device call; they work on a machine without a GPU):
+ *   mapf_sym_cell      where cell (r, c) of an F x F plane goes under g
+ *   mapf_sym_action    the action (any other value is returned as it is)
+ *   mapf_sym_vec_host  vec float [n][4] -> out [n][4]
+ *   mapf_sym_cols_host columns float [n][5] -> out [n][5]
+ *   mapf_sym_obs_host  obs float [n_agents][C][F][F] -> out, every plane transformed (out != obs)
+ *   mapf_sym_compose   the g whose effect is g1's, then g2's
+ *   mapf_sym_inverse   the g that undoes g
+ * MAPF_EINVAL for g outside 0..7, F < 1, a cell outside the plane, a null pointer, n < 0. */
+int mapf_sym_cell(int32_t g, int32_t F, int32_t r, int32_t c, int32_t *r2, int32_t *c2);
+int64_t mapf_sym_action(int32_t g, int64_t a);
+int mapf_sym_vec_host(const float *vec, int64_t n, int32_t g, float *out);
+int mapf_sym_cols_host(const float *cols, int64_t n, int32_t g, float *out);
+int mapf_sym_obs_host(const float *obs, int64_t n_agents, int32_t C, int32_t F, int32_t g, float *out);
+int mapf_sym_compose(int32_t g1, int32_t g2);
+int mapf_sym_inverse(int32_t g);
+
+/* mapf_sym_draw: sym_out[j] for j < count, DEVICE uint8 [count], uniform over the set bits of the 8-bit
+ * mask `allowed` (0xFF the whole group, 0x0F rotations only, 0x01 identity only).  Stateless, a pure
+ * function of (seed, epoch, start + j): word = x of the Philox4x32-10 draw with key `seed` and counter
+ * (low 32 bits of start + j, P_SYM, epoch, high 32 bits of start + j), P_SYM = 13; the pick is the
+ * ((word * popcount(allowed)) >> 32)-th set bit of allowed, counted from bit 0.  MAPF_EINVAL for
+ * allowed == 0 or > 0xFF, start < 0, count < 0, a null sym_out with count > 0; count == 0 launches
+ * nothing.  Asynchronous on `stream`; capturable.  mapf_sym_draw_host: the same values into a HOST
+ * array by the same function, no device call. */
+int mapf_sym_draw(uint64_t seed, uint32_t epoch, int64_t start, int64_t count, uint32_t allowed, uint8_t *sym_out,
+                  void *stream);
+int mapf_sym_draw_host(uint64_t seed, uint32_t epoch, int64_t start, int64_t count, uint32_t allowed,
+                       uint8_t *sym_out);
+
+/* What mapf_gather_rows_sym does to one array's rows. */
+#define MAPF_GATHER_PLAIN 0      /* bytes copied, as mapf_gather_rows                                   */
+#define MAPF_GATHER_OBS_F32 1    /* float [N][C][F][F] -> the same shape, every plane transformed       */
+#define MAPF_GATHER_OBS_BITS 2   /* uint32 [N][WPA] ("Packed observations") -> float [N][C][F][F]       */
+#define MAPF_GATHER_VEC 3        /* float [N][4]                                                        */
+#define MAPF_GATHER_ACTION32 4   /* int32 [N]                                                           */
+#define MAPF_GATHER_ACTION64 5   /* int64 [N], src and dst 8-byte aligned                               */
+#define MAPF_GATHER_COLS 6       /* float [N][5]: per-action columns (train_valid, ps)                  */
+
+typedef struct mapf_gather_sym_array {
+    const void *src;         /* DEVICE, t-major [T][B][src_row_bytes]                       */
+    void *dst;               /* DEVICE, [M][dst_row_bytes]                                  */
+    int64_t src_row_bytes;   /* positive multiples of 4; equal but for MAPF_GATHER_OBS_BITS */
+    int64_t dst_row_bytes;
+    int32_t kind;            /* MAPF_GATHER_*                                               */
+    int32_t reserved;
+} mapf_gather_sym_array;
+
+typedef struct mapf_gather_sym_spec {
+    int32_t T, B;            /* the rollout: T steps of B envs                              */
+    int64_t M;               /* rows gathered                                               */
+    const int64_t *rows;     /* DEVICE [M]: env-major row ids in [0, B*T)                   */
+    const uint8_t *sym;      /* DEVICE [M]: g per gathered row (its low 3 bits); NULL = identity */
+    int32_t N, C, F;         /* agents per row, channels, window                            */
+    int32_t count;           /* arrays, 1..MAPF_GATHER_MAX                                  */
+    mapf_gather_sym_array arrays[MAPF_GATHER_MAX];
+} mapf_gather_sym_spec;
+
+/* mapf_gather_rows with a symmetry per gathered row, in ONE launch: row j of every array's dst is row
+ * rows[j] of its src (mapf_gather_rows' addressing: env-major row r is step r % T, env r / T)
+ * transformed by sym[j] as the array's kind says.  A packed observation is unpacked and transformed in
+ * the same pass -- no staging copy, no mapf_unpack_obs launch; with sym NULL (or g = 0) the result is
+ * mapf_gather_rows' bytes (followed by mapf_unpack_obs' for MAPF_GATHER_OBS_BITS).  No byte outside
+ * the destinations is written; duplicate rows are legal; rows are not range-checked.
+ * Row lengths: OBS_F32 N*C*F*F*4 both sides; OBS_BITS N*WPA*4 -> N*C*F*F*4; VEC N*16; ACTION32 N*4;
+ * ACTION64 N*8; COLS N*20; PLAIN any equal pair.
+ * Grid: per gathered row, one workgroup of 256 lanes per 4 KiB piece of the DESTINATION row of each
+ * array whose destination rows are longer than 1 KiB; the shorter arrays ride with the row's first
+ * workgroup.  An observation whose dst and dst_row_bytes are multiples of 16 is stored in 16-byte
+ * pieces, lane-contiguous, each lane finding its source cells through the inverse map; the packed words
+ * under a piece are staged in LDS (5 KiB per workgroup).
+ * MAPF_EINVAL, before any launch: what mapf_gather_rows refuses (null spec / rows / src / dst, count
+ * outside 1..16, row lengths that are not positive multiples of 4, pointers not 4-byte aligned, T, B or
+ * M < 1, more than 2^31 - 1 workgroups); a kind outside the list; N < 1; F outside 1..16 or C outside
+ * 1..7; F even while sym != NULL (an even window is not centred on the agent: its transform is not an
+ * observation the env can produce); a row length that does not match the kind and N, C, F; an int64
+ * action array not 8-byte aligned.  mapf_last_error names the field.  No host synchronisation and no
+ * allocation: capturable. */
+int mapf_gather_rows_sym(const mapf_gather_sym_spec *spec, void *stream);
+
 /* ---- Policy acting forward: fused elementwise epilogues (csrc/mapf_policy.hip) ----
  * SCRIMPNet.forward (net.py:101-155) under autocast with no grad (Model.step /
  * Model.value, model.py:26-69); each call replaces two or three of torch's passes

@@ -22,6 +22,8 @@
 #include "mapf_kernels.h"
 #include "mapf_group.h"     // pace_gate, evaluated on the host by mapf_pace_gate
 #include "mapf_observe.h"  // obs_band_skip, evaluated on the host by mapf_obs_band_skip
+#include "mapf_obs_bits.h"
+#include "mapf_sym.h"      // the grid symmetries, evaluated on the host by mapf_sym_*
 
 using namespace mapf;
 
@@ -1611,6 +1613,159 @@ int mapf_gather_rows(const mapf_gather_spec *spec, void *stream) {
     const int64_t blocks = spec->M * a.chunks_per_row;
     if (spec->M > 0x7FFFFFFF || blocks > 0x7FFFFFFF) return fail(MAPF_EINVAL, "more than 2^31 - 1 workgroups");
     launch_gather_rows(a, blocks, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+// ---- grid symmetries (mapf_sym.h) ----
+static int sym_ok(int32_t g) { return g >= 0 && g <= 7 ? MAPF_OK : fail(MAPF_EINVAL, "g must be in 0..7"); }
+
+int mapf_sym_cell(int32_t g, int32_t F, int32_t r, int32_t c, int32_t *r2, int32_t *c2) {
+    if (int rc = sym_ok(g)) return rc;
+    if (!r2 || !c2) return fail(MAPF_EINVAL, "null argument");
+    if (F < 1 || r < 0 || r >= F || c < 0 || c >= F) return fail(MAPF_EINVAL, "need F >= 1 and a cell (r, c) inside F x F");
+    int rr, cc;
+    sym_cell(g, F, r, c, rr, cc);
+    *r2 = rr;
+    *c2 = cc;
+    return MAPF_OK;
+}
+
+int64_t mapf_sym_action(int32_t g, int64_t a) { return sym_action(g & 7, a); }
+
+int mapf_sym_vec_host(const float *vec, int64_t n, int32_t g, float *out) {
+    if (int rc = sym_ok(g)) return rc;
+    if (n < 0 || ((!vec || !out) && n > 0)) return fail(MAPF_EINVAL, "null argument or n < 0");
+    for (int64_t i = 0; i < n; ++i) {
+        float v[4] = {vec[4 * i], vec[4 * i + 1], vec[4 * i + 2], vec[4 * i + 3]};
+        sym_vec(g, v, out + 4 * i);
+    }
+    return MAPF_OK;
+}
+
+int mapf_sym_cols_host(const float *cols, int64_t n, int32_t g, float *out) {
+    if (int rc = sym_ok(g)) return rc;
+    if (n < 0 || ((!cols || !out) && n > 0)) return fail(MAPF_EINVAL, "null argument or n < 0");
+    for (int64_t i = 0; i < n; ++i) {
+        float v[NA];
+        for (int a = 0; a < NA; ++a) v[a] = cols[NA * i + a];
+        sym_cols(g, v, out + NA * i);
+    }
+    return MAPF_OK;
+}
+
+int mapf_sym_obs_host(const float *obs, int64_t n_agents, int32_t C, int32_t F, int32_t g, float *out) {
+    if (int rc = sym_ok(g)) return rc;
+    if (n_agents < 0 || C < 1 || F < 1) return fail(MAPF_EINVAL, "need n_agents >= 0, C >= 1, F >= 1");
+    if ((!obs || !out || obs == out) && n_agents > 0) return fail(MAPF_EINVAL, "null argument, or out == obs");
+    const int64_t FF = (int64_t)F * F;
+    for (int64_t p = 0; p < n_agents * C; ++p)
+        for (int i = 0; i < F; ++i)
+            for (int j = 0; j < F; ++j) {
+                int r, c;
+                sym_cell_inv(g, F, i, j, r, c);
+                out[p * FF + i * F + j] = obs[p * FF + r * F + c];
+            }
+    return MAPF_OK;
+}
+
+int mapf_sym_compose(int32_t g1, int32_t g2) { return sym_compose(g1 & 7, g2 & 7); }
+int mapf_sym_inverse(int32_t g) { return sym_inverse(g & 7); }
+
+static int sym_draw_ok(int64_t start, int64_t count, uint32_t allowed, const uint8_t *sym_out) {
+    if (allowed == 0 || allowed > 0xFFu) return fail(MAPF_EINVAL, "allowed must be in 1..0xFF");
+    if (start < 0 || count < 0) return fail(MAPF_EINVAL, "start and count must be >= 0");
+    if (!sym_out && count > 0) return fail(MAPF_EINVAL, "null argument");
+    return MAPF_OK;
+}
+
+int mapf_sym_draw(uint64_t seed, uint32_t epoch, int64_t start, int64_t count, uint32_t allowed, uint8_t *sym_out,
+                  void *stream) {
+    if (int rc = sym_draw_ok(start, count, allowed, sym_out)) return rc;
+    if (count == 0) return MAPF_OK;
+    launch_sym_draw(seed, epoch, start, count, allowed, sym_out, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return MAPF_OK;
+}
+
+int mapf_sym_draw_host(uint64_t seed, uint32_t epoch, int64_t start, int64_t count, uint32_t allowed,
+                       uint8_t *sym_out) {
+    if (int rc = sym_draw_ok(start, count, allowed, sym_out)) return rc;
+    for (int64_t j = 0; j < count; ++j) sym_out[j] = (uint8_t)sym_draw(seed, epoch, (uint64_t)(start + j), allowed);
+    return MAPF_OK;
+}
+
+int mapf_gather_rows_sym(const mapf_gather_sym_spec *spec, void *stream) {
+    if (!spec || !spec->rows) return fail(MAPF_EINVAL, "null argument");
+    if (spec->count < 1 || spec->count > MAPF_GATHER_MAX) return fail(MAPF_EINVAL, "count must be in 1..16");
+    if (spec->T < 1 || spec->B < 1 || spec->M < 1) return fail(MAPF_EINVAL, "T, B and M must be >= 1");
+    const int N = spec->N, C = spec->C, F = spec->F;
+    if (N < 1) return fail(MAPF_EINVAL, "N must be >= 1");
+    if (F < 1 || F > 16) return fail(MAPF_EINVAL, "F must be in 1..16");
+    if (C < 1 || C > 7) return fail(MAPF_EINVAL, "C must be in 1..7");
+    if (spec->sym && !(F & 1)) return fail(MAPF_EINVAL, "F must be odd with sym: an even window is not centred");
+    const int64_t CFF = (int64_t)C * F * F, WPA = obs_bits_words(C, F);
+    SymGatherArgs a{};
+    a.rows = spec->rows;
+    a.sym = spec->sym;
+    a.T = spec->T;
+    a.B = spec->B;
+    a.N = N;
+    a.C = C;
+    a.F = F;
+    a.count = spec->count;
+    for (int i = 0; i < spec->count; ++i) {
+        const mapf_gather_sym_array &g = spec->arrays[i];
+        if (!g.src || !g.dst) return fail(MAPF_EINVAL, "null src or dst");
+        if (g.src_row_bytes < 4 || (g.src_row_bytes & 3) || g.dst_row_bytes < 4 || (g.dst_row_bytes & 3))
+            return fail(MAPF_EINVAL, "src_row_bytes and dst_row_bytes must be positive multiples of 4");
+        if (((uintptr_t)g.src | (uintptr_t)g.dst) & 3) return fail(MAPF_EINVAL, "src and dst must be 4-byte aligned");
+        int64_t want_src = g.src_row_bytes, want_dst = g.src_row_bytes;
+        switch (g.kind) {
+        case MAPF_GATHER_PLAIN: break;
+        case MAPF_GATHER_OBS_F32: want_src = want_dst = N * CFF * 4; break;
+        case MAPF_GATHER_OBS_BITS: want_src = N * WPA * 4, want_dst = N * CFF * 4; break;
+        case MAPF_GATHER_VEC: want_src = want_dst = (int64_t)N * 16; break;
+        case MAPF_GATHER_ACTION32: want_src = want_dst = (int64_t)N * 4; break;
+        case MAPF_GATHER_ACTION64: want_src = want_dst = (int64_t)N * 8; break;
+        case MAPF_GATHER_COLS: want_src = want_dst = (int64_t)N * 4 * NA; break;
+        default: return fail(MAPF_EINVAL, "kind must be one of MAPF_GATHER_* (0..6)");
+        }
+        if (g.src_row_bytes != want_src || g.dst_row_bytes != want_dst)
+            return fail(MAPF_EINVAL, "src_row_bytes / dst_row_bytes do not match the kind and N, C, F");
+        if (g.dst_row_bytes > 0x7FFFFFFF) return fail(MAPF_EINVAL, "dst_row_bytes above 2^31 - 1");
+        if (g.kind == MAPF_GATHER_ACTION64 && (((uintptr_t)g.src | (uintptr_t)g.dst) & 7))
+            return fail(MAPF_EINVAL, "int64 action src and dst must be 8-byte aligned");
+        // the packed words staged for one piece: the agents under min(row, GATHER_CHUNK) / 4 floats
+        if (g.kind == MAPF_GATHER_OBS_BITS && std::min<int64_t>(N, (GATHER_CHUNK / 4 - 1) / CFF + 2) * WPA > SYM_LDS_WORDS)
+            return fail(MAPF_EINVAL, "N, C, F: a piece's packed words do not fit the staging buffer");
+        a.nbig += g.dst_row_bytes > GATHER_SMALL;
+    }
+    int nb = 0, ns = a.nbig;                       // big arrays first, each group in the caller's order
+    int64_t chunks = 0;
+    for (int i = 0; i < spec->count; ++i) {
+        const mapf_gather_sym_array &g = spec->arrays[i];
+        const int k = g.dst_row_bytes > GATHER_SMALL ? nb++ : ns++;
+        a.src[k] = static_cast<const char *>(g.src);
+        a.dst[k] = static_cast<char *>(g.dst);
+        a.src_row_bytes[k] = g.src_row_bytes;
+        a.dst_row_bytes[k] = g.dst_row_bytes;
+        a.kind[k] = g.kind;
+        // 16-byte accesses: the destination always; the source too where its bytes are copied
+        uintptr_t bits = (uintptr_t)g.dst | (uintptr_t)g.dst_row_bytes;
+        if (g.kind != MAPF_GATHER_OBS_BITS) bits |= (uintptr_t)g.src | (uintptr_t)g.src_row_bytes;
+        if (!(bits & 15)) a.vec16 |= 1u << k;
+    }
+    for (int k = 0; k < a.nbig; ++k) {
+        a.chunk_begin[k] = (int)chunks;
+        chunks += (a.dst_row_bytes[k] + GATHER_CHUNK - 1) / GATHER_CHUNK;
+        if (chunks > 0x7FFFFFFF) return fail(MAPF_EINVAL, "more than 2^31 - 1 workgroups");
+    }
+    a.chunk_begin[a.nbig] = (int)chunks;
+    a.chunks_per_row = chunks > 0 ? (int)chunks : 1;
+    const int64_t blocks = spec->M * a.chunks_per_row;
+    if (spec->M > 0x7FFFFFFF || blocks > 0x7FFFFFFF) return fail(MAPF_EINVAL, "more than 2^31 - 1 workgroups");
+    launch_gather_rows_sym(a, blocks, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return MAPF_OK;
 }

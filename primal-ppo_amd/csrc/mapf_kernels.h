@@ -272,5 +272,26 @@ struct GatherArgs {
 };
 void launch_minibatch_rows(const ShuffleKey &key, int64_t start, int64_t count, int64_t *rows, hipStream_t s);
 void launch_gather_rows(const GatherArgs &a, int64_t blocks, hipStream_t s);
+// the gather with a symmetry per row (mapf_sym.hip).  SymGatherArgs: GatherArgs' layout with the row
+// lengths of both sides and the kind of every array; "big" and the chunks go by the destination row.
+// vec16: the array's plain copy (kind plain, or an identity row of float observations) and its
+// observation stores may be 16 bytes wide.
+struct SymGatherArgs {
+    const int64_t *rows;
+    const uint8_t *sym;          // NULL: identity for every row
+    int T, B, count, nbig, chunks_per_row;
+    int N, C, F;
+    uint32_t vec16;
+    int chunk_begin[MAPF_GATHER_MAX + 1];
+    int kind[MAPF_GATHER_MAX];
+    int64_t src_row_bytes[MAPF_GATHER_MAX], dst_row_bytes[MAPF_GATHER_MAX];
+    const char *src[MAPF_GATHER_MAX];
+    char *dst[MAPF_GATHER_MAX];
+};
+// packed words a piece of a gathered row can need in LDS: the agents under GATHER_CHUNK / 4 floats
+constexpr int SYM_LDS_WORDS = 1280;
+void launch_gather_rows_sym(const SymGatherArgs &a, int64_t blocks, hipStream_t s);
+void launch_sym_draw(uint64_t seed, uint32_t epoch, int64_t start, int64_t count, uint32_t allowed, uint8_t *out,
+                     hipStream_t s);
 
 }  // namespace mapf

@@ -67,6 +67,22 @@ class GatherSpec(ctypes.Structure):
                 ("arrays", GatherArray * GATHER_MAX)]
 
 
+# mapf_gather_rows_sym's kinds (include/mapf.h: MAPF_GATHER_*)
+GATHER_KINDS = {"plain": 0, "obs": 1, "obs_bits": 2, "vec": 3, "action32": 4, "action64": 5, "cols": 6}
+
+
+class GatherSymArray(ctypes.Structure):
+    """include/mapf.h: mapf_gather_sym_array."""
+    _fields_ = [("src", P), ("dst", P), ("src_row_bytes", I64), ("dst_row_bytes", I64), ("kind", I32),
+                ("reserved", I32)]
+
+
+class GatherSymSpec(ctypes.Structure):
+    """include/mapf.h: mapf_gather_sym_spec."""
+    _fields_ = [("T", I32), ("B", I32), ("M", I64), ("rows", P), ("sym", P), ("N", I32), ("C", I32), ("F", I32),
+                ("count", I32), ("arrays", GatherSymArray * GATHER_MAX)]
+
+
 TUNING_FIELDS = ("roll_occ", "roll_group", "roll_fair", "roll_slack", "wide_nt", "wide_pipe", "wide_grid",
                  "wide_overlap", "wide_obs", "wide_epw", "wide_pair", "wide_slack", "wide_fair", "wide_prio",
                  "wide_bfsobs", "xcd_remap", "obs_envs", "step_block", "search_blocks", "band_blocks", "agent_lanes",
@@ -144,6 +160,17 @@ SIGNATURES = {
     "mapf_minibatch_rows": (ctypes.c_int, [ctypes.c_uint64, U32, I64, I64, I64, P, P]),
     "mapf_minibatch_rows_host": (ctypes.c_int, [ctypes.c_uint64, U32, I64, I64, I64, P]),
     "mapf_gather_rows": (ctypes.c_int, [ctypes.POINTER(GatherSpec), P]),
+    # grid symmetries (mapf.h: "Grid symmetries")
+    "mapf_sym_cell": (ctypes.c_int, [I32, I32, I32, I32, ctypes.POINTER(I32), ctypes.POINTER(I32)]),
+    "mapf_sym_action": (I64, [I32, I64]),
+    "mapf_sym_vec_host": (ctypes.c_int, [P, I64, I32, P]),
+    "mapf_sym_cols_host": (ctypes.c_int, [P, I64, I32, P]),
+    "mapf_sym_obs_host": (ctypes.c_int, [P, I64, I32, I32, I32, P]),
+    "mapf_sym_compose": (ctypes.c_int, [I32, I32]),
+    "mapf_sym_inverse": (ctypes.c_int, [I32]),
+    "mapf_sym_draw": (ctypes.c_int, [ctypes.c_uint64, U32, I64, I64, U32, P, P]),
+    "mapf_sym_draw_host": (ctypes.c_int, [ctypes.c_uint64, U32, I64, I64, U32, P]),
+    "mapf_gather_rows_sym": (ctypes.c_int, [ctypes.POINTER(GatherSymSpec), P]),
     "mapf_advantage_moments": (ctypes.c_int, [P, P, P, P, I32, P, P, P]),
     "mapf_normalize_advantages_stats": (ctypes.c_int, [P, P, P, P, P, P, P, I32, ctypes.c_double, I32, P]),
     "mapf_normalize_advantages_stats_dlam": (ctypes.c_int, [P, P, P, P, P, P, P, I32, P, I32, P]),

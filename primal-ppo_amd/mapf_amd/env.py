@@ -1231,3 +1231,143 @@ def gather_rows(srcs, T, B, rows, dsts):
         spec.arrays[a] = _lib.GatherArray(src.data_ptr(), dst.data_ptr(), row * src.element_size())
     _lib.check(_lib.lib().mapf_gather_rows(ctypes.byref(spec), _stream(dev)))
     return dsts
+
+
+def sym_draw(seed, epoch, start, count, allowed=0xFF, out=None, device=None):
+    """One grid symmetry g in 0..7 per element of the window [start, start + count) of the stream
+    (seed, epoch), uniform over the set bits of the mask `allowed` (mapf_sym_draw: 0xFF the whole group,
+    0x0F rotations only): a uint8 tensor [count].  Stateless like minibatch_rows, and like it
+    device="cpu" (or a CPU `out`) runs the host twin."""
+    start, count, allowed = int(start), int(count), int(allowed)
+    if out is not None:
+        device = out.device
+    device = torch.device("cuda" if device is None else device)
+    if out is None:
+        out = torch.empty(max(count, 0), dtype=torch.uint8, device=device)
+    _check(out, torch.uint8, max(count, 0), None, "out")
+    if not 0 <= allowed <= 0xFFFFFFFF:
+        raise ValueError(f"sym_draw: allowed {allowed:#x} is not an 8-bit mask")
+    seed, epoch = int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF
+    if device.type == "cpu":
+        _lib.check(_lib.lib().mapf_sym_draw_host(seed, epoch, start, count, allowed, _ptr(out)))
+    else:
+        _lib.check(_lib.lib().mapf_sym_draw(seed, epoch, start, count, allowed, _ptr(out), _stream(out.device)))
+    return out
+
+
+def gather_rows_sym(srcs, T, B, rows, dsts, kinds, sym=None, geometry=None):
+    """gather_rows with one grid symmetry per gathered row (mapf_gather_rows_sym, ONE launch): dsts[a][j]
+    is row rows[j] of srcs[a] transformed by sym[j] as kinds[a] says -- "plain" (bytes), "obs" (float
+    [N, C, F, F]), "obs_bits" (packed int32 [N, WPA] -> float [N, C, F, F], unpacked in the same pass),
+    "vec" (float [N, 4]), "action32" / "action64" (int [N]), "cols" (float [N, 5]: train_valid, ps).
+    sym: uint8 [M] on the device, g in 0..7 (sym_draw), or None for the identity; geometry = (N, C, F).
+    With sym=None the destinations hold gather_rows' bytes (unpack_obs' for "obs_bits").  Capturable."""
+    srcs, dsts, kinds = list(srcs), list(dsts), list(kinds)
+    if not (len(srcs) == len(dsts) == len(kinds)) or not 1 <= len(srcs) <= _lib.GATHER_MAX:
+        raise ValueError(f"gather_rows_sym: {len(srcs)} sources, {len(dsts)} destinations and {len(kinds)} kinds "
+                         f"(1..{_lib.GATHER_MAX} triples)")
+    if geometry is None or len(geometry) != 3:
+        raise ValueError("gather_rows_sym: geometry=(N, C, F) is required")
+    N, C, F = (int(x) for x in geometry)
+    T, B = int(T), int(B)
+    if T < 1 or B < 1:
+        raise ValueError("gather_rows_sym: T and B must be >= 1")
+    if not isinstance(rows, torch.Tensor) or rows.device.type != "cuda":
+        raise ValueError("gather_rows_sym: rows must be a tensor on the GPU")
+    dev, M = rows.device, rows.numel()
+    _check(rows, torch.int64, M, dev, "rows")
+    if M < 1:
+        raise ValueError("gather_rows_sym: no rows")
+    if sym is not None:
+        _check(sym, torch.uint8, M, dev, "sym")
+    spec = _lib.GatherSymSpec(T=T, B=B, M=M, rows=rows.data_ptr(), sym=None if sym is None else sym.data_ptr(),
+                              N=N, C=C, F=F, count=len(srcs))
+    for a, (src, dst, kind) in enumerate(zip(srcs, dsts, kinds)):
+        if kind not in _lib.GATHER_KINDS:
+            raise ValueError(f"gather_rows_sym: kind {kind!r} of array {a} is not one of {sorted(_lib.GATHER_KINDS)}")
+        if not isinstance(src, torch.Tensor) or not isinstance(dst, torch.Tensor):
+            raise TypeError(f"gather_rows_sym: triple {a} holds no pair of tensors")
+        want = {"obs": (torch.float32, torch.float32), "obs_bits": (torch.int32, torch.float32),
+                "vec": (torch.float32, torch.float32), "action32": (torch.int32, torch.int32),
+                "action64": (torch.int64, torch.int64), "cols": (torch.float32, torch.float32)}.get(kind, (src.dtype, src.dtype))
+        if (src.dtype, dst.dtype) != want or src.device != dev or dst.device != dev:
+            raise ValueError(f"gather_rows_sym: array {a} ({kind}): {src.dtype} on {src.device} -> {dst.dtype} on "
+                             f"{dst.device}, rows on {dev}")
+        if src.dim() < 2 or tuple(src.shape[:2]) != (T, B) or not src.is_contiguous():
+            raise ValueError(f"gather_rows_sym: source {a} must be a contiguous [T={T}, B={B}, ...] buffer, got "
+                             f"{tuple(src.shape)}")
+        row = src[0, 0].numel()
+        drow = N * C * F * F if kind == "obs_bits" else row
+        if dst.dim() < 1 or dst.shape[0] != M or dst.numel() != M * drow or not dst.is_contiguous():
+            raise ValueError(f"gather_rows_sym: destination {a} must be contiguous with {M} rows of {drow} elements, "
+                             f"got {tuple(dst.shape)}")
+        spec.arrays[a] = _lib.GatherSymArray(src.data_ptr(), dst.data_ptr(), row * src.element_size(),
+                                             drow * dst.element_size(), _lib.GATHER_KINDS[kind], 0)
+    _lib.check(_lib.lib().mapf_gather_rows_sym(ctypes.byref(spec), _stream(dev)))
+    return dsts
+
+
+def _sym_action(g, a):
+    """include/mapf.h, "Grid symmetries": the mirror swaps moves 1 and 3, a quarter turn takes move a to a - 1
+    (1 to 4); 0 stays (csrc/mapf_sym.h: sym_action is the rule, tests/test_sym_cpu.py compares)"""
+    if a == 0:
+        return 0
+    if g & 4 and a & 1:
+        a = 4 - a
+    return 1 + ((a - 1 - (g & 3)) & 3)
+
+
+_SYM_ACTION = [[_sym_action(g, a) for a in range(5)] for g in range(8)]
+
+
+def sym_apply(obs, vec, actions, cols, g):
+    """The grid symmetries in plain torch, for models off the GPU and as the reference of the kernels:
+    (obs [M, ..., F, F], vec [M, ..., 4], actions [M, ...] of any int dtype, cols [M, ..., 5]) transformed by
+    g -- one int for every row, or M of them (a sequence or tensor).  Any of the four may be None; numpy
+    arrays come back as numpy arrays.  Bit-equal to the host twins (mapf_sym_*_host)."""
+    import numpy as np
+    first = next((x for x in (obs, vec, actions, cols) if x is not None), None)
+    if first is None:
+        return None, None, None, None
+    M = first.shape[0]
+    gs = torch.as_tensor(g).reshape(-1).to("cpu", torch.int64) & 7
+    if gs.numel() == 1:
+        gs = gs.expand(M)
+    if gs.numel() != M:
+        raise ValueError(f"sym_apply: {gs.numel()} symmetries for {M} rows")
+    outs = []
+    for what, x in (("obs", obs), ("vec", vec), ("actions", actions), ("cols", cols)):
+        if x is None:
+            outs.append(None)
+            continue
+        was_numpy = isinstance(x, np.ndarray)
+        t = torch.from_numpy(x) if was_numpy else x
+        if t.shape[0] != M:
+            raise ValueError(f"sym_apply: {what} has {t.shape[0]} rows, expected {M}")
+        out = t.clone()
+        for gv in torch.unique(gs).tolist():
+            if gv == 0:
+                continue
+            sel = (gs == gv).nonzero().reshape(-1).to(t.device)
+            y = t[sel]
+            if what == "obs":
+                y = torch.rot90(torch.flip(y, (-1,)) if gv & 4 else y, gv & 3, (-2, -1))
+            elif what == "vec":
+                a, b = y[..., 0], y[..., 1]
+                if gv & 4:
+                    b = 0.0 - b
+                for _ in range(gv & 3):
+                    a, b = 0.0 - b, a
+                y = torch.stack((a, b, y[..., 2], y[..., 3]), dim=-1)
+            elif what == "actions":
+                table = torch.tensor(_SYM_ACTION[gv], dtype=y.dtype, device=y.device)
+                inside = (y >= 0) & (y <= 4)
+                y = torch.where(inside, table[y.clamp(0, 4).long()], y)
+            else:
+                perm = torch.tensor(_SYM_ACTION[gv], device=y.device)
+                z = torch.empty_like(y)
+                z[..., perm] = y
+                y = z
+            out[sel] = y
+        outs.append(out.numpy() if was_numpy else out)
+    return tuple(outs)

@@ -371,7 +371,7 @@ class Model:
         stats = upd.stats.cpu().numpy()       # one device -> host copy
         return [np.asarray(v) for v in stats] + [self.lagrange.get_lagrangian_param()]
 
-    def train_rows(self, runner, rows, episode_cost, checked=False):
+    def train_rows(self, runner, rows, episode_cost, checked=False, sym=None):
         """One update on the env-major rows `rows` of runner's last rollout (a DeviceRunner; row r =
         env r // T, step r % T, runner.EnvMajorRows' order), read straight from its device buffers:
         _train_device with _DeviceUpdate.load_rows in place of load -- one HIP launch gathers the nine
@@ -381,7 +381,10 @@ class Model:
         env.minibatch_rows) or any driver-style host index; range-checked as runner._row_index does
         unless checked=True says the caller has (device rows then cost no read-back).  Returns the
         same 12 stats as train().  A model that is not on the GPU, or has fused_loss off, trains
-        through train() on torch-indexed rows."""
+        through train() on torch-indexed rows.
+        sym: one grid symmetry per row, as in imitate_rows: the actions are remapped and old_ps and
+        train_valid have their columns permuted with the observation and vec, so the ratio is taken
+        against the permuted old_ps (opt-in: INTEGRATION.md)."""
         from .runner import _row_index
         T, B = runner.T, runner.env.B
         dev = self.device
@@ -391,9 +394,15 @@ class Model:
             rows, _ = _row_index(rows, T * B, dev)
         if dev.type != "cuda" or not self.fused_loss:
             mb = runner.batch()
-            return self.train(mb.observations[rows], mb.vectors[rows], mb.returns[rows], mb.costReturns[rows],
-                              mb.values[rows], mb.costValues[rows], mb.actions[rows], mb.ps[rows],
-                              mb.hiddenState[rows], mb.trainValid[rows], episode_cost)
+            o, v, a, p, tv = (mb.observations[rows], mb.vectors[rows], mb.actions[rows], mb.ps[rows],
+                              mb.trainValid[rows])
+            if sym is not None:
+                from .env import sym_apply
+                g = self._sym_rows(sym, len(rows), "cpu")
+                o, v, a, p = sym_apply(o, v, a, p, g)
+                tv = sym_apply(None, None, None, tv, g)[3]
+            return self.train(o, v, mb.returns[rows], mb.costReturns[rows], mb.values[rows], mb.costValues[rows],
+                              a, p, mb.hiddenState[rows], tv, episode_cost)
         if isinstance(rows, np.ndarray):
             rows = torch.from_numpy(rows)
         rows = rows.to(dev, non_blocking=True).contiguous()
@@ -410,7 +419,8 @@ class Model:
         distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         if self.distributed_update is not None:
             distributed = bool(self.distributed_update) and dist.is_available() and dist.is_initialized()
-        upd.load_rows(buffers, T, B, rows, coef=self._loss_coef(lam), lam=lam, packed=(C_, F_) if packed else None)
+        upd.load_rows(buffers, T, B, rows, coef=self._loss_coef(lam), lam=lam, packed=(C_, F_) if packed else None,
+                      sym=self._sym_rows(sym, M, dev))
         return self._run_device_update(upd, episode_cost, distributed)
 
     # ------------------------------------------------------------ imitation
@@ -487,7 +497,16 @@ class Model:
         self.network.weights_updated()        # replays bump no tensor version: drop the fp16 acting copies
         return [np.asarray(v) for v in upd.stats.cpu().numpy()]       # one device -> host copy
 
-    def imitate_rows(self, source, rows, checked=False):
+    def _sym_rows(self, sym, M, device):
+        """sym= of train_rows / imitate_rows: None, or one grid symmetry per row -> uint8 [M] on `device`"""
+        if sym is None:
+            return None
+        s = torch.as_tensor(sym)
+        if s.dim() != 1 or s.numel() != M or s.dtype.is_floating_point:
+            raise ValueError(f"sym: expected {M} integers in 0..7, one per row")
+        return s.to(device=device, dtype=torch.uint8, non_blocking=True).contiguous()
+
+    def imitate_rows(self, source, rows, checked=False, sym=None):
         """One imitation update on the env-major rows `rows` of source's last rollout, the twin of
         train_rows: one gather launch (env.gather_rows) moves the rows' observations (packed rows are
         unpacked by one more launch, as _DeviceUpdate.load_rows does), vectors and expert actions into
@@ -495,7 +514,10 @@ class Model:
         slots, slot t = the state the expert saw at step t), vec and expert_actions (int32 [T, B, N]) --
         imitation.DemoRunner, or a DeviceRunner built with expert=.  rows as in train_rows.  Returns
         the 4 stats (loss, grad norm, agreement, expert probability).  A model that is not on the GPU,
-        or has fused_loss off, trains through imitation_train() on torch-indexed rows (2 stats)."""
+        or has fused_loss off, trains through imitation_train() on torch-indexed rows (2 stats).
+        sym: one grid symmetry g in 0..7 per row (env.sym_draw; a uint8 device tensor costs no copy) --
+        observation, vec and expert action are transformed together in the one gather launch
+        (env.gather_rows_sym; the fallback applies env.sym_apply).  None: the rows as they are."""
         from .runner import _row_index
         T, B = source.T, source.env.B
         dev = self.device
@@ -511,13 +533,19 @@ class Model:
         if dev.type != "cuda" or not self.fused_loss:
             r = rows.to(obs.device)
             ts, bs = r % T, r // T
-            return self.imitation_train(obs[ts, bs], vec[ts, bs], act[ts, bs], None)
+            o, v, a = obs[ts, bs], vec[ts, bs], act[ts, bs]
+            if sym is not None:
+                from .env import sym_apply, unpack_obs
+                if packed:
+                    o = unpack_obs(o.contiguous(), source.env.C, source.env.F)
+                o, v, a, _ = sym_apply(o, v, a, None, self._sym_rows(sym, r.numel(), "cpu"))
+            return self.imitation_train(o, v, a, None)
         rows = rows.to(dev, non_blocking=True).contiguous()
         M = rows.numel()
         C_, F_ = source.env.C, source.env.F
         obs_shape = (M, obs.shape[2], C_, F_, F_) if packed else (M,) + tuple(obs.shape[2:])
         upd = self._device_imitation(obs_shape, (M,) + tuple(vec.shape[2:]), (M,) + tuple(act.shape[2:]))
-        upd.load_rows((obs, vec, act), T, B, rows, packed=(C_, F_) if packed else None)
+        upd.load_rows((obs, vec, act), T, B, rows, packed=(C_, F_) if packed else None, sym=self._sym_rows(sym, M, dev))
         return self._run_device_imitation(upd)
 
     def _finish_update(self, all_loss, policy_loss, entropy, critic_loss, valid_loss, cost_critic_loss, cost_loss,
@@ -629,15 +657,27 @@ class _DeviceUpdate:
         h = torch.tensor(list(coef) + [lam, lam + 1.0], dtype=torch.float64).float()
         self.dyn.copy_(h.pin_memory() if torch.cuda.is_available() else h, non_blocking=True)
 
-    def load_rows(self, buffers, T, B, rows, coef, lam, packed=None):
+    def load_rows(self, buffers, T, B, rows, coef, lam, packed=None, sym=None):
         """load() straight from a rollout's t-major [T, B, ...] device buffers: buffers = (obs, vec,
         returns, cost returns, values, cost values, actions int64, ps, train_valid), rows = int64
         device tensor of env-major row ids in [0, B * T), one per minibatch row.  One gather launch
         (env.gather_rows) fills the nine static inputs; with the coefficients' copy that is two
         launches per minibatch.  packed = (C, F): buffers[0] is the packed observation buffer (int32
         [T, B, N, WPA]); its rows (N * WPA * 4 bytes each) are gathered into a staging tensor by the same
-        launch and unpacked into the static float input (env.unpack_obs: one more launch)."""
+        launch and unpacked into the static float input (env.unpack_obs: one more launch).
+        sym: uint8 device tensor, one grid symmetry per row (env.sym_draw) -- ONE env.gather_rows_sym
+        launch then fills the inputs transformed (packed rows too: no staging, no unpack launch): the
+        actions remapped, old_ps and train_valid with their columns permuted."""
         from .env import gather_rows, unpack_obs
+        if sym is not None:
+            from .env import gather_rows_sym
+            N, F = self.obs.shape[1], self.obs.shape[-1]
+            gather_rows_sym(buffers, T, B, rows, (self.obs, self.vec, self.ret, self.cret, self.v, self.cv, self.action,
+                                                  self.old_ps, self.tv),
+                            ("obs_bits" if packed is not None else "obs", "vec", "plain", "plain", "plain", "plain",
+                             "action64", "cols", "cols"), sym=sym, geometry=(N, self.obs.shape[2], F))
+            self._load_dyn(coef, lam)
+            return
         obs_dst = self.obs
         if packed is not None:
             shape = (rows.numel(),) + tuple(buffers[0].shape[2:])
@@ -817,10 +857,17 @@ class _DeviceImitation(_DeviceUpdate):
         self.vec.copy_(vector.reshape(self.vec.shape), non_blocking=True)
         self.action.copy_(action.reshape(self.action.shape), non_blocking=True)      # int64 -> int32 in the copy
 
-    def load_rows(self, buffers, T, B, rows, packed=None):
+    def load_rows(self, buffers, T, B, rows, packed=None, sym=None):
         """load() straight from t-major [T, B, ...] device buffers (observations or packed observations,
-        vec, expert actions int32) in one gather launch; packed = (C, F): as _DeviceUpdate.load_rows."""
+        vec, expert actions int32) in one gather launch; packed = (C, F) and sym: as
+        _DeviceUpdate.load_rows (with sym, one env.gather_rows_sym launch and nothing else)."""
         from .env import gather_rows, unpack_obs
+        if sym is not None:
+            from .env import gather_rows_sym
+            gather_rows_sym(buffers, T, B, rows, (self.obs, self.vec, self.action),
+                            ("obs_bits" if packed is not None else "obs", "vec", "action32"), sym=sym,
+                            geometry=(self.obs.shape[1], self.obs.shape[2], self.obs.shape[-1]))
+            return
         obs_dst = self.obs
         if packed is not None:
             shape = (rows.numel(),) + tuple(buffers[0].shape[2:])

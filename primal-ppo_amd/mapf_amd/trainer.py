@@ -18,6 +18,10 @@ imitate(source) walks the same kind of epochs over a source of demonstrations (i
 or a DeviceRunner built with expert=) through Model.imitate_rows, and fit(n, demo=, demonstration_prob=)
 draws per rollout which of the two it is (TrainingParameters.DEMONSTRATION_PROB).
 
+augment=MASK (off by default) draws one of the square's eight symmetries per minibatch row
+(env.sym_draw, keyed by the trainer's seed and epoch counter) and passes it down as sym=: the gather
+then transforms observation, vec, action and the per-action columns together (env.gather_rows_sym).
+
 Several ranks: every rank must hold the same B and T (Model's distributed update needs equal
 minibatch counts on every rank); each rank shuffles its own rollout.
 """
@@ -25,11 +29,11 @@ import numpy as np
 import torch
 
 from .config import TrainingParameters
-from .env import minibatch_rows
+from .env import minibatch_rows, sym_draw
 
 
 class DeviceTrainer:
-    def __init__(self, runner, model, minibatch=None, n_epochs=None, seed=0):
+    def __init__(self, runner, model, minibatch=None, n_epochs=None, seed=0, augment=None):
         self.runner, self.model = runner, model
         self.minibatch = TrainingParameters.MINIBATCH_SIZE if minibatch is None else int(minibatch)
         self.n_epochs = TrainingParameters.N_EPOCHS if n_epochs is None else int(n_epochs)
@@ -39,6 +43,21 @@ class DeviceTrainer:
         if not 1 <= self.minibatch <= self.n:
             raise ValueError(f"minibatch {self.minibatch} for a rollout of {self.n} rows")
         self.rows = None                        # the minibatch's row ids: one device tensor, reused
+        # grid-symmetry augmentation: the mask of allowed symmetries (env.sym_draw: 0xFF the whole group,
+        # 0x0F rotations only); None or 0x01 (identity only) = off, nothing is drawn and nothing changes
+        self.augment = None if augment is None or int(augment) == 0x01 else int(augment)
+        if self.augment is not None and not 1 <= self.augment <= 0xFF:
+            raise ValueError(f"augment {augment!r} is not a mask of the eight symmetries (1..0xFF)")
+        self.sym = None                         # the minibatch's symmetries: one device tensor, reused
+
+    def _sym_arg(self, k, M):
+        """the sym= argument of minibatch k's train_rows / imitate_rows: nothing with augmentation off (a
+        model without the argument still serves), else window [k * M, (k + 1) * M) of the epoch's draws"""
+        if self.augment is None:
+            return {}
+        if self.sym is None:
+            self.sym = torch.empty(M, dtype=torch.uint8, device=self.rows.device)
+        return {"sym": sym_draw(self.seed, self.epoch_counter, k * M, M, self.augment, out=self.sym)}
 
     def minibatches_per_epoch(self):
         return self.n // self.minibatch
@@ -57,7 +76,7 @@ class DeviceTrainer:
             for k in range(self.minibatches_per_epoch()):
                 minibatch_rows(self.n, self.seed, self.epoch_counter, k * M, M, out=self.rows)
                 mb_loss.append(self.model.train_rows(self.runner, self.rows, performance.episodeCostReward,
-                                                     checked=True))
+                                                     checked=True, **self._sym_arg(k, M)))
             self.epoch_counter += 1
         return mb_loss
 
@@ -78,7 +97,7 @@ class DeviceTrainer:
         for _ in range(int(n_epochs)):
             for k in range(n // M):
                 minibatch_rows(n, self.seed, self.epoch_counter, k * M, M, out=self.rows)
-                mb_loss.append(self.model.imitate_rows(source, self.rows, checked=True))
+                mb_loss.append(self.model.imitate_rows(source, self.rows, checked=True, **self._sym_arg(k, M)))
             self.epoch_counter += 1
         return mb_loss
 

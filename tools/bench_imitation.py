@@ -19,6 +19,11 @@
 
 --noise EPS puts action noise eps on the demonstrations (DemoRunner(noise=...), mapf_set_action_noise): the rollouts
 play a uniform random action with probability eps, the labels stay the planner's.  Part 4's labels are clean.
+
+--augment MASK trains part 3 with grid-symmetry augmentation (DeviceTrainer(augment=MASK): 0xFF the whole group,
+0x0F rotations only, 0x01 identity only = off) and adds two lines: the time of one whole imitate_rows call
+(row gather + captured update) without and with a symmetry per row, alternated, and the agreement with PIBT on
+--heldout-rows rows of one more rollout that is not trained on and not augmented (dropout off).
 """
 import argparse
 import json
@@ -53,6 +58,9 @@ def main():
     ap.add_argument("--noise", type=float, default=None, help="action noise eps in [0, 1] on the demonstrations")
     ap.add_argument("--own-steps", type=int, default=0, help="part 4: steps the learner acts, the planner labelling (0: skip)")
     ap.add_argument("--skip-timing", action="store_true", help="leave out part 2, the update times")
+    ap.add_argument("--augment", type=lambda x: int(x, 0), default=None,
+                    help="mask of grid symmetries drawn per minibatch row in part 3 (0xFF: all eight)")
+    ap.add_argument("--heldout-rows", type=int, default=4096, help="--augment: rows of the held-out agreement")
     args = ap.parse_args()
     import mapf_amd  # noqa: F401
     import torch
@@ -115,7 +123,8 @@ def main():
     # ---- 3. learning curve on PIBT demonstrations (the envs run on from rollout to rollout: new states every time)
     env.reset_seeded(generate_warehouse(S, S), seed=7)
     model = Model(0, "cuda", global_model=True, numChannel=C, num_agents=N, fov=F)
-    tr = DeviceTrainer(demo, model, minibatch=256, n_epochs=1, seed=args.seed)
+    tr = DeviceTrainer(demo, model, minibatch=256, n_epochs=1, seed=args.seed,
+                       **({} if args.augment is None else {"augment": args.augment}))
     curve, k = [], 0
     while k < args.updates:
         demo.run()
@@ -131,6 +140,25 @@ def main():
                           "expert_prob": round(statistics.mean(x[3] for x in w), 4)}), flush=True)
     assert not env.counters()[:8 if not env.action_noise else 1].any()      # (noise boxes agents in: counters 1, 2 may count)
 
+    # ---- 3b. --augment: the held-out agreement (the whole imitate_rows call is timed last: it trains on)
+    if args.augment is not None:
+        from mapf_amd.env import minibatch_rows, sym_draw, unpack_obs
+        n_rows = T * B
+        demo.run()                                   # states no update has seen
+        held = min(args.heldout_rows, n_rows) // 256 * 256
+        hits, was_training = 0.0, model.network.training
+        model.network.eval()
+        with torch.no_grad():
+            for k in range(held // 256):
+                r = minibatch_rows(n_rows, args.seed + 1, 0, k * 256, 256)
+                ts, bs = r % T, r // T
+                obs = unpack_obs(demo.obs_bits[:T][ts, bs].contiguous(), C, F)
+                ps = model.network(obs, demo.vec[:T][ts, bs], None)[0]
+                hits += float((ps.argmax(-1).to(torch.int32) == demo.expert_actions[ts, bs]).float().mean())
+        model.network.train(was_training)
+        print(json.dumps({"part": "heldout", "augment": args.augment, "updates": len(curve), "rows": held,
+                          "agreement": round(hits / max(1, held // 256), 4)}), flush=True)
+
     # ---- 4. the learner on its own states, labelled by the planner (no noise: the sampler explores)
     if args.own_steps > 0:
         from mapf_amd.runner import DeviceRunner
@@ -144,6 +172,19 @@ def main():
                           "agreement": round(float(agree), 4),
                           "goals_per_env_step": round(float(runner.goals.sum()) / (args.own_steps * B), 4),
                           "agent_collisions_per_env_step": round(float((runner.status == -3).sum()) / (args.own_steps * B), 4)}),
+              flush=True)
+
+    # ---- 5. --augment: the whole imitate_rows call without and with a symmetry per row
+    if args.augment is not None:
+        rows = minibatch_rows(n_rows, args.seed, 0, 0, 256)
+        sym = sym_draw(args.seed, 0, 0, 256, args.augment if args.augment != 1 else 0xFF)
+        t_plain, t_sym = [], []
+        for _ in range(args.reps):                   # alternated
+            t_plain += timed(lambda: model.imitate_rows(demo, rows, checked=True), 1)
+            t_sym += timed(lambda: model.imitate_rows(demo, rows, checked=True, sym=sym), 1)
+        print(json.dumps({"part": "imitate_rows", "rows": 256, "agents": N,
+                          "ms": {k: {"median": round(statistics.median(x), 3), "min": round(min(x), 3),
+                                     "max": round(max(x), 3)} for k, x in (("sym=None", t_plain), ("sym", t_sym))}}),
               flush=True)
 
 
