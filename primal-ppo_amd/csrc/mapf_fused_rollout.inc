@@ -231,7 +231,9 @@
             float *ob;
             if constexpr (ST == OBS_BITS) ob = R.obs + s * BN * (size_t)obs_bits_words(E.C, E.F);
             else ob = R.obs + s * BN * E.C * E.F * E.F;
-            obs_emit<false, ST, BAND>(E, L, ob, R.vec + s * BN * 4, g, b0, false, band_mask);
+            // the store loop in groups of four (obs_store_wave_nt); PIBT's kernels stand at their register
+            // limit and spill with it: they keep the loop of one store per trip
+            obs_emit<false, ST, BAND, PIBT ? 0 : OBS_NT_GROUP>(E, L, ob, R.vec + s * BN * 4, g, b0, false, band_mask);
             // SPARSE: what the slot holds now, for the next launch over it (the stream is whole until the
             // next step's obs_wave_init); ordinary vector stores of lanes 0, 4, .., 60
             if constexpr (BAND == OBS_SPARSE) obs_sparse_store(g.stream, L.swe, sp_words, (int)(threadIdx.x & 63));

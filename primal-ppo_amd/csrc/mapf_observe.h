@@ -284,7 +284,8 @@ __device__ inline void obs_sparse_store(const uint32_t *stream, int swe, uint32_
 // the uint32 buffer; skip_band and band_mask are ignored: nothing else writes a packed buffer).  BAND: the one-wave table loop skips the stores of `band_mask`
 // (bit k = this lane's iteration k, obs_band_skip_mask); BAND = 0 compiles the test out; BAND = OBS_SPARSE:
 // `band_mask` is obs_sparse_old's word (all ones: store everything) and the loop stores the pieces that
-// were non-zero by it or are non-zero now.
+// were non-zero by it or are non-zero now.  GN (with OBS_NT): OBS_NT_GROUP, the one-wave table loop runs in
+// groups of that many stores (obs_store_wave_nt, below: the pair-lane kernels but PIBT's); 0, one store per trip.
 // The threads that observe a run of the workgroup's envs together: the whole
 // workgroup (workgroup barriers) or one wave observing its own env (per_env
 // layout; wave-level ordering only).
@@ -326,7 +327,97 @@ __device__ inline ObsGroup obs_wave_init(const DevEnv &e, const ObsLds &L, int l
     return g;
 }
 
-template <bool BFSCH = true, int ST = OBS_PLAIN, int BAND = 0>
+// ---- the one-wave table loop of phase 4 with streaming stores (obs_emit<.., OBS_NT, ..>) ----
+// Lane l stores float4 l + 64k of the env's slice at iteration k (obs_emit's comment).  The slice has
+// `q` float4s, a wave-uniform count, so the loop is counted in scalars and runs in groups of
+// OBS_NT_GROUP iterations: the group's stream words are read first (constant LDS offsets, 32 B apart),
+// then its skip tests and table reads, then its stores -- one LDS latency per kind and group instead
+// of two per store.  The stores are buffer stores through a descriptor of the slice: base = the
+// slice, num_records = its bytes, so the hardware's range check drops the lanes past the slice in the
+// last iteration and nothing can land outside it; the lane's byte offset 16 l + 4096 g stays in one
+// VGPR and the iteration's 1 KiB step is the instruction's immediate offset.  A skipped store (the
+// clean band, a sparse piece of zeros over zeros) takes an offset out of range instead of a branch.
+// The LDS reads are not predicated: in the last iteration the lanes past q read up to 7 words past the
+// env's stream (the next env's stream or the occupancy words after it, inside the workgroup's LDS) and, in
+// the sparse form, make a skip test of them.  That is harmless only because the range check drops those
+// lanes' stores whatever the test says; the loop of one store per trip never touched those words.
+// Cache bits sc1 nt: streamed AND not kept in the XCD's L2 (MI355X_MICROARCH: sc1 stores drop the
+// line), so the lines the step outputs merge in stay resident.  A/B on one box: c2 slots 21.3 ->
+// 20.3 us per step, c5 (446 MB in place) 89.1 -> 86.8 vs nt alone; plain 23.7, sc1 alone 21.0 (taken
+// with the loop of one store per trip in every kernel: tools/ab_libs.sh, MAPF_SLOT_STORE in obs_emit).
+constexpr int OBS_NT_GROUP = 4;                    // 4 x 1 KiB: the immediate offset's 12 bits
+constexpr uint32_t OBS_NT_DROP = 0x80000000u;      // a byte offset no slice reaches (+ 3 KiB: no wrap)
+constexpr int OBS_NT_AUX = 16 | 2;                 // raw buffer store's aux: sc1 (16), nt (2, the former slc)
+// experiment build: MAPF_STORE_PRED=1 skips by EXEC (a branch around the store) instead
+#ifndef MAPF_STORE_PRED
+#define MAPF_STORE_PRED 0
+#endif
+
+// One group: iterations [0, cnt) from `swp` / `voff` on.  WHOLE: cnt == GN, known to the compiler.
+// `mask`: the group's skip bits -- OBS_BAND bit j = iteration j; OBS_SPARSE obs_sparse_old's layout,
+// bit (j & 1) * 16 + (j >> 1) = iteration j's old bit (0: the piece held zeros).
+template <int BAND, bool WHOLE, int GN>
+__device__ __forceinline__ void obs_nt_group(__amdgpu_buffer_rsrc_t rs, const float4 *lut, const uint32_t *swp, int sh,
+                                             int hsh, uint32_t voff, uint32_t mask, int cnt) {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    uint32_t sw[GN], vo[GN];
+    float4 f[GN];
+#pragma unroll
+    for (int j = 0; j < GN; ++j) sw[j] = (WHOLE || j < cnt) ? swp[8 * j] : 0u;
+#pragma unroll
+    for (int j = 0; j < GN; ++j) {
+        bool skip = false;
+        if constexpr (BAND == OBS_BAND) skip = (mask >> j) & 1u;
+        // the piece's 16 bits are the lane's half of the word
+        if constexpr (BAND == OBS_SPARSE)
+            skip = (__builtin_amdgcn_ubfe(sw[j], hsh, 16) | __builtin_amdgcn_ubfe(mask, (j & 1) * 16 + (j >> 1), 1)) == 0;
+        vo[j] = skip ? OBS_NT_DROP : voff;
+        // opaque: `+ 1024 j` below stays the store's immediate offset (the compiler would otherwise move
+        // the addition into both arms of the select: a VALU add per store and four registers of constants)
+        if constexpr (BAND != 0) asm("" : "+v"(vo[j]));
+    }
+#pragma unroll
+    for (int j = 0; j < GN; ++j)
+        if (WHOLE || j < cnt) f[j] = lut[__builtin_amdgcn_ubfe(sw[j], sh, 4)];
+#pragma unroll
+    for (int j = 0; j < GN; ++j) {
+        if (!(WHOLE || j < cnt)) continue;
+        const v4u d = {__float_as_uint(f[j].x), __float_as_uint(f[j].y), __float_as_uint(f[j].z), __float_as_uint(f[j].w)};
+#if MAPF_STORE_PRED
+        if (vo[j] != OBS_NT_DROP) __builtin_amdgcn_raw_buffer_store_b128(d, rs, voff + 1024u * j, 0, OBS_NT_AUX);
+#else
+        __builtin_amdgcn_raw_buffer_store_b128(d, rs, vo[j] + 1024u * j, 0, OBS_NT_AUX);
+#endif
+    }
+}
+
+// The whole slice: `dst` its first float (16-B aligned), `q` its float4s; every lane of the wave is
+// active and holds the same `dst` and `q` (the wave's env).  `swp` / `sh` / `hsh`: the lane's stream
+// word pointer, nibble shift and half-word shift; BAND and `band_mask` as obs_emit's.
+template <int BAND, int GN>
+__device__ __forceinline__ void obs_store_wave_nt(const float4 *lut, const uint32_t *swp, int sh, int hsh, float *dst, int q,
+                                                  int lane, uint32_t band_mask) {
+    // the descriptor out of values the compiler knows to be uniform (the env index comes from
+    // threadIdx): otherwise every store is wrapped in a loop over the descriptor's values
+    const uintptr_t a = reinterpret_cast<uintptr_t>(dst);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32));
+    q = __builtin_amdgcn_readfirstlane(q);
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((uintptr_t)hi << 32) | lo), 0, q * 16, 0x00020000);
+    const int iters = (q + 63) >> 6;
+    uint32_t voff = (uint32_t)lane * 16u;
+    static_assert(GN == OBS_NT_GROUP, "an even group (the sparse mask's layout) within the immediate offset");
+    for (int g = 0; g < iters / GN; ++g) {
+        obs_nt_group<BAND, true, GN>(rs, lut, swp, sh, hsh, voff, band_mask, GN);
+        swp += 8 * GN;
+        voff += 1024u * GN;
+        band_mask >>= BAND == OBS_SPARSE ? GN / 2 : GN;
+    }
+    if (iters % GN) obs_nt_group<BAND, false, GN>(rs, lut, swp, sh, hsh, voff, band_mask, iters % GN);
+}
+
+template <bool BFSCH = true, int ST = OBS_PLAIN, int BAND = 0, int GN = 0>
 __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restrict__ obs, float *__restrict__ vec,
                                 const ObsGroup &G, int b0, bool skip_band = false, uint32_t band_mask = 0) {
     using namespace obsd;
@@ -518,6 +609,10 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
         // 16-entry LDS table L.lut: one 1 KiB store per wave instruction, constant step.
         const int sh = (tid & 7) * 4;
         const uint32_t *swp = stream + (tid >> 3);
+        if constexpr (ST == OBS_NT && GN != 0) {
+            obs_store_wave_nt<BAND, GN>(L.lut, swp, sh, (tid & 4) * 4, dst, (K * CFF) >> 2, tid, band_mask);
+            return;
+        }
         float4 *dp = reinterpret_cast<float4 *>(dst) + tid;
         [[maybe_unused]] int it = 0;          // OBS_SPARSE: the iteration
 #pragma unroll 4
@@ -531,31 +626,30 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
                 skip = (__builtin_amdgcn_ubfe(sw, (tid & 4) * 4, 16) | __builtin_amdgcn_ubfe(band_mask, (it & 1) * 16 + (it >> 1), 1)) == 0;
             if (skip) {
                 // inside the clean zero band, or a piece of zeros over zeros: nothing to store
-            } else if constexpr (ST == OBS_NT) {   // streaming stores (rollout slot buffers: not re-read by this launch)
+            } else if constexpr (ST == OBS_NT) {   // streaming stores, one per trip (GN = 0: the wide and the PIBT kernels)
+                // (an asm x4 store ends with s_nop 1: the compiler's next instruction may write the data registers)
                 typedef float v4f __attribute__((ext_vector_type(4)));
 #if defined(MAPF_SLOT_STORE) && MAPF_SLOT_STORE == 1     // store-policy experiment: nt only (round 2's)
                 __builtin_nontemporal_store(v4f{f.x, f.y, f.z, f.w}, reinterpret_cast<v4f *>(dp));
 #elif defined(MAPF_SLOT_STORE) && MAPF_SLOT_STORE == 2   // store-policy experiment: sc1 only
-                asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
+                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
 #elif defined(MAPF_SLOT_STORE) && MAPF_SLOT_STORE == 3   // store-policy experiment: plain
                 *dp = f;
 #else
-                // nt sc1: streamed AND not kept in the XCD's L2 (MI355X_MICROARCH: sc1 stores
-                // drop the line), so the lines the step outputs merge in stay resident.  A/B on
-                // one box: c2 slots 21.3 -> 20.3 us per step, c5 (446 MB in place) 89.1 -> 86.8
-                // vs nt alone; plain 23.7, sc1 alone 21.0 (tools/ab_libs.sh, MAPF_SLOT_STORE)
-                asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
+                // nt sc1 (obs_store_wave_nt's comment has the A/B; tools/ab_libs.sh, MAPF_SLOT_STORE: these arms
+                // cover the kernels of this loop, c4 / c5 among them; the grouped loop's bits are OBS_NT_AUX)
+                asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
 #endif
             } else {
 #if defined(MAPF_INPLACE_STORE) && MAPF_INPLACE_STORE == 1      // store-policy experiment: sc1
                 typedef float v4f __attribute__((ext_vector_type(4)));
-                asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
+                asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
 #elif defined(MAPF_INPLACE_STORE) && MAPF_INPLACE_STORE == 2    // store-policy experiment: nt sc1
                 typedef float v4f __attribute__((ext_vector_type(4)));
-                asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
+                asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
 #elif defined(MAPF_INPLACE_STORE) && MAPF_INPLACE_STORE == 3    // store-policy experiment: sc0 sc1
                 typedef float v4f __attribute__((ext_vector_type(4)));
-                asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
+                asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(dp), "v"(v4f{f.x, f.y, f.z, f.w}) : "memory");
 #else
                 *dp = f;
 #endif
