@@ -8,6 +8,12 @@
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int E = 4;                     // envs per workgroup, one per wave
     constexpr bool TAPE = rollout_pol(POL) == ROLLOUT_TAPE, DESCENT = rollout_pol(POL) == ROLLOUT_DESCENT, PIBT = rollout_pol(POL) == ROLLOUT_PIBT;
+    // LEAN: the step loop's forms that save VALU issue (DESIGN.md 9s): the map rows copied to LDS once, the
+    // stream zeroed in uint4s, phases 1-3 of the observation in the one-wave form, the slot's offset added in
+    // the storing lanes.  Not PIBT's kernels, which stand at their register limit (122-128 VGPRs) and would
+    // take scratch, and not the kernels with plain observation stores (in place), which measured slower with
+    // them: both keep the code they had.
+    constexpr bool LEAN = !PIBT && ST != OBS_PLAIN;
     constexpr bool NOISE = rollout_pol_noise(POL);      // DESCENT / PIBT with action noise: an instantiation of its own
     // XCD-aware env order: workgroups are dealt round-robin over the 8 XCDs, so workgroup w
     // takes env block (w % 8) * (grid / 8) + w / 8 -- each XCD owns one contiguous range of
@@ -84,11 +90,11 @@
             band_mask = obs_band_skip_mask(e, MAPF_BAND_UNIT, (size_t)(ro.obs + (size_t)(b0 + le) * e.N * e.C * e.F * e.F),
                                            (int)(threadIdx.x & 63));
     }
-    if constexpr (PERF) {
-        // the env's map rows in LDS, once (the observing forms copy them in obs_wave_init at every step):
-        // the wave's searches read them.  Lane k holds word k: rowsz <= 64 (regmap_fits, which
-        // rollout_fusable requires; obs_wave_init's rule)
-        if (le < nenv && (int)(threadIdx.x & 63) < L.rowsz) L.mapc[(size_t)le * L.rowsz + (threadIdx.x & 63)] = mreg;
+    // the env's map rows in LDS, once: the map does not change within a launch, the observation and the
+    // wave's searches read them at every step.  Lane k holds word k: rowsz <= 64 (regmap_fits, which
+    // rollout_fusable requires)
+    if constexpr (PERF || LEAN) {
+        if (le < nenv) obs_wave_map(L, le, mreg);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
     }
@@ -199,22 +205,26 @@
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
         }
+        // LEAN: the slot's offset goes into the head lanes' store indices (step_pairs_env's `so`, `sb`), not
+        // into nine bumped 64-bit pointers per step
         StepOut o = PERF ? StepOut{} : R.out;
-        if (o.status) o.status += s * BN;
-        if (o.reward) o.reward += s * BN;
-        if (o.shadow_goals) o.shadow_goals += s * E.B;
-        if (o.cost) o.cost += s * BN;
-        if (o.train_valid) o.train_valid += s * BN * NA;
-        if (o.actions_fixed) o.actions_fixed += s * BN;
-        if (o.goals_reached) o.goals_reached += s * BN;
-        if (o.constraints) o.constraints += s * BN;
-        if (o.reward_total) o.reward_total += s * BN;
+        if constexpr (!LEAN) {
+            if (o.status) o.status += s * BN;
+            if (o.reward) o.reward += s * BN;
+            if (o.shadow_goals) o.shadow_goals += s * E.B;
+            if (o.cost) o.cost += s * BN;
+            if (o.train_valid) o.train_valid += s * BN * NA;
+            if (o.actions_fixed) o.actions_fixed += s * BN;
+            if (o.goals_reached) o.goals_reached += s * BN;
+            if (o.constraints) o.constraints += s * BN;
+            if (o.reward_total) o.reward_total += s * BN;
+        }
         PairsDeferred dfr;
         [[maybe_unused]] StepVals pv;
         step_pairs_env<8, !PERF, true, true, TAPE || DESCENT || PIBT, PERF>(
             E, TAPE ? trow + (size_t)(t & (TAPE_K - 1)) * 8 : (DESCENT || PIBT ? trow : (PERF && !R.actions ? nullptr : R.actions + s * BN)), o,
             TAPE || DESCENT || PIBT ? 1u : 3u, 0,
-            blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs, PERF ? &pv : nullptr);
+            blk * 256 + qt, L, b0, RegMap{mreg, true}, dfr, &rs, PERF ? &pv : nullptr, LEAN ? s * BN : 0, LEAN ? s * (size_t)E.B : 0);
         if constexpr (PERF) {
             if (le < nenv) {
                 perf_acc_step<8>(pacc, pv, E.N, (int)(threadIdx.x & 63));
@@ -222,7 +232,7 @@
             }
         } else
         if (le < nenv) {
-            const ObsGroup g = obs_wave_init(E, L, le, mreg);
+            const ObsGroup g = obs_wave_init(E, L, le, mreg, !LEAN, LEAN);
             if (BAND == OBS_BAND && band_moves)
                 band_mask = obs_band_skip_mask(E, MAPF_BAND_UNIT,
                                                (size_t)(R.obs + (s * BN + (size_t)(b0 + le) * E.N) * E.C * E.F * E.F),
@@ -233,7 +243,8 @@
             else ob = R.obs + s * BN * E.C * E.F * E.F;
             // the store loop in groups of four (obs_store_wave_nt); PIBT's kernels stand at their register
             // limit and spill with it: they keep the loop of one store per trip
-            obs_emit<false, ST, BAND, PIBT ? 0 : OBS_NT_GROUP>(E, L, ob, R.vec + s * BN * 4, g, b0, false, band_mask);
+            // LEAN: phases 1-3 in the one-wave form (obs_wave_rows: N <= 8 by rollout_fusable's G == 8)
+            obs_emit<false, ST, BAND, PIBT ? 0 : OBS_NT_GROUP, LEAN>(E, L, ob, R.vec + s * BN * 4, g, b0, false, band_mask);
             // SPARSE: what the slot holds now, for the next launch over it (the stream is whole until the
             // next step's obs_wave_init); ordinary vector stores of lanes 0, 4, .., 60
             if constexpr (BAND == OBS_SPARSE) obs_sparse_store(g.stream, L.swe, sp_words, (int)(threadIdx.x & 63));

@@ -313,15 +313,29 @@ __device__ inline ObsGroup obs_workgroup(const ObsLds &L, int nenv) {
     return ObsGroup{(int)threadIdx.x, (int)blockDim.x, 0, nenv, L.stream, L.mapc, false};
 }
 
+// The map rows of env le that the wave holds in registers (lane k = word k), into its LDS copy
+__device__ inline void obs_wave_map(const ObsLds &L, int le, uint32_t mreg) {
+    const int lane = lane_id();
+    if (lane < L.rowsz) L.mapc[le * L.rowsz + lane] = mreg;
+}
 // One wave observes env le of the workgroup (per_env layout): zero its stream
-// and occupancy, copy the map rows it holds in registers (lane k = word k).
-__device__ inline ObsGroup obs_wave_init(const DevEnv &e, const ObsLds &L, int le, uint32_t mreg) {
+// and occupancy, copy the map rows.  copy_map = false: the caller stored the rows
+// once before its step loop (obs_wave_map; the map does not change within a launch).
+// zero16: the stream is zeroed in uint4s (swe is a multiple of 4 words and every env's
+// stream starts 16-B aligned: obs_layout), a third of the word loop's trips.
+__device__ inline ObsGroup obs_wave_init(const DevEnv &e, const ObsLds &L, int le, uint32_t mreg, bool copy_map = true,
+                                         bool zero16 = false) {
     const int lane = lane_id();
     uint32_t *st = L.stream + (size_t)le * L.swe;
-    for (int k = lane; k < L.swe; k += 64) st[k] = 0u;
+    if (zero16) {
+        uint4 *st4 = reinterpret_cast<uint4 *>(st);
+        for (int k = lane; k < (L.swe >> 2); k += 64) st4[k] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        for (int k = lane; k < L.swe; k += 64) st[k] = 0u;
+    }
     for (int k = lane; k < L.rowsz; k += 64) L.occ[le * L.rowsz + k] = 0u;
     uint32_t *mp = L.mapc + le * L.rowsz;
-    if (lane < L.rowsz) mp[lane] = mreg;
+    if (copy_map) obs_wave_map(L, le, mreg);
     ObsGroup g{lane, 64, le, 1, st, mp, true};
     obs_sync(g);
     return g;
@@ -417,7 +431,100 @@ __device__ __forceinline__ void obs_store_wave_nt(const float4 *lut, const uint3
     if (iters % GN) obs_nt_group<BAND, false, GN>(rs, lut, swp, sh, hsh, voff, band_mask, iters % GN);
 }
 
-template <bool BFSCH = true, int ST = OBS_PLAIN, int BAND = 0, int GN = 0>
+// ---- phases 1-3 of obs_emit for one wave observing its own env (obs_emit<.., WV = true>: G.wave, G.nenv == 1,
+// N <= 8, F <= 16, no BFS channel) ----
+// The workgroup form below numbers its tasks k = tid, tid + nt, .. and divides by the run-time N and F to
+// find the env, the agent and the FOV row of each: generic signed divisions, ~17 VALU instructions apiece,
+// issued by the whole wave.  Here the env is G.le0 and lane l works for agent l >> 3: its FOV rows are
+// (l & 7) and (l & 7) + 8 -- shifts, and at most two rows per lane for every accepted F -- and the agent's
+// cell, window corner and stream offset are computed once per lane, not once per row task.  The agent's
+// head lane (l & 7 == 0) does phase 1 and phase 3.  The same bits are ORed into the same stream words
+// (or_bits / set_bit: atomic ORs, whose order does not matter), so the stream is the workgroup form's.
+__device__ inline void obs_wave_occ(const DevEnv &e, const ObsLds &L, const ObsGroup &G, int KB) {
+    const int k = G.tid >> 3;
+    if ((G.tid & 7) == 0 && k < KB) {
+        const uint32_t p = L.spos[G.le0 * e.N + k];
+        const int r = prow(p), c = pcol(p);
+        const int rr = r + e.P, cc = c + e.P;
+        atomicOr(&L.occ[G.le0 * L.rowsz + rr * e.WW + (cc >> 5)], 1u << (cc & 31));
+        L.idg[G.le0 * e.H * e.W + r * e.W + c] = (uint8_t)k;
+    }
+}
+
+__device__ inline void obs_wave_rows(const DevEnv &e, const ObsLds &L, float *__restrict__ vec, const ObsGroup &G,
+                                     int b, int KB) {
+    using namespace obsd;
+    const int k = G.tid >> 3, j = G.tid & 7;
+    if (k >= KB) return;
+    const int N = e.N, F = e.F, FF = F * F, half = F / 2;
+    const int le = G.le0, kw = le * N;
+    uint32_t *stream = G.stream;
+    const uint32_t *occ = L.occ + le * L.rowsz;
+    const uint8_t *idg = L.idg + le * e.H * e.W;
+    const uint32_t p = L.spos[kw + k];
+    const int pr = prow(p), pc = pcol(p);
+    const int tr = pr - half, tc = pc - half;
+    const int abase = k * (e.C * FF);                // the agent's block in the env's stream
+    const int R2 = e.R * e.R;
+    // ---- phase 2: the lane's FOV rows ----
+    for (int y0 = 0; y0 < F; y0 += 8) {               // a scalar count: one trip for F <= 8, two above
+        const int y = y0 + j;
+        if (y >= F) continue;
+        const int rr = tr + y;                       // map row of this FOV row
+        const int prow_idx = rr + e.P;               // padded row (always inside)
+        const uint32_t seg0 = seg_at(G.mapc + prow_idx * e.WW, e.WW, tc + e.P, F);
+        const uint32_t segA = seg_at(occ + prow_idx * e.WW, e.WW, tc + e.P, F);
+        const uint32_t self = (y == half) ? (1u << half) : 0u;
+        const int base = abase + y * F;
+        or_bits(stream, base, seg0 | self, F);
+        or_bits(stream, base + FF, segA & ~self, F);
+        // visibleAgents (the agents of this FOV row) -> their goals clamped to the FOV (ch3)
+        for (uint32_t others = segA & ~self; others; others &= others - 1u) {
+            const int cc = tc + __builtin_ctz(others);
+            const uint32_t g = L.sgoal[kw + idg[rr * e.W + cc]];
+            const int xr = min(max(prow(g), tr), tr + F - 1);
+            const int xc = min(max(pcol(g), tc), tc + F - 1);
+            set_bit(stream, abase + 3 * FF + (xr - tr) * F + (xc - tc));
+        }
+        if (e.use_da && rr >= 0 && rr < e.H) {      // ch4 danger area
+            const uint32_t hn = L.shn[le];
+            const int dy = prow(hn) - rr;
+            if (dy * dy <= R2) {
+                const int w = isqrt_floor(R2 - dy * dy);
+                const int c0 = max(max(pcol(hn) - w, 0), tc), c1 = min(min(pcol(hn) + w, e.W - 1), tc + F - 1);
+                if (c0 <= c1) or_bits(stream, base + 4 * FF, ((1u << (c1 - c0 + 1)) - 1u) << (c0 - tc), F);
+            }
+        }
+    }
+    if (j != 0) return;
+    // ---- phase 3, on the agent's head lane: own goal (ch2), human next position (ch4), HP cells (ch5), vector ----
+    const uint32_t gl = L.sgoal[kw + k];
+    const int gr = prow(gl), gc = pcol(gl);
+    if (tr <= gr && gr < tr + F && tc <= gc && gc < tc + F) set_bit(stream, abase + 2 * FF + (gr - tr) * F + (gc - tc));
+    const uint32_t hn = L.shn[le];
+    const int hr = prow(hn), hc = pcol(hn);
+    if (tr <= hr && hr < tr + F && tc <= hc && hc < tc + F) set_bit(stream, abase + 4 * FF + (hr - tr) * F + (hc - tc));
+    for (int q = 0; q < L.shpn[le]; ++q) {            // ch5: in-map cells inside the FOV
+        const uint32_t cell = L.shp[le * e.k_predict + q];
+        const int r = prow(cell), c = pcol(cell);
+        if (tr <= r && r < tr + F && tc <= c && c < tc + F) set_bit(stream, abase + 5 * FF + (r - tr) * F + (c - tc));
+    }
+    // vector: obs_emit's phase 3 has the rule (float64 square root and divides, then float32)
+    const int dx = gr - pr, dy = gc - pc;
+    const int d2 = dx * dx + dy * dy;
+    float4 v;
+    if (d2 == 0) {
+        v = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        const double d = __builtin_sqrt((double)d2);
+        v = make_float4((float)((double)dx / d), (float)((double)dy / d), (float)d, 0.f);
+    }
+    reinterpret_cast<float4 *>(vec)[(size_t)b * N + k] = v;
+}
+
+// WV: the group is one wave observing one env (G.wave, G.nenv == 1) of at most 8 agents with no BFS channel:
+// phases 1-3 take obs_wave_occ / obs_wave_rows above, without divisions.
+template <bool BFSCH = true, int ST = OBS_PLAIN, int BAND = 0, int GN = 0, bool WV = false>
 __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restrict__ obs, float *__restrict__ vec,
                                 const ObsGroup &G, int b0, bool skip_band = false, uint32_t band_mask = 0) {
     using namespace obsd;
@@ -437,6 +544,9 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
 #else
     const int KB = K;
 #endif
+    static_assert(!(WV && BFSCH), "the one-wave path has no BFS channel");
+    if constexpr (WV) obs_wave_occ(e, L, G, KB);
+    else
     for (int k = tid; k < KB; k += nt) {
         const int le = G.le0 + k / N;
         const int r = prow(L.spos[kw + k]), c = pcol(L.spos[kw + k]);
@@ -465,6 +575,8 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
 
     // ---- phase 2: (agent, FOV row) ----
     const int R2 = e.R * e.R;
+    if constexpr (WV) obs_wave_rows(e, L, vec, G, b0, KB);      // phases 2 and 3
+    else
     for (int task = tid; task < KB * F; task += nt) {
         const int k = task / F, y = task - k * F;
         const int le = G.le0 + k / N;
@@ -540,6 +652,7 @@ __device__ inline void obs_emit(const DevEnv &e, const ObsLds &L, float *__restr
     }
 
     // ---- phase 3: per agent: own goal (ch2), human next position (ch4), HP cells (ch5), vector ----
+    if constexpr (!WV)
     for (int k = tid; k < KB; k += nt) {
         const int le = G.le0 + k / N;
         const int pr = prow(L.spos[kw + k]), pc = pcol(L.spos[kw + k]);

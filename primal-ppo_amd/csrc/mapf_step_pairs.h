@@ -163,11 +163,13 @@ __device__ inline void step_pairs_finish(const DevEnv &e, const PairsDeferred &d
 // (index = agent), so the step loop reads no global memory.
 // PERF (mapf_rollout_perf's kernels): the values the output stores take are also left in *pv, on the
 // agents' head lanes (zeros elsewhere), for the wave's record (mapf_perf.h).
+// so, sb: the slot a rollout's step writes its outputs to, as an offset in agents (slot * B * N) and in envs
+// (slot * B) that the storing lanes add to their index into `out`'s arrays.
 template <int NP, bool FEED, bool INLINE = false, bool RES = false, bool LDSACT = false, bool PERF = false>
 __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restrict__ actions, const StepOut &out,
                                                uint32_t flags, int slot, int gt, const ObsLds &ob, int b0,
                                                RegMap rm, PairsDeferred &dfr, EnvRegs *rs = nullptr,
-                                               StepVals *pv = nullptr) {
+                                               StepVals *pv = nullptr, size_t so = 0, size_t sb = 0) {
     using namespace pairs;
     constexpr int L = NP * NP;
     constexpr uint32_t ROW = (1u << NP) - 1u;
@@ -202,6 +204,7 @@ __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restr
     const bool vi = i < N, vj = j < N;
     const bool head = j == 0;               // lane that writes agent i's outputs
     const size_t ai = (size_t)b * N + i, aj = (size_t)b * N + j;
+    const size_t ao = ai + so;              // agent i's index into the outputs
     const uint32_t env_id = e.env_offset + (uint32_t)b;
     // ---- every per-env / per-agent load is issued here, in two dependent rounds
     const uint32_t clock = RES ? rs->clock : e.clock[b];
@@ -337,17 +340,17 @@ __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restr
     }
     if (vi) {
         if (head) {
-            if (out.status) out.status[ai] = (int8_t)st;
-            if (out.reward) out.reward[ai] = rw;
-            if (out.cost) out.cost[ai] = cost;
+            if (out.status) out.status[ao] = (int8_t)st;
+            if (out.reward) out.reward[ao] = rw;
+            if (out.cost) out.cost[ao] = cost;
         }
         if (out.train_valid) {
-            float *tv = out.train_valid + ai * NA;
+            float *tv = out.train_valid + ao * NA;
             for (int t = j; t < NA; t += NP)
                 tv[t] = (((good >> t) & 1u) || (((keys >> t) & 1u) && !((conf >> t) & 1u))) ? 1.f : 0.f;
         }
     }
-    if (li == 0 && out.shadow_goals) out.shadow_goals[b] = __popc(shadow);
+    if (li == 0 && out.shadow_goals) out.shadow_goals[(size_t)b + sb] = __popc(shadow);
     if constexpr (PERF) {
         if (vi && head) { pv->st = st; pv->cost = cost; }
         pv->nshadow = __popc(shadow);
@@ -584,10 +587,10 @@ __device__ __forceinline__ void step_pairs_env(const DevEnv &e, int32_t *__restr
     if (vi && head) {
         const int d0 = prow(hp_new) - nr, d1 = pcol(hp_new) - nc;
         const float cv = (d0 * d0 + d1 * d1 <= e.constr_d2) ? 1.f : 0.f;
-        if (out.actions_fixed) out.actions_fixed[ai] = fixed;
-        if (out.goals_reached) out.goals_reached[ai] = reached ? 1.f : 0.f;
-        if (out.constraints) out.constraints[ai] = cv;
-        if (out.reward_total) out.reward_total[ai] = reached ? rw + e.goal_reward : rw;
+        if (out.actions_fixed) out.actions_fixed[ao] = fixed;
+        if (out.goals_reached) out.goals_reached[ao] = reached ? 1.f : 0.f;
+        if (out.constraints) out.constraints[ao] = cv;
+        if (out.reward_total) out.reward_total[ao] = reached ? rw + e.goal_reward : rw;
         if constexpr (PERF) {
             pv->reached = reached;
             pv->cv = cv == 1.f;
